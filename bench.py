@@ -8,11 +8,12 @@ compress all 32 chunks (one batched call) + decompress them (one batched call), 
 resident in HBM.  value = ranks * steps * 2 * N / wall  (N = 128 MiB per rank; weak scaling: every rank
 owns its own 4 channels, there is no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `roofline` is for the kernel with the largest share of device time
 (HIP events recorded on the engine's stream around every launch); `kernels` lists all four.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs below) for output-to-output comparison of two builds.
 `cpu_baseline` times the oracle (CPU restatement, oracle/) on the host cores -- it is the checker
 being timed, never part of the measured GPU path.
 """
@@ -233,6 +234,54 @@ def measure_copy_peak(nbytes=256 << 20, reps=12):
         best = gbps if best is None or gbps > best else best
     del a, b
     return round(best, 1)
+
+
+DUMP_SEED = 20240917
+DUMP_LEAD = 4096                  # leading bytes of every compressed chunk dumped whole (header + the first streams)
+DUMP_CHUNK_SAMPLES = 1 << 17      # further positions per compressed chunk, one seeded set for all chunks
+DUMP_PIXEL_SAMPLES = 1 << 22      # seeded pixel positions of the decompressed batch
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, comp, comp_off, comp_sizes, pixels, chunk_off, chunk_bytes, dtype):
+    """Write what one batched step handed back -- compressed chunks + their sizes, decompressed pixels -- as float32 / float64 .npy.
+
+    comp: the compressed batch (uint8, chunk i at comp_off[i], comp_sizes[i] bytes); pixels: the decompressed batch (uint8, chunk i
+    at chunk_off[i], chunk_bytes[i] bytes), read as `dtype`.  The whole of both is covered by a CRC-32 per chunk; the bytes and
+    pixels themselves by a sample whose positions depend only on the geometry (DUMP_SEED), so two builds compare position by
+    position (the pixel positions are not stored: they follow from DUMP_SEED and the pixel count).  A sampled position past the
+    end of its compressed chunk reads -1.  Returns {name: shape}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    comp = np.asarray(comp, np.uint8)
+    pixels = np.asarray(pixels, np.uint8)
+    comp_sizes = np.asarray(comp_sizes, np.int64)
+    span = int(np.max(np.diff(np.append(comp_off, comp.size))))          # the room of one compressed chunk
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    lead = np.arange(min(DUMP_LEAD, span), dtype=np.int64)
+    rest = np.sort(lead.size + rng.choice(span - lead.size, size=min(DUMP_CHUNK_SAMPLES, span - lead.size), replace=False))
+    pos = np.concatenate([lead, rest])
+    sample = np.full((len(comp_off), pos.size), -1.0, np.float32)
+    for i, (o, n) in enumerate(zip(comp_off, comp_sizes)):
+        k = int(np.searchsorted(pos, n))
+        sample[i, :k] = comp[int(o) + pos[:k]]
+    pix = pixels.view(dtype)
+    exact32 = np.dtype(dtype).itemsize <= 2 or np.dtype(dtype) == np.float32    # every value of these types is a float32
+    pix_idx = np.sort(rng.choice(pix.size, size=min(DUMP_PIXEL_SAMPLES, pix.size), replace=False))
+    arrays = {
+        "compressed_sizes": comp_sizes.astype(np.float64),
+        "compressed_crc32": np.array([zlib.crc32(comp[int(o):int(o) + int(n)]) for o, n in zip(comp_off, comp_sizes)], np.float64),
+        "compressed_byte_positions": pos.astype(np.float64),
+        "compressed_bytes_sample": sample,
+        "pixels_crc32": np.array([zlib.crc32(pixels[int(o):int(o) + int(n)]) for o, n in zip(chunk_off, chunk_bytes)], np.float64),
+        "pixels_sample": pix[pix_idx].astype(np.float32 if exact32 else np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT} byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
 
 
 def _median(xs):
@@ -711,8 +760,8 @@ def run_config5(args, rank, world, local_rank, dist, red_dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 50; 200 for --config 1, 5 for --config 3)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps in front of them (default: 10; 20 for --config 1, 1 for --config 3)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--family", default="tiled", choices=["tiled", "natural", "random", "zero"])
     ap.add_argument("--zstd-clevel", type=int, default=9, help="--config 5: blosc2 clevel the chunks are made with (9 = the reference's default = zstd level 22)")
@@ -730,11 +779,18 @@ def main():
     ap.add_argument("--pmc-json", default=None, help="per-launch PMC averages to take roofline.traffic from (profiles/tools/collect.sh)")
     ap.add_argument("--filter", default=None, choices=["shuffle", "bitshuffle", "none"],
                     help="default: what the configuration names (byte shuffle; bitshuffle for 3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--config 2 / 4: after the timed steps, write what the last step computed (compressed sizes, CRC-32 of every "
+                         "compressed and decompressed chunk, a fixed seeded sample of the compressed bytes and of the pixels) as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.config in (1, 3) and args.steps == 50 and "--steps" not in sys.argv:
-        args.steps = 200 if args.config == 1 else 5            # (a step of configs[0] is one 1 MiB chunk, of configs[2] a pass over 96 chunks)
-    if args.config in (1, 3) and "--warmup" not in sys.argv:
-        args.warmup = 20 if args.config == 1 else 1
+    if args.steps is None:
+        args.steps = {1: 200, 3: 5}.get(args.config, 50)       # (a step of configs[0] is one 1 MiB chunk, of configs[2] a pass over 96 chunks)
+    if args.warmup is None:
+        args.warmup = {1: 20, 3: 1}.get(args.config, 10)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and args.config not in (2, 4):
+        ap.error("--dump-outputs is defined for the batched path of --config 2 / 4")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -959,6 +1015,9 @@ def main():
     if not torch.equal(d_out, d_raw) and not no_verify:
         print("bench.py: pixels differ after the timed region", file=sys.stderr)
         sys.exit(3)
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step handed back (rank 0's share), before the legs below reuse the buffers
+        dump_outputs(args.dump_outputs, d_comp.cpu().numpy(), comp_off, cbytes, d_out.cpu().numpy(), raw_off, nbytes, DTYPE)
 
     # ---- a measured copy peak beside the 8 TB/s specification, and the OTHER face of the codec (natural family) in the same line ----
     copy_peak = natural = dtypes = None

@@ -1,7 +1,7 @@
 // tests/cpp/ref_headers_test.cpp -- the REFERENCE'S OWN host headers over this repository's C ABI.
 //
-// Compiled only in the build container, by tests/test_reference_headers.py, with
-//     -I /root/reference/compressed_image/include      the reference's headers, read where they lie (nothing is copied)
+// Compiled by oracle/Makefile (`ref`, run by build()) into oracle/_ref/ and run by tests/test_reference_headers.py, with
+//     -I $(REFERENCE)/compressed_image/include         the reference's headers, read where they lie (nothing is copied)
 //     -I include                                       THIS repository's blosc2.h: the seam
 //     -I tests/cpp/compat                              <format> served by {fmt} (this image's libstdc++ has none)
 // and linked against tests/emu/libcimg_hip_mock.so (the C ABI served by the host lane emulator: no GPU here).  It replays the

@@ -46,3 +46,44 @@ def test_committed_counters_name_their_sources():
         table = json.load(f)
     assert isinstance(table.get("_source_hash"), str) and len(table["_source_hash"]) >= 16
     assert "FETCH_SIZE" in table["cimg_encode_streams"] and "WRITE_SIZE" in table["cimg_decode_lean"]
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """--dump-outputs: float32 / float64 arrays only, CRC-32 over every chunk, the sampled bytes and pixels at positions that
+    depend on the geometry alone (two builds compare position by position), -1 past the end of a compressed chunk."""
+    import zlib
+
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    n, chunk, stride = 3, 8192, 8192 + 64
+    comp = rng.integers(0, 256, n * stride, dtype=np.uint8)
+    comp_off = np.arange(n) * stride
+    sizes = np.array([100, 5000, stride], np.int64)
+    pixels = rng.standard_normal(n * chunk // 2).astype(np.float16).view(np.uint8)     # finite values: NaN is in no set
+    pix_off, pix_n = np.arange(n) * chunk, np.full(n, chunk)
+    shapes = b.dump_outputs(str(tmp_path / "a"), comp, comp_off, sizes, pixels, pix_off, pix_n, np.float16)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["compressed_sizes"].tolist() == sizes.tolist()
+    assert got["compressed_crc32"].tolist() == [zlib.crc32(comp[o:o + s]) for o, s in zip(comp_off, sizes)]
+    assert got["pixels_crc32"].tolist() == [zlib.crc32(pixels[o:o + chunk]) for o in pix_off]
+    pos = got["compressed_byte_positions"].astype(np.int64)
+    for i in range(n):
+        inside = pos < sizes[i]
+        assert np.array_equal(got["compressed_bytes_sample"][i, inside], comp[comp_off[i] + pos[inside]])
+        assert np.all(got["compressed_bytes_sample"][i, ~inside] == -1)
+    assert np.all(np.isin(got["pixels_sample"], pixels.view(np.float16).astype(np.float32)))
+    # other bytes, same geometry: the same positions
+    b.dump_outputs(str(tmp_path / "b"), comp[::-1].copy(), comp_off, sizes, pixels[::-1].copy(), pix_off, pix_n, np.float16)
+    assert np.array_equal(np.load(tmp_path / "b" / "compressed_byte_positions.npy"), got["compressed_byte_positions"])
+
+
+def test_dump_outputs_fits_64_mb_at_the_headline_geometry():
+    """BASELINE configs[1]: 32 chunks of 4 MiB float16; the dump stays within 64 MB whatever the chunks compress to."""
+    b = _bench()
+    n = 128 << 20 >> 22
+    stride = b.CHUNK + 64
+    rows = b.DUMP_LEAD + b.DUMP_CHUNK_SAMPLES
+    total = 2 * 8 * n + 8 * n + 8 * rows + 4 * n * rows + 4 * b.DUMP_PIXEL_SAMPLES
+    assert rows <= stride and total <= b.DUMP_LIMIT <= 64 << 20
