@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "plan.h"
+#include "wide_plan.h"
 #include "assemble_kernel.h"
 #include "deinterleave_kernel.h"
 #include "zstd_kernel.h"
@@ -177,6 +178,29 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_blocks(DecodeArgs 
 #endif
 }
 
+// Blocks beyond the normal kernels' LDS (wide_kernel.h, up to 256 KiB).  Encode: single-wave workgroups, 16 KiB of LDS each (the
+// hash table), pulling streams from one counter.  Decode: persistent 256-thread workgroups, workgroup k decodes blocks k, k + G, ...
+// in its own device-memory slot.
+extern "C" __global__ __launch_bounds__(64) void cimg_encode_wide(WideEncodeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    WideEncodeWave ww(a, reinterpret_cast<uint32_t*>(lds), (int)blockIdx.x);
+    ww.run();
+}
+
+extern "C" __global__ __launch_bounds__(256) void cimg_decode_wide(WideDecodeArgs a)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint8_t* const slot = a.slots + (size_t)blockIdx.x * (size_t)a.d.lds_bytes;
+    for (int b = (int)blockIdx.x; b < a.d.total_blocks; b += (int)gridDim.x) {
+        WideDecodeBlock blk(a.d, slot, b);
+        blk.phase_a_wide(wave);
+        __syncthreads();
+        blk.phase_b(wave);
+        __syncthreads();                                         // (the slot is the next block's)
+    }
+}
+
 // ====================================================================================================
 //  engine
 // ====================================================================================================
@@ -298,6 +322,14 @@ struct cimg_engine {
         DecodeArgs da{};
     } dflight;
     bool dflight_open = false;            // between cimg_decompress_batch_device_begin and _fetch
+    // a decode batch with wide blocks (wide_plan.h): its normal chunks are the batch of dflight, its wide ones went to cimg_decode_wide
+    struct WideFlight {
+        bool active = false;
+        std::vector<int> normal, wide;    // chunk indices of the caller's batch
+    } wflight;
+    DevBuf wide_planes, wide_queue, wide_slots, descs_wide;
+    PinBuf h_descs_wide, h_wst;
+    std::vector<uint8_t> shadow_wide;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
     bool claunched = false;               // compress_launch got past the planner and the allocations: h_out holds (or will hold) this batch's sizes
 
@@ -437,6 +469,8 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_LAYOUT: return "cimg_layout_chunks";
     case CIMG_K_EMIT: return "cimg_emit_blocks";
     case CIMG_K_DECODE: return "cimg_decode_blocks";
+    case CIMG_K_ENCODE_WIDE: return "cimg_encode_wide";
+    case CIMG_K_DECODE_WIDE: return "cimg_decode_wide";
     case CIMG_K_DEINTERLEAVE: return "cimg_deinterleave";
     case CIMG_K_DECODE_ZSTD: return "cimg_decode_zstd";
     case CIMG_K_ENCODE_ZSTD: return "cimg_encode_streams_zstd";
@@ -515,9 +549,10 @@ void cimg_engine_destroy(cimg_engine* e)
     (void)hipStreamSynchronize(e->stream);
     e->drain_timing();
     for (EventPair& ev : e->free_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-    for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan})
+    for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
+                    &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide})
         if (b->p) (void)hipFree(b->p);
-    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec})
+    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst})
         if (b->p) (void)hipHostFree(b->p);
     (void)hipStreamDestroy(e->stream);
     if (e->s_h2d) { (void)hipStreamSynchronize(e->s_h2d); (void)hipStreamDestroy(e->s_h2d); }
@@ -654,6 +689,38 @@ static HostCParams to_host(const cimg_cparams* p)
     return h;
 }
 
+// A compress batch the normal planner refused for size alone (wide_plan.h): every stream through cimg_encode_wide, then the two
+// assembly kernels.  compress_finish() reads the sizes as for any batch.
+static int compress_launch_wide(cimg_engine* e, EncodePlan& plan, int32_t nchunks, const void* d_raw, void* d_comp)
+{
+    int rc;
+    if ((rc = e->reserve(e->recs, sizeof(StreamRec) * (size_t)plan.total_blocks * plan.cp.streams_per_block))) return rc;
+    if ((rc = e->reserve(e->layout, sizeof(ChunkLayout) * (size_t)nchunks))) return rc;
+    if ((rc = e->reserve(e->h_out, sizeof(ChunkLayout) * ((size_t)nchunks + 1)))) return rc;
+    if ((rc = e->reserve(e->scratch, (size_t)plan.total_blocks * plan.cp.slot_bytes + 64))) return rc;
+    ChunkLayout* lay_host = nullptr;
+    if ((rc = e->device_alias(e->h_out, &lay_host))) return rc;
+    if ((rc = e->upload_descs(e->descs_enc, e->shadow_enc, e->h_descs, plan.descs.data(), sizeof(ChunkDesc) * (size_t)nchunks))) return rc;
+    const int items = plan.total_blocks * plan.cp.streams_per_block;
+    // as many single-wave workgroups as a few per CU (each stages its shuffled stream in a plane of its own), never more than streams
+    const int grid = std::max(1, std::min(items, 4 * e->num_cus));
+    const int64_t stride = ((int64_t)plan.cp.max_blocksize + 255) & ~(int64_t)255;
+    if ((rc = e->reserve(e->wide_planes, (size_t)stride * (size_t)grid + 64))) return rc;
+    if ((rc = e->reserve(e->wide_queue, 64))) return rc;
+    if ((rc = e->hip(hipMemsetAsync(e->wide_queue.p, 0, 64, e->stream), "wide queue memset"))) return rc;
+    ((ChunkLayout*)e->h_out.p)[nchunks].cbytes = 0;
+    e->claunched = true;
+    WideEncodeArgs wa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (uint8_t*)e->scratch.p,
+                      (StreamRec*)e->recs.p, plan.total_blocks, plan.uniform_nblocks, (uint8_t*)e->wide_planes.p, stride,
+                      (uint32_t*)e->wide_queue.p};
+    if ((rc = e->launch(CIMG_K_ENCODE_WIDE, cimg_encode_wide, wa, grid, 64, LZ4_HASH_BYTES + 64))) return rc;
+    AssembleArgs aa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (const uint8_t*)e->scratch.p,
+                    (const StreamRec*)e->recs.p, (uint8_t*)d_comp, (ChunkLayout*)e->layout.p, plan.uniform_nblocks, lay_host, 1};
+    if ((rc = e->launch(CIMG_K_LAYOUT, cimg_layout_chunks, aa, nchunks, 64, 0))) return rc;
+    if ((rc = e->launch(CIMG_K_EMIT, cimg_emit_blocks, aa, plan.total_blocks, 256, 0))) return rc;
+    return 0;
+}
+
 // the kernels of one compress batch, enqueued on the engine's stream; compress_finish() waits and fetches the sizes
 // inputs_behind_stream: the pixels are produced by work already enqueued on e->stream (a copy the stream waits for, the
 // deinterleave kernel): a launch on another stream has to wait for that too.  The device-resident entry points pass false --
@@ -667,6 +734,8 @@ static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     e->begin_batch(0);
     EncodePlan plan;
     int rc = plan_encode_batch(to_host(p), nchunks, raw_off, nbytes, comp_off, destsize, &plan);
+    if (rc == ERR_CODEC_SUPPORT && plan_encode_wide(to_host(p), nchunks, raw_off, nbytes, comp_off, destsize, &plan) == 0)
+        return compress_launch_wide(e, plan, nchunks, d_raw, d_comp);
     if (rc < 0) return e->fail(rc, "compress batch rejected by the planner (code %d): codec %d / filter pipeline / block size %d not available on the GPU path",
                                rc, p->compcode, p->blocksize);
     if ((rc = e->reserve(e->recs, sizeof(StreamRec) * (size_t)plan.total_blocks * plan.cp.streams_per_block))) return rc;
@@ -888,6 +957,10 @@ int cimg_compress_batch_device_fetch(cimg_engine* e, int32_t nchunks, int32_t* c
     return compress_finish(e, nchunks, cbytes);
 }
 
+static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                  const int32_t* nbytes, const int32_t* blocksize, void* d_raw, const int64_t* raw_off,
+                                  const int32_t* comp_size, bool inputs_behind_stream);
+
 // the kernels of one decode batch, enqueued on the engine's stream; decompress_finish() waits, launches the general
 // kernel late if the lean one left blocks behind, and collects the status words
 static int decompress_launch(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
@@ -899,8 +972,14 @@ static int decompress_launch(cimg_engine* e, int32_t nchunks, const void* d_comp
     e->dflight.lean_grid = 0;
     e->dflight.nchunks = 0;
     e->begin_batch(1);
+    e->wflight.active = false;
     DecodePlan plan;
     int rc = plan_decode_batch(nchunks, comp_off, nbytes, blocksize, raw_off, &plan, comp_size);
+    if (rc == ERR_CODEC_SUPPORT) {
+        WideDecodePlan wp;
+        if (plan_decode_wide(nchunks, comp_off, nbytes, blocksize, raw_off, &wp, comp_size) == 0)
+            return decompress_launch_wide(e, wp, nchunks, d_comp, comp_off, nbytes, blocksize, d_raw, raw_off, comp_size, inputs_behind_stream);
+    }
     if (rc < 0) return e->fail(rc, "decompress batch rejected by the planner (code %d)", rc);
     if (plan.lds_lean > 0) plan.lds_lean += e->lean_lds_pad;
     const size_t desc_bytes = sizeof(ChunkDesc) * (size_t)nchunks;
@@ -1023,7 +1102,75 @@ static int decompress_launch(cimg_engine* e, int32_t nchunks, const void* d_comp
     return rc;
 }
 
+// A decode batch with wide blocks: the normal chunks go through decompress_launch as a batch of their own (dflight), the wide
+// ones through cimg_decode_wide behind them on the same stream; decompress_finish() merges the status words.
+static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                  const int32_t* nbytes, const int32_t* blocksize, void* d_raw, const int64_t* raw_off,
+                                  const int32_t* comp_size, bool inputs_behind_stream)
+{
+    (void)nchunks;
+    int rc = 0;
+    if (!wp.normal.empty()) {
+        const size_t nn = wp.normal.size();
+        std::vector<int64_t> co(nn), ro(nn);
+        std::vector<int32_t> nb(nn), bs(nn), cs(comp_size ? nn : 0);
+        for (size_t k = 0; k < nn; k++) {
+            const int i = wp.normal[k];
+            co[k] = comp_off[i]; ro[k] = raw_off[i]; nb[k] = nbytes[i]; bs[k] = blocksize[i];
+            if (comp_size) cs[k] = comp_size[i];
+        }
+        if ((rc = decompress_launch(e, (int32_t)nn, d_comp, co.data(), nb.data(), bs.data(), d_raw, ro.data(),
+                                    comp_size ? cs.data() : nullptr, inputs_behind_stream))) return rc;
+    }
+    const int nw = (int)wp.wide.size();
+    const DecodePlan& plan = wp.plan;
+    if ((rc = e->upload_descs(e->descs_wide, e->shadow_wide, e->h_descs_wide, plan.descs.data(), sizeof(ChunkDesc) * (size_t)nw))) return rc;
+    if ((rc = e->reserve(e->h_wst, sizeof(int32_t) * (size_t)nw))) return rc;
+    int32_t* st_dev = nullptr;
+    if ((rc = e->device_alias(e->h_wst, &st_dev))) return rc;
+    memset(e->h_wst.p, 0, sizeof(int32_t) * (size_t)nw);
+    // persistent workgroups, two per CU: the slots (one block's staging each) are bounded by them, not by the batch
+    const int grid = std::max(1, std::min(plan.total_blocks, 2 * e->num_cus));
+    if ((rc = e->reserve(e->wide_slots, (size_t)wp.slot_bytes * (size_t)grid + 64))) return rc;
+    WideDecodeArgs wa{};
+    wa.d = DecodeArgs{(const ChunkDesc*)e->descs_wide.p, nw, (const uint8_t*)d_comp, (uint8_t*)d_raw, st_dev, wp.slot_bytes, nullptr,
+                      plan.uniform_nblocks, nullptr, 0, nullptr, plan.total_blocks, 0, 1, 0};
+    wa.slots = (uint8_t*)e->wide_slots.p;
+    e->wflight.normal = wp.normal;
+    e->wflight.wide = wp.wide;
+    if ((rc = e->launch(CIMG_K_DECODE_WIDE, cimg_decode_wide, wa, grid, 256, 0))) return rc;
+    e->wflight.active = true;
+    e->dflight.launched = true;                   // (the callers' "is there something to finish" test: there is, with or without normal chunks)
+    return 0;
+}
+
+static int decompress_finish_normal(cimg_engine* e, int32_t* status);
+
 static int decompress_finish(cimg_engine* e, int32_t* status)
+{
+    if (!e->wflight.active) return decompress_finish_normal(e, status);
+    e->wflight.active = false;
+    const std::vector<int> normal = e->wflight.normal, wide = e->wflight.wide;
+    std::vector<int32_t> nst(normal.size(), 0);
+    const int rc_normal = normal.empty() ? cimg_engine_synchronize(e) : decompress_finish_normal(e, nst.data());
+    if (!normal.empty() && rc_normal) (void)cimg_engine_synchronize(e);      // (a failing normal batch may return before the wide launch is done)
+    bool chunk_error = false;
+    for (int32_t v : nst) chunk_error |= v < 0;
+    if (rc_normal && !chunk_error) return rc_normal;                          // not a chunk's status: the batch failed as a whole
+    const int32_t* wst = (const int32_t*)e->h_wst.p;
+    int first = 0;
+    std::vector<int32_t> all(normal.size() + wide.size(), 0);
+    for (size_t k = 0; k < normal.size(); k++) all[(size_t)normal[k]] = nst[k];
+    for (size_t k = 0; k < wide.size(); k++) all[(size_t)wide[k]] = wst[k];
+    for (size_t i = 0; i < all.size(); i++) {
+        if (status) status[i] = all[i];
+        if (!first && all[i] < 0) first = all[i];
+    }
+    if (first) return e->fail(first, "chunk decode failed with blosc2 error %d", first);
+    return 0;
+}
+
+static int decompress_finish_normal(cimg_engine* e, int32_t* status)
 {
     const cimg_engine::DecodeFlight& f = e->dflight;
     if (!f.launched) return cimg_engine_synchronize(e);          // nothing of this batch was enqueued (planner / allocation failure)
@@ -1247,7 +1394,7 @@ int cimg_decompress_batch_device_fetch(cimg_engine* e, int32_t* status)
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     if (!e->dflight_open) return e->fail(ERR_INVALID_PARAM, "no decompress batch is in flight (cimg_decompress_batch_device_begin comes first)");
     e->dflight_open = false;
-    if (e->dflight.nchunks <= 0) return 0;
+    if (e->dflight.nchunks <= 0 && !e->wflight.active) return 0;
     return decompress_finish(e, status);
 }
 

@@ -1,0 +1,361 @@
+// wide_kernel.h -- blocks whose streams or staging do not fit the LDS of the normal kernels (blocks up to 256 KiB, LZ4 / LZ4HC
+// write, LZ4 / LZ4HC / BloscLZ read).  wide_plan.h decides which batches come here; engine.hip launches the two kernels.
+//
+//   cimg_encode_wide   persistent single-wave workgroups pull streams from one atomic counter.  A stream that needs the byte
+//                      shuffle is staged into the wave's own plane in device memory (a stream that is a plain slice of the
+//                      pixels is read where it lies); the LZ4 hash table stays in LDS.  The encoder is liblz4 1.9.3's
+//                      LZ4_compress_fast walked in wave-uniform order -- the byU16 regime below 65 547 bytes (8192 x u16,
+//                      LZ4_hash4), the byU32 regime from there on (4096 x u32, LZ4_hash5, candidates more than 65 535 bytes
+//                      back rejected) -- with the 64 lanes used for match extension and literal copies.  Records and
+//                      payloads go to the scratch slots exactly as the normal encoder leaves them; cimg_layout_chunks /
+//                      cimg_emit_blocks put the chunks together behind the launch.
+//   cimg_decode_wide   persistent 256-thread workgroups, each owning one block-sized scratch slot in device memory, walk the
+//                      batch's blocks.  The block body is DecodeBlock (decode_kernel.h) with its "LDS" in the slot: the same
+//                      header walk (WideDecodeBlock below: each stream decoded relative to its own region), the same wave
+//                      decoders and unshuffle, so every bound it keeps (comp_size / cbytes on reads, the slot size on writes)
+//                      holds as it does there.
+//                      Matches are copied from the slot, at most 64 KiB (LZ4) / ~72 KiB (BloscLZ far) back: L2-resident.
+#pragma once
+#include "encode_kernel.h"
+
+namespace cimg {
+
+enum : int {
+    WIDE_MAX_BLOCK = 262144,             // largest block the wide kernels take (the planner refuses anything above)
+    LZ4_U32_HASHLOG = 12,                // liblz4: LZ4_HASHLOG - 1 for the byU32 table (4096 entries, the same 16 KiB)
+    LZ4_U16_HASHLOG = 13,
+    LZ4_LIMIT_64K = 65536 + 12 - 1,      // liblz4 LZ4_64Klimit: from this input size on the byU32 regime is used
+    LZ4_DIST_MAX = 65535,
+};
+
+struct WideEncodeArgs {
+    const ChunkDesc* descs;
+    int32_t nchunks;
+    CodecParams p;
+    const uint8_t* raw;        // pixels at raw + desc.raw_off
+    uint8_t* scratch;          // block b owns scratch + b * p.slot_bytes (as EncodeArgs)
+    StreamRec* recs;           // block b, stream s -> recs[b * p.streams_per_block + s]
+    int32_t total_blocks;
+    int32_t uniform_nblocks;
+    uint8_t* planes;           // wave w stages a shuffled stream at planes + w * plane_stride
+    int64_t plane_stride;
+    uint32_t* queue;           // one counter, zero at launch
+};
+
+struct WideDecodeArgs {
+    DecodeArgs d;              // d.lds_bytes = slot bytes; d.done / d.skipped unused
+    uint8_t* slots;            // workgroup k owns slots + k * d.lds_bytes
+};
+
+CIMG_DEV uint32_t wide_rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+CIMG_DEV uint64_t wide_rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
+
+// bytes in[a + k] == in[b + k] for k = 0, 1, ... while a + k < limit: 64 compares per step
+CIMG_DEV int wide_common(const uint8_t* in, int a, int b, int limit)
+{
+    int k = 0;
+    for (;;) {
+        LV<bool> diff;
+        FOR_LANES(l) { const int i = a + k + l; diff[l] = i >= limit || in[i < limit ? i : a] != in[i < limit ? b + k + l : a]; }
+        const uint64_t m = ballot(diff);
+        if (m) return k + ctz64(m);
+        k += 64;
+    }
+}
+
+CIMG_DEV void wide_copy(const uint8_t* src, uint8_t* dst, int n)
+{
+    for (int k = 0; k < n; k += 64) { FOR_LANES(l) { if (k + l < n) dst[k + l] = src[k + l]; } }
+}
+
+// an LZ4 length extension of `rem` (rem / 255 bytes 255, then rem % 255) at out[op..); returns the new op
+CIMG_DEV int wide_len_ext(uint8_t* out, int op, int rem)
+{
+    const int full = rem / 255;
+    for (int k = 0; k < full; k += 64) { FOR_LANES(l) { if (k + l < full) out[op + k + l] = 255; } }
+    LV<int> z;
+    FOR_LANES_W(l) { z[l] = 0; if (l == 0) out[op + full] = (uint8_t)(rem - 255 * full); }
+    return op + full + 1;
+}
+
+CIMG_DEV uint32_t wide_hash(const uint8_t* p, bool u32)
+{
+    if (u32) return (uint32_t)(((wide_rd64(p) << 24) * 889523592379ull) >> (64 - LZ4_U32_HASHLOG));
+    return (wide_rd32(p) * 2654435761u) >> (32 - LZ4_U16_HASHLOG);
+}
+
+// Bit-exact LZ4_compress_fast(in, out, n, cap, accel) of liblz4 1.9.3 (noDict, 64-bit host), either table regime.
+// tab: 16 KiB of LDS.  Returns bytes written, 0 if the result does not fit cap (limited-output mode); need_out = the
+// smallest cap under which it still succeeds (the maximum of the limited-output checks' left-hand sides).
+CIMG_DEV int lz4_wide_encode(const uint8_t* in, uint32_t* tab, int n, uint8_t* out, int cap, int accel, int& need_out)
+{
+    enum { MINMATCH = 4, MFLIMIT = 12, LASTLITERALS = 5, ML_BITS = 4, ML_MASK = 15, RUN_MASK = 15, SKIP_TRIGGER = 6 };
+    if (accel < 1) accel = 1;
+    if (accel > 65537) accel = 65537;
+    const bool u32 = n >= LZ4_LIMIT_64K;
+    const bool limited = cap < n + n / 255 + 16;
+    uint16_t* tab16 = reinterpret_cast<uint16_t*>(tab);
+    for (int k = 0; k < 4096; k += 64) { FOR_LANES(l) { tab[k + l] = 0; } }
+    int ip = 0, anchor = 0, op = 0, need = 0;
+    const int mflimit_p1 = n - MFLIMIT + 1, matchlimit = n - LASTLITERALS;
+    auto get = [&](uint32_t h) -> int { return u32 ? (int)tab[h] : (int)tab16[h]; };
+    auto put = [&](uint32_t h, int pos) { LV<int> z; FOR_LANES_W(l) { z[l] = 0; if (l == 0) { if (u32) tab[h] = (uint32_t)pos; else tab16[h] = (uint16_t)pos; } } };
+    if (n >= MFLIMIT + 1) {
+        put(wide_hash(in, u32), 0);
+        ip = 1;
+        for (;;) {
+            int match = 0;
+            {   // search: probe positions with the skip schedule
+                int probe = ip, step = 1, nb = accel << SKIP_TRIGGER;
+                for (;;) {
+                    const int cur = probe, next = cur + step;
+                    step = nb++ >> SKIP_TRIGGER;
+                    if (next > mflimit_p1) goto last_literals;
+                    const uint32_t h = wide_hash(in + cur, u32);
+                    match = get(h);
+                    put(h, cur);
+                    probe = next;
+                    if (u32 && match + LZ4_DIST_MAX < cur) continue;
+                    if (wide_rd32(in + match) == wide_rd32(in + cur)) { ip = cur; break; }
+                }
+            }
+            while (ip > anchor && match > 0 && in[ip - 1] == in[match - 1]) { ip--; match--; }
+            int token_pos, token;
+            {   // literals
+                const int lit = ip - anchor;
+                token_pos = op++;
+                const int lhs = op + lit + (2 + 1 + LASTLITERALS) + lit / 255;
+                if (limited && lhs > cap) return 0;
+                need = imax(need, lhs);
+                if (lit >= RUN_MASK) { token = RUN_MASK << ML_BITS; op = wide_len_ext(out, op, lit - RUN_MASK); }
+                else token = lit << ML_BITS;
+                wide_copy(in + anchor, out + op, lit);
+                op += lit;
+            }
+            for (;;) {
+                {   // offset + match length
+                    const int off = ip - match;
+                    LV<int> z;
+                    FOR_LANES_W(l) { z[l] = 0; if (l == 0) { out[op] = (uint8_t)(off & 0xFF); out[op + 1] = (uint8_t)(off >> 8); } }
+                    op += 2;
+                    int mcode = wide_common(in, ip + MINMATCH, match + MINMATCH, matchlimit);
+                    ip += mcode + MINMATCH;
+                    const int lhs = op + (1 + LASTLITERALS) + (mcode + 240) / 255;
+                    if (limited && lhs > cap) return 0;
+                    need = imax(need, lhs);
+                    if (mcode >= ML_MASK) { token += ML_MASK; op = wide_len_ext(out, op, mcode - ML_MASK); }
+                    else token += mcode;
+                    FOR_LANES_W(l) { z[l] = 0; if (l == 0) out[token_pos] = (uint8_t)token; }
+                }
+                anchor = ip;
+                if (ip >= mflimit_p1) goto last_literals;
+                put(wide_hash(in + ip - 2, u32), ip - 2);
+                // the position right after the match
+                const uint32_t h = wide_hash(in + ip, u32);
+                match = get(h);
+                put(h, ip);
+                if ((!u32 || match + LZ4_DIST_MAX >= ip) && wide_rd32(in + match) == wide_rd32(in + ip)) {
+                    token_pos = op++;
+                    token = 0;
+                    continue;
+                }
+                break;
+            }
+            ip++;
+        }
+    }
+last_literals:
+    {
+        const int run = n - anchor;
+        const int lhs = op + run + 1 + (run + 255 - RUN_MASK) / 255;
+        if (limited && lhs > cap) return 0;
+        need = imax(need, lhs);
+        LV<int> z;
+        if (run >= RUN_MASK) {
+            FOR_LANES_W(l) { z[l] = 0; if (l == 0) out[op] = (uint8_t)(RUN_MASK << ML_BITS); }
+            op = wide_len_ext(out, op + 1, run - RUN_MASK);
+        } else {
+            FOR_LANES_W(l) { z[l] = 0; if (l == 0) out[op] = (uint8_t)(run << ML_BITS); }
+            op++;
+        }
+        wide_copy(in + anchor, out + op, run);
+        op += run;
+    }
+    need_out = need;
+    return op;
+}
+
+// true if all n bytes equal the first (any alignment)
+CIMG_DEV bool wide_is_run(const uint8_t* in, int n, uint32_t& value)
+{
+    LV<uint32_t> first;
+    FOR_LANES(l) { first[l] = in[0]; }
+    value = readlane(first, 0);
+    const uint32_t w = value * 0x01010101u;
+    const int units = n >> 4;
+    for (int c = 0; c < units; c += 64) {
+        LV<bool> bad;
+        FOR_LANES(l) {
+            const u128 q = ld128u(in + 16 * (c + l < units ? c + l : 0));
+            bad[l] = (c + l < units) & ((q.x != w) | (q.y != w) | (q.z != w) | (q.w != w));
+        }
+        if (ballot(bad)) return false;
+    }
+    LV<bool> bad;
+    FOR_LANES(l) { bad[l] = 16 * units + l < n && in[16 * units + l] != (uint8_t)value; }
+    return ballot(bad) == 0;
+}
+
+// one wave: pulls streams until the counter passes the last one
+struct WideEncodeWave {
+    const WideEncodeArgs& a;
+    uint32_t* tab;             // 16 KiB of LDS
+    int w;
+
+    CIMG_DEV WideEncodeWave(const WideEncodeArgs& a_, uint32_t* tab_, int w_) : a(a_), tab(tab_), w(w_) {}
+
+    CIMG_DEV void run()
+    {
+        const int items = a.total_blocks * a.p.streams_per_block;
+        for (int pops = 0; pops <= items; ++pops) {
+            LV<uint32_t> got;
+            FOR_LANES(l) { got[l] = 0; }
+            FOR_LANES_W(l) { if (l == 0) got[l] = atomic_add_agent(a.queue, 1u); }
+            const int item = (int)uni(readlane(got, 0));
+            if (item >= items) break;
+            run_item(item / a.p.streams_per_block, item % a.p.streams_per_block);
+        }
+    }
+
+    CIMG_DEV void run_item(int b, int s)
+    {
+        const int chunk = find_chunk(a.descs, a.nchunks, b, a.uniform_nblocks);
+        const ChunkDesc d = uniform_desc(a.descs + chunk);
+        if (d.memcpyed) return;
+        const int j = b - d.blk0;
+        const int ts = a.p.typesize;
+        const bool leftover_blk = j == d.nblocks - 1 && d.leftover;
+        const int bsize = leftover_blk ? d.leftover : d.blocksize;
+        const int ns = (d.split && !leftover_blk) ? ts : 1;
+        if (s >= ns) return;
+        const int n = bsize / ns;
+        const uint8_t* src = a.raw + d.raw_off + (int64_t)j * d.blocksize;
+        const uint8_t* in;
+        if (a.p.filter == FILTER_SHUFFLE && ts > 1) {
+            // stage the stream: byte s of every element (a split plane), or the whole shuffled block
+            uint8_t* plane = a.planes + (int64_t)w * a.plane_stride;
+            const int ne = bsize / ts;
+            if (ns > 1) {
+                for (int e0 = 0; e0 < n; e0 += 64) { FOR_LANES(l) { const int e = e0 + l; if (e < n) plane[e] = src[(int64_t)e * ts + s]; } }
+            } else {
+                for (int o0 = 0; o0 < bsize; o0 += 64) {
+                    FOR_LANES(l) {
+                        const int o = o0 + l;
+                        if (o < bsize) plane[o] = o < ne * ts ? src[(int64_t)(o % ne) * ts + o / ne] : src[o];
+                    }
+                }
+            }
+            in = plane;
+        } else {
+            in = src + (int64_t)s * n;                  // no shuffle: stream s is slice s of the block
+        }
+        uint8_t* out = a.scratch + (int64_t)b * a.p.slot_bytes + (int64_t)s * n;
+        StreamRec r;
+        r.kind = REC_RAW; r.value = 0; r.csize = n; r.need = 0;
+        uint32_t value;
+        if (wide_is_run(in, n, value)) {
+            r.kind = REC_RUN; r.value = (int32_t)value; r.csize = 0;
+        } else {
+            int need = 0;
+            const int cb = lz4_wide_encode(in, tab, n, out, n, a.p.accel, need);
+            if (cb > 0 && cb < n) { r.kind = REC_LZ4; r.csize = cb; r.need = need; }
+            else wide_copy(in, out, n);
+        }
+        StreamRec* dst = a.recs + (int64_t)b * a.p.streams_per_block + s;
+        FOR_LANES_W(l) { if (l == 0) *dst = r; }
+    }
+};
+
+// One block of cimg_decode_wide: DecodeBlock (decode_kernel.h) with its "LDS" in a device-memory slot.  The header walk is
+// DecodeBlock::phase_a with one difference: every stream is decoded with its own region as the decoder's base.  The wave decoders
+// pack LDS offsets into 18 bits (lz4_decode_wave2 / blosclz_decode_wave: "LDS offsets are below 2^18"), which holds for a region
+// of up to 256 KiB of output but not for the second plane of a two-plane 256 KiB block seen from the slot's start.
+struct WideDecodeBlock : DecodeBlock {
+    CIMG_DEV WideDecodeBlock(const DecodeArgs& a_, uint8_t* slot_, int b_) : DecodeBlock(a_, slot_, b_) {}
+
+    CIMG_DEV void phase_a_wide(int wave)
+    {
+        mode = 3;
+        chunk = find_chunk(a.descs, a.nchunks, b, a.uniform_nblocks);
+        const ChunkDesc d = uniform_desc(a.descs + chunk);
+        j = b - d.blk0;
+        c = a.comp + d.comp_off;
+        out = a.raw + d.raw_off + (int64_t)j * d.blocksize;
+        bsize = (j == d.nblocks - 1 && d.leftover) ? d.leftover : d.blocksize;
+        const u128 h0 = ld128u(c), h1 = ld128u(c + 16);
+        const uint32_t w0 = uni(h0.x);
+        const int flags = (int)((w0 >> 16) & 0xFF);
+        ts = (int)(w0 >> 24);
+        const int nbytes = (int)uni(h0.y), blocksize = (int)uni(h0.z), cbytes = (int)uni(h0.w);
+        const uint32_t f0 = uni(h1.x), f1 = uni(h1.y), b2 = uni(h1.w);
+        if ((w0 & 0xFF) > 5) { fail(ERR_VERSION_SUPPORT); return; }
+        if (nbytes != d.nbytes || blocksize != d.blocksize || ts == 0 || cbytes < HEADER_LEN) { fail(ERR_INVALID_HEADER); return; }
+        if (cbytes > d.destsize) { fail(ERR_READ_BUFFER); return; }
+        if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) { fail(ERR_VERSION_SUPPORT); return; }
+        const int special = (int)((b2 >> 28) & 7);
+        if (special == SPECIAL_ZERO) { mode = 2; wave_fill_global(out, bsize, 0, wave, 4); return; }
+        if (special != 0) { fail(ERR_DATA); return; }
+        if (flags & FLAG_MEMCPYED) {
+            if (cbytes != nbytes + HEADER_LEN) { fail(ERR_DATA); return; }
+            mode = 1;
+            wave_copy_g2g(c + HEADER_LEN + (int64_t)j * blocksize, out, bsize, wave, 4);
+            return;
+        }
+        const int fmt = flags >> 5;
+        if (fmt != 0 && fmt != 1) { fail(ERR_CODEC_SUPPORT); return; }          // (zstd blocks this large: not built)
+        filter = (int)((f1 >> 8) & 0xFF);
+        if (f0 != 0 || (f1 & 0xFF) != 0) { fail(ERR_CODEC_SUPPORT); return; }
+        if (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE) { fail(ERR_CODEC_SUPPORT); return; }
+        if (filter == FILTER_BITSHUFFLE && !(flags & FLAG_DONT_SPLIT)) { fail(ERR_CODEC_SUPPORT); return; }
+        const bool leftover_blk = bsize != blocksize;
+        ns = (!(flags & FLAG_DONT_SPLIT) && !leftover_blk) ? ts : 1;
+        neblock = bsize / ns;
+        rs = fmt == 0 ? blz_region_stride(neblock) : region_stride(neblock);
+        if (ns * rs + 16 > a.lds_bytes) { fail(ERR_FAILURE); return; }
+        if (cbytes < HEADER_LEN + 4 * d.nblocks) { fail(ERR_READ_BUFFER); return; }
+        const int bstart = ld32s(c + HEADER_LEN + 4 * j);
+        if (bstart < HEADER_LEN + 4 * d.nblocks || bstart > cbytes) { fail(ERR_DATA); return; }
+        mode = 0;
+        int pos = bstart;
+        for (int s = 0; s < ns; s++) {
+            if (cbytes - pos < 4) { fail(ERR_READ_BUFFER); mode = 3; return; }
+            const int cs = ld32s(c + pos);
+            pos += 4;
+            const int payload = cs > 0 ? cs : (cs < 0 ? 1 : 0);
+            if (payload > cbytes - pos) { fail(ERR_READ_BUFFER); mode = 3; return; }
+            if ((s & 3) == wave) {
+                uint8_t* region = lds + (int64_t)s * rs;                // the decoder's base: offsets inside the region only
+                if (cs == 0) {
+                    wave_fill_lds(region, 0, neblock, 0);
+                } else if (cs < 0) {
+                    const int token = c[pos];
+                    if (!(token & 1) || cs < -255) { fail(ERR_RUN_LENGTH); }
+                    wave_fill_lds(region, 0, neblock, (uint32_t)(-cs) & 0xFF);
+                } else if (cs == neblock) {
+                    wave_copy_g2l(c + pos, region, 0, neblock);
+                } else if (cs > neblock) {
+                    fail(ERR_DATA);
+                } else {
+                    const int park = rs - round16(cs);
+                    wave_copy_g2l(c + pos, region, park, cs);
+                    const int rc = fmt == 0 ? blosclz_decode_wave(region, 0, neblock, park, cs, rs)
+                                            : CIMG_LZ4_DECODE(region, 0, neblock, park, cs, rs);
+                    if (rc < 0) fail(rc);
+                }
+            }
+            pos += payload;
+        }
+    }
+};
+
+}  // namespace cimg
