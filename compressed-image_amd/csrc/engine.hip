@@ -201,6 +201,25 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_wide(WideDecodeArg
     }
 }
 
+// zstd blocks beyond the normal kernels' LDS.  Encode: cimg_encode_wide's waves with zstd_wide_encode (hash table and FSE tables in
+// LDS, sequences in a device-memory area per wave).  Decode, behind cimg_zstd_walk: the replay with its planes in a device-memory
+// slot per single-wave workgroup, which walks blocks blk_first + k, k + G, ... of the group.
+extern "C" __global__ __launch_bounds__(64) void cimg_encode_wide_zstd(WideZstdEncodeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    WideEncodeWaveT<CODEC_ZSTD> ww(a, reinterpret_cast<uint32_t*>(lds), (int)blockIdx.x);
+    ww.run();
+}
+
+extern "C" __global__ __launch_bounds__(64) void cimg_zstd_replay_wide(WideDecodeArgs a)
+{
+    uint8_t* const slot = a.slots + (size_t)blockIdx.x * (size_t)a.d.lds_bytes;
+    for (int k = (int)blockIdx.x; k < a.d.zblocks; k += (int)gridDim.x) {
+        ZstdReplayBlockT<uint8_t*> blk(a.d, slot, a.d.blk_first + k);
+        blk.run();
+    }
+}
+
 // ====================================================================================================
 //  engine
 // ====================================================================================================
@@ -270,7 +289,7 @@ struct cimg_engine {
     int lean_tune = getenv("CIMG_LEAN_TUNE") ? atoi(getenv("CIMG_LEAN_TUNE")) : (0x10000 | 0x100 | (3 << 9) | 16);
     int lean_hold = getenv("CIMG_NO_LEAN") ? (1 << 30) : 0;   // batches for which the lean launch is skipped
     int64_t zstd_batches = 0;           // decode batches that needed cimg_decode_zstd
-    int64_t zstd_blocks_refused = 0;    // blocks whose plan did not fit its slot (decoded by cimg_decode_zstd behind the two launches)
+    int64_t zstd_blocks_refused = 0;    // blocks whose plan did not fit its slot (decoded by cimg_decode_zstd behind the two launches; wide blocks: their chunks fail)
     int zstd_fused = getenv("CIMG_ZSTD_FUSED") ? atoi(getenv("CIMG_ZSTD_FUSED")) : 0;          // 1: cimg_decode_zstd only (no walk / replay launches)
     int zstd_plan_cap = getenv("CIMG_ZSTD_PLAN_CAP") ? atoi(getenv("CIMG_ZSTD_PLAN_CAP")) : 0;   // diagnostic: bytes of records / literals a plan may take (0: the block area)
     int64_t zstd_plan_bytes = getenv("CIMG_ZSTD_PLAN_MIB") ? atoll(getenv("CIMG_ZSTD_PLAN_MIB")) << 20 : 1024ll << 20;   // device memory for the plans of one group of launches (a plan is ~4.25 x its block: 139 KB for 32 KiB; larger batches go in groups; round 4 took up to 2 GiB and kept it: ADVICE r4.  Measured on configs[4]'s share, 1 GiB of libzstd-22 chunks: 2 GiB = 2 groups 17.9 ms, 512 MiB = 9 groups 19.6 ms)
@@ -326,8 +345,11 @@ struct cimg_engine {
     struct WideFlight {
         bool active = false;
         std::vector<int> normal, wide;    // chunk indices of the caller's batch
+        DecodeArgs da{};                  // the wide launch's arguments (the wide zstd read path starts from them)
+        int32_t max_blocksize = 0;
     } wflight;
     DevBuf wide_planes, wide_queue, wide_slots, descs_wide;
+    DevBuf wide_zseq, wide_zslots;        // zstd on the wide paths: per-wave sequence records (encode), per-workgroup replay slots (decode)
     PinBuf h_descs_wide, h_wst;
     std::vector<uint8_t> shadow_wide;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
@@ -471,6 +493,8 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_DECODE: return "cimg_decode_blocks";
     case CIMG_K_ENCODE_WIDE: return "cimg_encode_wide";
     case CIMG_K_DECODE_WIDE: return "cimg_decode_wide";
+    case CIMG_K_ENCODE_WIDE_ZSTD: return "cimg_encode_wide_zstd";
+    case CIMG_K_ZSTD_REPLAY_WIDE: return "cimg_zstd_replay_wide";
     case CIMG_K_DEINTERLEAVE: return "cimg_deinterleave";
     case CIMG_K_DECODE_ZSTD: return "cimg_decode_zstd";
     case CIMG_K_ENCODE_ZSTD: return "cimg_encode_streams_zstd";
@@ -550,7 +574,7 @@ void cimg_engine_destroy(cimg_engine* e)
     e->drain_timing();
     for (EventPair& ev : e->free_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
-                    &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide})
+                    &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots})
         if (b->p) (void)hipFree(b->p);
     for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst})
         if (b->p) (void)hipHostFree(b->p);
@@ -713,7 +737,19 @@ static int compress_launch_wide(cimg_engine* e, EncodePlan& plan, int32_t nchunk
     WideEncodeArgs wa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (uint8_t*)e->scratch.p,
                       (StreamRec*)e->recs.p, plan.total_blocks, plan.uniform_nblocks, (uint8_t*)e->wide_planes.p, stride,
                       (uint32_t*)e->wide_queue.p};
-    if ((rc = e->launch(CIMG_K_ENCODE_WIDE, cimg_encode_wide, wa, grid, 64, LZ4_HASH_BYTES + 64))) return rc;
+    if (plan.cp.compcode == CODEC_ZSTD) {
+        // (every wave owns the records of one zstd block: a sequence covers at least four bytes)
+        if ((rc = e->reserve(e->wide_zseq, sizeof(uint64_t) * (size_t)WIDE_ZSTD_SEQ_STRIDE * (size_t)grid))) return rc;
+        if (!e->zstd_tables.p) {
+            ZstdEncTables t;
+            zstd_build_enc_tables(&t);
+            if ((rc = e->reserve(e->zstd_tables, sizeof(t)))) return rc;
+            if ((rc = e->hip(hipMemcpyAsync(e->zstd_tables.p, &t, sizeof(t), hipMemcpyHostToDevice, e->stream), "zstd tables H2D"))) return rc;
+            if ((rc = e->hip(hipStreamSynchronize(e->stream), "zstd tables H2D"))) return rc;     // (t lives on this stack frame)
+        }
+        WideZstdEncodeArgs za{wa, (uint64_t*)e->wide_zseq.p, WIDE_ZSTD_SEQ_STRIDE, (const ZstdEncTables*)e->zstd_tables.p};
+        if ((rc = e->launch(CIMG_K_ENCODE_WIDE_ZSTD, cimg_encode_wide_zstd, za, grid, 64, WIDE_ZSTD_LDS + 64))) return rc;
+    } else if ((rc = e->launch(CIMG_K_ENCODE_WIDE, cimg_encode_wide, wa, grid, 64, LZ4_HASH_BYTES + 64))) return rc;
     AssembleArgs aa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (const uint8_t*)e->scratch.p,
                     (const StreamRec*)e->recs.p, (uint8_t*)d_comp, (ChunkLayout*)e->layout.p, plan.uniform_nblocks, lay_host, 1};
     if ((rc = e->launch(CIMG_K_LAYOUT, cimg_layout_chunks, aa, nchunks, 64, 0))) return rc;
@@ -1125,7 +1161,7 @@ static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int3
     const int nw = (int)wp.wide.size();
     const DecodePlan& plan = wp.plan;
     if ((rc = e->upload_descs(e->descs_wide, e->shadow_wide, e->h_descs_wide, plan.descs.data(), sizeof(ChunkDesc) * (size_t)nw))) return rc;
-    if ((rc = e->reserve(e->h_wst, sizeof(int32_t) * (size_t)nw))) return rc;
+    if ((rc = e->reserve(e->h_wst, ((sizeof(int32_t) * (size_t)nw + 15) & ~(size_t)15) + 16))) return rc;   // (behind the words: the wide zstd walk's refusal counter)
     int32_t* st_dev = nullptr;
     if ((rc = e->device_alias(e->h_wst, &st_dev))) return rc;
     memset(e->h_wst.p, 0, sizeof(int32_t) * (size_t)nw);
@@ -1138,6 +1174,9 @@ static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int3
     wa.slots = (uint8_t*)e->wide_slots.p;
     e->wflight.normal = wp.normal;
     e->wflight.wide = wp.wide;
+    e->wflight.da = wa.d;
+    e->wflight.max_blocksize = 0;
+    for (const ChunkDesc& d : plan.descs) e->wflight.max_blocksize = std::max(e->wflight.max_blocksize, (int32_t)d.blocksize);
     if ((rc = e->launch(CIMG_K_DECODE_WIDE, cimg_decode_wide, wa, grid, 256, 0))) return rc;
     e->wflight.active = true;
     e->dflight.launched = true;                   // (the callers' "is there something to finish" test: there is, with or without normal chunks)
@@ -1145,6 +1184,73 @@ static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int3
 }
 
 static int decompress_finish_normal(cimg_engine* e, int32_t* status);
+
+// The wide chunks cimg_decode_wide left with STATUS_ZSTD_PENDING[_SPLIT] (words cleared by the caller, `pending` = their indices
+// among the wide chunks): cimg_zstd_walk over the wide launch's blocks (a block of another codec says ZPLAN_NOT_OURS; the walkers
+// decode the sequences themselves: no lane decoders, no tables to overflow), then cimg_zstd_replay_wide.  There is no fused
+// fallback for these blocks: a plan that does not fit its slot fails its chunk (tune 2), and when the plans' device memory cannot
+// be had even for one block at a time, every pending chunk says BLOSC2_ERROR_MEMORY_ALLOC.
+static int decompress_finish_wide_zstd(cimg_engine* e, const std::vector<int>& pending)
+{
+    const cimg_engine::WideFlight& f = e->wflight;
+    int32_t* const wst = (int32_t*)e->h_wst.p;
+    const int nw = (int)f.wide.size();
+    const int total = f.da.total_blocks;
+    const int area = zstd_kernel_area(f.max_blocksize), cap = zstd_wide_plan_cap(area);
+    const int64_t stride = zstd_plan_stride(cap, false);
+    int group = (int)std::max<int64_t>(1, std::min<int64_t>(total, e->zstd_plan_bytes / stride));
+    int rc;
+    while ((rc = e->zstd_plan_fail ? -4 /* BLOSC2_ERROR_MEMORY_ALLOC */ : e->reserve(e->zplan, (size_t)group * (size_t)stride))) {
+        (void)hipGetLastError();
+        if (group <= 1) break;
+        group /= 2;
+    }
+    if (rc) {
+        if (e->verbose) fprintf(stderr, "[cimg] wide zstd: no device memory for plans (%lld bytes a block)\n", (long long)stride);
+        for (int k : pending) wst[k] = -4;                       // BLOSC2_ERROR_MEMORY_ALLOC
+        return 0;
+    }
+    const int slot = zstd_replay_lds_bytes(f.max_blocksize);
+    const int grid = std::max(1, std::min(group, 4 * e->num_cus));
+    if ((rc = e->reserve(e->wide_zslots, (size_t)slot * (size_t)grid + 64))) {
+        (void)hipGetLastError();
+        for (int k : pending) wst[k] = -4;
+        return 0;
+    }
+    DecodeArgs zb = f.da;
+    // (the walk's refusal counter: behind the status words in page-locked memory, zeroed for every group and read behind it)
+    const size_t ctr_at = (sizeof(int32_t) * (size_t)nw + 15) & ~(size_t)15;
+    volatile uint32_t* const refused = (volatile uint32_t*)((uint8_t*)e->h_wst.p + ctr_at);
+    zb.skipped = (uint32_t*)((uint8_t*)f.da.status + ctr_at);
+    zb.zplan = (uint8_t*)e->zplan.p; zb.zplan_stride = stride; zb.zcap = cap; zb.zarea = area; zb.zlanes = 0;
+    zb.tune = 2;                                                 // (a block the walk refuses has nobody to go to: its chunk fails)
+    const int walk_lds = zstd_walk_lds_bytes(e->zstd_walk_stage);
+    if ((rc = e->allow_lds(cimg_zstd_walk, 7, walk_lds))) return rc;
+    // (one event pair around the whole path, as for the normal read path: CIMG_K_DECODE_ZSTD is the time of a batch's zstd read path)
+    EventPair zev{};
+    const bool ztimed = e->timing;
+    if (ztimed) { zev = e->get_events(); (void)hipEventRecord(zev.a, e->stream); }
+    for (int g0 = 0; g0 < total && !rc; g0 += group) {
+        const int nb = std::min(group, total - g0);
+        *refused = 0;
+        DecodeArgs wa = zb;
+        wa.blk_first = g0; wa.zblocks = nb; wa.lds_bytes = walk_lds;
+        if ((rc = e->launch(CIMG_K_ZSTD_WALK, cimg_zstd_walk, wa, nb, 64, walk_lds))) break;
+        WideDecodeArgs ra{};
+        ra.d = zb;
+        ra.d.blk_first = g0; ra.d.zblocks = nb; ra.d.lds_bytes = slot;
+        ra.slots = (uint8_t*)e->wide_zslots.p;
+        if ((rc = e->launch(CIMG_K_ZSTD_REPLAY_WIDE, cimg_zstd_replay_wide, ra, std::min(nb, grid), 64, 0))) break;
+        if ((rc = cimg_engine_synchronize(e))) break;
+        e->zstd_blocks_refused += *refused;                      // (their chunks failed: these blocks have nobody to fall back to)
+        if (*refused && e->verbose) fprintf(stderr, "[cimg] wide zstd: %u of %d plans did not fit their slots (their chunks fail)\n", (unsigned)*refused, nb);
+    }
+    if (ztimed) {
+        if (rc) e->free_events.push_back(zev);
+        else { (void)hipEventRecord(zev.b, e->stream); e->pending[CIMG_K_DECODE_ZSTD].push_back(zev); }
+    }
+    return rc;
+}
 
 static int decompress_finish(cimg_engine* e, int32_t* status)
 {
@@ -1157,7 +1263,13 @@ static int decompress_finish(cimg_engine* e, int32_t* status)
     bool chunk_error = false;
     for (int32_t v : nst) chunk_error |= v < 0;
     if (rc_normal && !chunk_error) return rc_normal;                          // not a chunk's status: the batch failed as a whole
-    const int32_t* wst = (const int32_t*)e->h_wst.p;
+    int32_t* const wst = (int32_t*)e->h_wst.p;
+    std::vector<int> zpending;                                   // wide zstd chunks: cimg_decode_wide leaves them to the zstd read path
+    for (size_t k = 0; k < wide.size(); k++) if (wst[k] == STATUS_ZSTD_PENDING || wst[k] == STATUS_ZSTD_PENDING_SPLIT) { zpending.push_back((int)k); wst[k] = 0; }
+    if (!zpending.empty()) {
+        const int rc = decompress_finish_wide_zstd(e, zpending);
+        if (rc) { (void)cimg_engine_synchronize(e); return rc; }
+    }
     int first = 0;
     std::vector<int32_t> all(normal.size() + wide.size(), 0);
     for (size_t k = 0; k < normal.size(); k++) all[(size_t)normal[k]] = nst[k];

@@ -1,5 +1,6 @@
-// wide_kernel.h -- blocks whose streams or staging do not fit the LDS of the normal kernels (blocks up to 256 KiB, LZ4 / LZ4HC
-// write, LZ4 / LZ4HC / BloscLZ read).  wide_plan.h decides which batches come here; engine.hip launches the two kernels.
+// wide_kernel.h -- blocks whose streams or staging do not fit the LDS of the normal kernels (blocks up to 256 KiB, LZ4 / LZ4HC /
+// zstd write, LZ4 / LZ4HC / BloscLZ read; zstd read: zstd_walk_kernel.h's replay out of a device-memory slot).  wide_plan.h decides
+// which batches come here; engine.hip launches the kernels.
 //
 //   cimg_encode_wide   persistent single-wave workgroups pull streams from one atomic counter.  A stream that needs the byte
 //                      shuffle is staged into the wave's own plane in device memory (a stream that is a plain slice of the
@@ -15,6 +16,11 @@
 //                      decoders and unshuffle, so every bound it keeps (comp_size / cbytes on reads, the slot size on writes)
 //                      holds as it does there.
 //                      Matches are copied from the slot, at most 64 KiB (LZ4) / ~72 KiB (BloscLZ far) back: L2-resident.
+//                      A block of a zstd chunk (codec format 4) is left with STATUS_ZSTD_PENDING[_SPLIT], as cimg_decode_blocks
+//                      leaves it: the engine then runs the zstd read path's walk over those blocks and cimg_zstd_replay_wide,
+//                      the replay with its planes in a device-memory slot per workgroup (zstd_walk_kernel.h).
+//   cimg_encode_wide_zstd  the same persistent waves and staging as cimg_encode_wide; each stream becomes one zstd frame of
+//                      ceil(n / 128 KiB) blocks (zstd_wide_encode below, the frame writer of zstd_encode.h).
 #pragma once
 #include "encode_kernel.h"
 
@@ -206,13 +212,111 @@ CIMG_DEV bool wide_is_run(const uint8_t* in, int n, uint32_t& value)
     return ballot(bad) == 0;
 }
 
-// one wave: pulls streams until the counter passes the last one
-struct WideEncodeWave {
-    const WideEncodeArgs& a;
-    uint32_t* tab;             // 16 KiB of LDS
-    int w;
+// what the zstd instance of the wave needs beside WideEncodeArgs
+struct WideZstdEncodeArgs {
+    WideEncodeArgs w;
+    uint64_t* seq;             // wave w keeps the sequences of the zstd block it is coding at seq + w * seq_stride
+    int64_t seq_stride;        // (records: ZSTD_BLOCK_MAX / 4, a match is at least four bytes long)
+    const ZstdEncTables* tables;
+};
+enum : int { WIDE_ZSTD_SEQ_STRIDE = ZSTD_BLOCK_MAX / 4 + 64,
+             WIDE_ZSTD_LDS = LZ4_HASH_BYTES + (int)((sizeof(ZstdEncTables) + 63) & ~(size_t)63) };   // hash table, FSE tables
 
-    CIMG_DEV WideEncodeWave(const WideEncodeArgs& a_, uint32_t* tab_, int w_) : a(a_), tab(tab_), w(w_) {}
+// One stream -> one zstd frame of ceil(n / 128 KiB) blocks at out[0, cap) (zstd_encode.h: the frame writer).  Greedy matches from a
+// 4096-slot table of 32-bit positions (LZ4_hash5 over five bytes, the byU32 table of lz4_wide_encode) over the whole stream: an
+// offset reaches back to the stream's first byte, a match ends at its zstd block's end.  A block whose compressed form is not
+// smaller than itself is written as a Raw_Block.  Returns the frame size, 0 when the frame is not smaller than n or does not fit cap.
+// tab: 16 KiB of LDS; T: the FSE tables (LDS); seq: ZSTD_BLOCK_MAX / 4 records of device memory.
+CIMG_DEV int zstd_wide_encode(const uint8_t* in, uint32_t* tab, const ZstdEncTables* T, int n, uint8_t* out_, int cap, uint64_t* seq)
+{
+    enum { MINMATCH = 4, SKIP_TRIGGER = 6 };
+    cimg_global_u8p out = CIMG_AS_GLOBAL(out_);
+    const int fh = zstd_frame_header_bytes(n);
+    if (n < 64 || fh + 64 >= cap) return 0;
+    for (int k = 0; k < 4096; k += 64) { FOR_LANES(l) { tab[k + l] = 0; } }
+    auto put = [&](uint32_t h, int pos) { FOR_LANES_W(l) { if (l == 0) tab[h] = (uint32_t)pos; } };
+    const int probe_end = n - 8;                    // (the hash reads eight bytes)
+    int op = fh;
+    uint32_t rep = 1;                               // the decoder's first repeat offset in front of the next compressed block
+    put(wide_hash(in, true), 0);
+    for (int blk0 = 0; blk0 < n; blk0 += ZSTD_BLOCK_MAX) {
+        const int bend = imin(n, blk0 + ZSTD_BLOCK_MAX), bsz = bend - blk0;
+        const bool last = bend == n;
+        const int lit_at = op + 6;                  // block header, raw literals header, then the literals
+        int lit = 0, nseq = 0, anchor = blk0;
+        int ip = blk0 == 0 ? 1 : blk0;
+        const int limit = imin(probe_end, bend - MINMATCH);
+        bool fits = true;
+        while (ip <= limit && fits) {
+            int match = 0, cur = ip, nb = 1 << SKIP_TRIGGER;
+            bool found = false;
+            for (; cur <= limit; ) {                // probe with LZ4's skip schedule
+                const uint32_t h = wide_hash(in + cur, true);
+                match = (int)uni(tab[h]);
+                put(h, cur);
+                if (match < cur && wide_rd32(in + match) == wide_rd32(in + cur)) { found = true; break; }
+                cur += nb++ >> SKIP_TRIGGER;
+            }
+            if (!found) break;
+            while (cur > anchor && match > 0 && in[cur - 1] == in[match - 1]) { cur--; match--; }
+            // (a match may cover a whole zstd block -- 131 072 bytes: the record's 17-bit length field takes one byte less, and the
+            // rest of the match is found again as the next sequence)
+            const int ml = imin(MINMATCH + wide_common(in, cur + MINMATCH, match + MINMATCH, bend), ZSTD_WIDE_MAX_LEN);
+            const int ll = cur - anchor;
+            if (lit_at + lit + ll + 64 > cap) { fits = false; break; }
+            wide_copy(in + anchor, out_ + lit_at + lit, ll);
+            lit += ll;
+            const uint64_t r = zstd_wide_rec(ll, ml, cur - match);
+            FOR_LANES_W(l) { if (l == 0) seq[nseq] = r; }
+            nseq++;
+            ip = anchor = cur + ml;
+            if (ip - 2 <= probe_end) put(wide_hash(in + ip - 2, true), ip - 2);
+        }
+        int content = 0;                            // Block_Content bytes of a compressed block (0: the block goes raw)
+        if (fits && nseq > 0) {
+            const int tail = bend - anchor;
+            if (lit_at + lit + tail + 64 <= cap) {
+                wide_copy(in + anchor, out_ + lit_at + lit, tail);
+                lit += tail;
+                const int sb = zstd_wide_sequences(seq, nseq, rep, T, out, lit_at + lit, imin(cap, op + 3 + bsz));
+                if (sb > 0) content = 3 + lit + sb;
+            }
+        }
+        if (content > 0 && content < bsz) {
+            zstd_put24(out, op, (last ? 1u : 0u) | (2u << 1) | ((uint32_t)content << 3));      // Compressed_Block
+            zstd_put24(out, op + 3, (3u << 2) | ((uint32_t)lit << 4));                          // Raw_Literals_Block, 20-bit size
+            op += 3 + content;
+            rep = (uint32_t)(seq[nseq - 1] >> 34);
+        } else {
+            if (op + 3 + bsz > cap) return 0;
+            zstd_put24(out, op, (last ? 1u : 0u) | ((uint32_t)bsz << 3));                       // Raw_Block
+            wide_copy(in + blk0, out_ + op + 3, bsz);
+            op += 3 + bsz;
+        }
+        if (op >= n) return 0;
+    }
+    zstd_put_frame_header(out, n);
+    return op;
+}
+
+// one wave: pulls streams until the counter passes the last one (CODEC_LZ4: cimg_encode_wide, every LZ4 / LZ4HC batch;
+// CODEC_ZSTD: cimg_encode_wide_zstd, with z)
+template <int CODEC>
+struct WideEncodeWaveT {
+    const WideEncodeArgs& a;
+    uint32_t* tab;             // 16 KiB of LDS (zstd: the FSE tables behind it)
+    int w;
+    const WideZstdEncodeArgs* z = nullptr;
+
+    CIMG_DEV WideEncodeWaveT(const WideEncodeArgs& a_, uint32_t* tab_, int w_) : a(a_), tab(tab_), w(w_) {}
+    CIMG_DEV WideEncodeWaveT(const WideZstdEncodeArgs& z_, uint32_t* tab_, int w_) : a(z_.w), tab(tab_), w(w_), z(&z_)
+    {
+        // the FSE tables of the predefined distributions -> LDS behind the hash table
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(z_.tables);
+        uint32_t* dst = tab + LZ4_HASH_BYTES / 4;
+        const int words = (int)(sizeof(ZstdEncTables) / 4);
+        for (int w0 = 0; w0 < words; w0 += 64) { FOR_LANES(l) { if (w0 + l < words) dst[w0 + l] = src[w0 + l]; } }
+    }
 
     CIMG_DEV void run()
     {
@@ -267,7 +371,12 @@ struct WideEncodeWave {
             r.kind = REC_RUN; r.value = (int32_t)value; r.csize = 0;
         } else {
             int need = 0;
-            const int cb = lz4_wide_encode(in, tab, n, out, n, a.p.accel, need);
+            int cb;
+            if constexpr (CODEC == CODEC_ZSTD) {
+                cb = zstd_wide_encode(in, tab, reinterpret_cast<const ZstdEncTables*>(tab + LZ4_HASH_BYTES / 4), n, out, n,
+                                      z->seq + (int64_t)w * z->seq_stride);
+                need = cb;                                // (a frame fits a budget iff the budget holds its bytes)
+            } else cb = lz4_wide_encode(in, tab, n, out, n, a.p.accel, need);
             if (cb > 0 && cb < n) { r.kind = REC_LZ4; r.csize = cb; r.need = need; }
             else wide_copy(in, out, n);
         }
@@ -275,6 +384,7 @@ struct WideEncodeWave {
         FOR_LANES_W(l) { if (l == 0) *dst = r; }
     }
 };
+using WideEncodeWave = WideEncodeWaveT<CODEC_LZ4>;
 
 // One block of cimg_decode_wide: DecodeBlock (decode_kernel.h) with its "LDS" in a device-memory slot.  The header walk is
 // DecodeBlock::phase_a with one difference: every stream is decoded with its own region as the decoder's base.  The wave decoders
@@ -312,7 +422,8 @@ struct WideDecodeBlock : DecodeBlock {
             return;
         }
         const int fmt = flags >> 5;
-        if (fmt != 0 && fmt != 1) { fail(ERR_CODEC_SUPPORT); return; }          // (zstd blocks this large: not built)
+        if (fmt == 4) { fail((flags & FLAG_DONT_SPLIT) || ts <= 1 ? STATUS_ZSTD_PENDING : STATUS_ZSTD_PENDING_SPLIT); return; }   // the zstd read path's (engine.hip)
+        if (fmt != 0 && fmt != 1) { fail(ERR_CODEC_SUPPORT); return; }
         filter = (int)((f1 >> 8) & 0xFF);
         if (f0 != 0 || (f1 & 0xFF) != 0) { fail(ERR_CODEC_SUPPORT); return; }
         if (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE) { fail(ERR_CODEC_SUPPORT); return; }

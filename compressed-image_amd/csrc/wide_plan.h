@@ -1,8 +1,9 @@
 // wide_plan.h -- the planner of the wide-block kernels (wide_kernel.h).  It is asked only after plan_encode_batch /
 // plan_decode_batch (plan.h) refused a batch with ERR_CODEC_SUPPORT, and it takes exactly what those refuse for size alone:
-// LZ4 / LZ4HC streams longer than the byU16 encoder's 65 546 bytes or shuffled blocks whose staging exceeds LDS (write), and
-// lz4 / lz4hc / blosclz blocks whose staging exceeds LDS (read) -- in both cases for blocks up to WIDE_MAX_BLOCK.  Everything
-// else keeps the normal planner's answer.  Pure C++, shared by the engine and the emulator tests.
+// LZ4 / LZ4HC streams longer than the byU16 encoder's 65 546 bytes, zstd streams longer than ZSTD_ENC_MAX_INPUT, or shuffled
+// blocks whose staging exceeds LDS (write), and blocks whose staging exceeds LDS (read; zstd blocks among them go on to the zstd
+// read path's walk and cimg_zstd_replay_wide) -- in both cases for blocks up to WIDE_MAX_BLOCK.  Everything else keeps the normal
+// planner's answer.  Pure C++, shared by the engine and the emulator tests.
 #pragma once
 #include "plan.h"
 #include "wide_kernel.h"
@@ -17,7 +18,7 @@ inline int plan_encode_wide(const HostCParams& p, int nchunks, const int64_t* ra
     int filter = 0;
     int rc = single_filter(p, &filter);
     if (rc < 0) return rc;
-    if (p.compcode != CODEC_LZ4 && p.compcode != CODEC_LZ4HC) return ERR_CODEC_SUPPORT;   // BloscLZ / zstd / zlib: not built
+    if (p.compcode != CODEC_LZ4 && p.compcode != CODEC_LZ4HC && p.compcode != CODEC_ZSTD) return ERR_CODEC_SUPPORT;   // BloscLZ / zlib: not built
     if (filter == FILTER_BITSHUFFLE) return ERR_CODEC_SUPPORT;
     if (p.blocksize <= 0 || p.blocksize > WIDE_MAX_BLOCK) return ERR_CODEC_SUPPORT;      // (automatic block size stays with plan.h)
     CodecParams& cp = plan->cp;
@@ -25,7 +26,7 @@ inline int plan_encode_wide(const HostCParams& p, int nchunks, const int64_t* ra
     cp.clevel = p.clevel;
     cp.compcode = p.compcode;
     cp.filter = filter;
-    cp.accel = p.compcode == CODEC_LZ4HC ? 1 : 10 - p.clevel;
+    cp.accel = (p.compcode == CODEC_LZ4HC || p.compcode == CODEC_ZSTD) ? 1 : 10 - p.clevel;   // (zstd: zstd_wide_encode has no acceleration)
     cp.max_blocksize = 0;
     cp.streams_per_block = 1;
     int32_t blk = 0;
@@ -105,5 +106,10 @@ inline int plan_decode_wide(int nchunks, const int64_t* comp_off, const int32_t*
     wp->slot_bytes = (slot + 63) & ~63;
     return 0;
 }
+
+// The plans of the wide zstd read path (engine.hip: decompress_finish_wide_zstd): the walk decodes the sequences itself (no lane
+// decoders, hence no table area to overflow) and a slot holds records for a sequence per three bytes -- zstd's shortest match --
+// and literals for the whole block, so that no valid block is refused for its plan: these blocks have nobody to fall back to.
+inline int zstd_wide_plan_cap(int area) { return ((area + area / 3) + 15) & ~15; }
 
 }  // namespace cimg

@@ -734,7 +734,8 @@ CIMG_DEV int zstd_execute_batch(DP dst, int dcap, int* dpos_io, DP lit, int rege
 #else
         const bool shared_turn = true;
 #endif
-        if (shared_turn && mlo != nullptr && gd - mis >= (uintptr_t)mlo && (uintptr_t)mhi >= gd - mis + 8) {
+        // (its positions are 18-bit: an output that reaches 2^18 bytes -- a 256 KiB stream -- takes the byte-exact form below)
+        if (shared_turn && mlo != nullptr && gd - mis >= (uintptr_t)mlo && (uintptr_t)mhi >= gd - mis + 8 && dcap + mis + 64 <= (1 << 18)) {
             const int64_t span = (int64_t)((uintptr_t)mhi - (gd - mis));
             const int clampmax = (int)(((span < (1 << 18) ? span : (1 << 18) - 4) - 4) & ~3ll);
             const int lit0 = (int)((uintptr_t)(const uint8_t*)lit - gd) + mis + lpos;

@@ -297,4 +297,104 @@ CIMG_DEV int zstd_finish_frame(uint8_t* lds, int tab_off, int n, cimg_global_u8p
     return total;
 }
 
+// ---- frames of more than one block (wide_kernel.h: zstd_wide_encode, streams of 64 KiB .. 256 KiB) -------------------------
+// The same frame as above -- single segment with content size, raw literals, the three predefined distributions -- cut into
+// ceil(n / 128 KiB) blocks (zstd's block maximum), the last-block bit on the final one.  A sequence is one 64-bit record here:
+// literal length | match length << 17 | offset << 34 (lengths at most ZSTD_WIDE_MAX_LEN = 2^17 - 1: no sequence crosses a zstd block,
+// and a match that would cover a whole one is cut a byte short; offsets up to 2^18,
+// offset code <= 18 of the predefined table's 28; match length code <= 52).  The repeat offsets carry over between the blocks of
+// a frame as the decoder keeps them, so the first sequence of a block is coded against the last offset of the block before
+// (rep_in; 1 at the start of a frame).
+enum : int { ZSTD_BLOCK_MAX = 131072, ZSTD_WIDE_MAX_LEN = 131071 };
+CIMG_HD uint64_t zstd_wide_rec(int ll, int ml, int off) { return (uint64_t)ll | ((uint64_t)ml << 17) | ((uint64_t)off << 34); }
+CIMG_HD int zstd_frame_header_bytes(int n) { return 4 + 1 + (n < 256 ? 1 : n <= 65791 ? 2 : 4); }
+
+// magic + frame header descriptor + content size at out[0 ..)
+CIMG_DEV void zstd_put_frame_header(cimg_global_u8p out, int n)
+{
+    const int fcs_bytes = n < 256 ? 1 : n <= 65791 ? 2 : 4;
+    const int fcs_flag = n < 256 ? 0 : n <= 65791 ? 1 : 2;
+    const uint32_t fcs = n < 256 ? (uint32_t)n : n <= 65791 ? (uint32_t)(n - 256) : (uint32_t)n;
+    FOR_LANES_W(l) {
+        int v = -1;
+        if (l == 0) v = 0x28; else if (l == 1) v = 0xB5; else if (l == 2) v = 0x2F; else if (l == 3) v = 0xFD;
+        else if (l == 4) v = (fcs_flag << 6) | (1 << 5);                         // Single_Segment, no checksum, no dictionary
+        else if (l >= 5 && l < 5 + fcs_bytes) v = (int)((fcs >> (8 * (l - 5))) & 0xFF);
+        if (v >= 0) out[l] = (uint8_t)v;
+    }
+}
+// a 3-byte little-endian word (block header, raw literals header) at out[at ..)
+CIMG_DEV void zstd_put24(cimg_global_u8p out, int at, uint32_t v)
+{
+    FOR_LANES_W(l) { if (l < 3) out[at + l] = (uint8_t)(v >> (8 * l)); }
+}
+
+// The sequences section of one compressed block: nseq records (seq, in device memory) -> out[at, cap).  T: the FSE tables in LDS.
+// Returns the section's bytes, or 0 when it does not fit cap.
+CIMG_DEV int zstd_wide_sequences(const uint64_t* seq, int nseq, uint32_t rep_in, const ZstdEncTables* T, cimg_global_u8p out, int at, int cap)
+{
+    const int nseq_bytes = nseq < 128 ? 1 : nseq < 0x7F00 ? 2 : 3;
+    const int stream_at = at + nseq_bytes + 1;
+    if (nseq <= 0 || stream_at + 8 >= cap) return 0;
+    ZstdBitWriter bw;
+    bw.init(out, stream_at, cap);
+    uint32_t st_ll = 0, st_of = 0, st_ml = 0;
+    for (int base = ((nseq - 1) >> 6) << 6; base >= 0; base -= 64) {
+        LV<uint32_t> r0, r1, rp;
+        FOR_LANES(l) {
+            const int i = imin(base + l, nseq - 1);
+            const uint64_t r = seq[i];
+            r0[l] = (uint32_t)r; r1[l] = (uint32_t)(r >> 32);
+            rp[l] = i > 0 ? (uint32_t)(seq[i - 1] >> 34) : rep_in;
+        }
+        const int top = imin(63, nseq - 1 - base);
+        for (int k = top; k >= 0; --k) {
+            const uint64_t r = (uint64_t)readlane(r0, k) | ((uint64_t)readlane(r1, k) << 32);
+            const int ll = (int)(r & 0x1FFFF), ml = (int)((r >> 17) & 0x1FFFF);
+            const uint32_t off = (uint32_t)(r >> 34);
+            const int off_base = (off == readlane(rp, k) && ll > 0) ? 1 : (int)off + 3;     // (zstd_finish_frame: the first repeat offset)
+            const int llc = zstd_ll_code(ll), mlc = zstd_ml_code(ml), ofc = zstd_highbit((uint32_t)off_base);
+            const int llb = zstd_ll_bits(llc), mlb = zstd_ml_bits(mlc);
+            if (base + k == nseq - 1) {
+                st_ml = zstd_fse_init(T->ml_state, uni(T->ml_dnb[mlc]), uni(T->ml_dfs[mlc]));
+                st_of = zstd_fse_init(T->of_state, uni(T->of_dnb[ofc]), uni(T->of_dfs[ofc]));
+                st_ll = zstd_fse_init(T->ll_state, uni(T->ll_dnb[llc]), uni(T->ll_dfs[llc]));
+            } else {
+                zstd_fse_put(bw, st_of, T->of_state, uni(T->of_dnb[ofc]), uni(T->of_dfs[ofc]));
+                zstd_fse_put(bw, st_ml, T->ml_state, uni(T->ml_dnb[mlc]), uni(T->ml_dfs[mlc]));
+                zstd_fse_put(bw, st_ll, T->ll_state, uni(T->ll_dnb[llc]), uni(T->ll_dfs[llc]));
+                bw.flush();
+            }
+            bw.add((uint32_t)(ll - zstd_ll_base(llc)), llb);           // <= 16 bits (literal length code <= 35)
+            bw.add((uint32_t)(ml - zstd_ml_base(mlc)), mlb);           // <= 16 bits (match length code <= 52)
+            bw.flush();
+            bw.add((uint32_t)off_base - (1u << ofc), ofc);             // <= 18 bits
+            bw.flush();
+            if (bw.overflow) return 0;
+        }
+    }
+    bw.add(st_ml, 6);
+    bw.add(st_of, 5);
+    bw.add(st_ll, 6);
+    bw.add(1, 1);
+    bw.flush();
+    if (bw.overflow) return 0;
+    int end = bw.pos;
+    if (bw.nbits > 0) {
+        const uint64_t c = bw.cont;
+        FOR_LANES_W(l) { if (l == 0) out[end] = (uint8_t)c; }
+        end += 1;
+    }
+    if (end > cap) return 0;
+    FOR_LANES_W(l) {
+        int v = -1;
+        if (nseq_bytes == 1) { if (l == 0) v = nseq; }
+        else if (nseq_bytes == 2) { if (l == 0) v = (nseq >> 8) + 0x80; else if (l == 1) v = nseq & 0xFF; }
+        else { if (l == 0) v = 0xFF; else if (l == 1) v = (nseq - 0x7F00) & 0xFF; else if (l == 2) v = ((nseq - 0x7F00) >> 8) & 0xFF; }
+        if (l == nseq_bytes) v = 0;                                          // symbol compression modes: all three predefined
+        if (v >= 0) out[at + l] = (uint8_t)v;
+    }
+    return end - at;
+}
+
 }  // namespace cimg

@@ -89,11 +89,15 @@ struct ZstdWalkBlock {
     }
 };
 
-struct ZstdReplayBlock {
+// DP: how the block's planes are addressed -- cimg_lds_u8p (cimg_zstd_replay: `lds` is the workgroup's LDS, a.lds_bytes its size),
+// or uint8_t* (cimg_zstd_replay_wide: `lds` is the workgroup's slot in device memory, a.lds_bytes the slot's size -- blocks whose
+// planes do not fit LDS, up to WIDE_MAX_BLOCK)
+template <class DP = cimg_lds_u8p>
+struct ZstdReplayBlockT {
     const DecodeArgs& a;
     uint8_t* lds;
     int b;
-    CIMG_DEV ZstdReplayBlock(const DecodeArgs& a_, uint8_t* lds_, int b_) : a(a_), lds(lds_), b(b_) {}
+    CIMG_DEV ZstdReplayBlockT(const DecodeArgs& a_, uint8_t* lds_, int b_) : a(a_), lds(lds_), b(b_) {}
     CIMG_DEV void fail(int chunk, int code) { FOR_LANES_W(l) { if (l == 0) a.status[chunk] = code; } }
 
     CIMG_DEV void run()
@@ -132,12 +136,13 @@ struct ZstdReplayBlock {
                 const uint8_t v = (uint8_t)((uint32_t)(-cs) & 0xFF);
                 for (int i = 0; i < g.neblock; i += 64) { FOR_LANES_W(l) { if (i + l < g.neblock) plane[i + l] = v; } }
             } else if (cs == g.neblock) {
-                if (((s * g.neblock) & 15) == 0) wave_copy_g2l(g.c + pos, lds, s * g.neblock, g.neblock);
+                if constexpr (!std::is_same<DP, cimg_lds_u8p>::value) zstd_stage(plane, g.c + pos, g.neblock);
+                else if (((s * g.neblock) & 15) == 0) wave_copy_g2l(g.c + pos, lds, s * g.neblock, g.neblock);
                 else for (int i = 0; i < g.neblock; i += 64) { FOR_LANES_W(l) { if (i + l < g.neblock) plane[i + l] = g.c[pos + i + l]; } }
             } else if (cs > g.neblock) {
                 fail(g.chunk, ERR_DATA); return;
             } else {
-                const int r = zstd_replay_frame<cimg_lds_u8p>(ops, opi, nops, s, recs, nrecs, plane, g.neblock, lds, lds + (a.lds_bytes & ~3), &opi);
+                const int r = zstd_replay_frame<DP>(ops, opi, nops, s, recs, nrecs, plane, g.neblock, lds, lds + (a.lds_bytes & ~3), &opi);
 #if !defined(CIMG_ABL_ZSTD_NO_SEQ) && !defined(CIMG_ABL_ZSTD_NO_EXEC)
                 if (r != g.neblock) { fail(g.chunk, r < 0 ? r : ERR_DATA); return; }
 #endif
@@ -150,5 +155,6 @@ struct ZstdReplayBlock {
         for (int q = 0; q < 4; ++q) fb.phase_b(q);
     }
 };
+using ZstdReplayBlock = ZstdReplayBlockT<>;
 
 }  // namespace cimg

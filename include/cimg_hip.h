@@ -194,7 +194,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* CIMG_K_DECODE_ZSTD is the whole zstd read path of a batch; its launches are also timed one by one: */
        CIMG_K_ZSTD_WALK = 7, CIMG_K_ZSTD_REPLAY = 8, CIMG_K_ZSTD_FUSED = 9, CIMG_K_ZSTD_SEQ = 10, CIMG_K_ZSTD_LIT = 11,
        /* blocks beyond the normal kernels' LDS (up to 256 KiB): */
-       CIMG_K_ENCODE_WIDE = 12, CIMG_K_DECODE_WIDE = 13, CIMG_K_COUNT = 14 };
+       CIMG_K_ENCODE_WIDE = 12, CIMG_K_DECODE_WIDE = 13,
+       /* zstd blocks beyond the normal kernels' LDS: the wide encoder's zstd instance, the replay out of device-memory slots */
+       CIMG_K_ENCODE_WIDE_ZSTD = 14, CIMG_K_ZSTD_REPLAY_WIDE = 15, CIMG_K_COUNT = 16 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);
