@@ -8,12 +8,17 @@ compress all 32 chunks (one batched call) + decompress them (one batched call), 
 resident in HBM.  value = ranks * steps * 2 * N / wall  (N = 128 MiB per rank; weak scaling: every rank
 owns its own 4 channels, there is no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `roofline` is for the kernel with the largest share of device time
 (HIP events recorded on the engine's stream around every launch); `kernels` lists all four.
 `--dump-outputs DIR` writes what the last timed step returned (dump_outputs below) for output-to-output comparison of two builds.
+
+A plain run does only what the headline needs: set up, verify the first step, warm up, time the steps, verify the last one,
+dump if asked, print the line.  `--full` adds everything that runs on its own after the timed region: the CPU baselines,
+the measured copy peak, the natural family and the other pixel types (default configuration), the `compressible` legs
+(--config 1 / 3), the comparisons with the oracle and libzstd (--config 1 / 5), the exchange of the finished chunks (N > 1).
 `cpu_baseline` times the oracle (CPU restatement, oracle/) on the host cores -- it is the checker
 being timed, never part of the measured GPU path.
 """
@@ -316,8 +321,10 @@ def run_config1(args, rank, world, local_rank, dist, red_dev):
         print("bench.py --config 1: decompressed pixels differ from the input", file=sys.stderr)
         sys.exit(3)
     po = O.cparams(1, clevel=9, blocksize=BLOCK, compcode=O.BLOSCLZ if codec == "blosclz" else O.LZ4, filters=(0, 0, 0, 0, 0, filt))
-    r, want = O.compress(po, host, destsize=CHUNK + 32)
-    same_bytes = int(cb[0]) == r and d_comp[:r].cpu().numpy().tobytes() == want
+    same_bytes = None
+    if args.full:
+        r, want = O.compress(po, host, destsize=CHUNK + 32)
+        same_bytes = int(cb[0]) == r and d_comp[:r].cpu().numpy().tobytes() == want
     for _ in range(args.warmup):
         step()
     eng.enable_timing(1)
@@ -358,7 +365,7 @@ def run_config1(args, rank, world, local_rank, dist, red_dev):
                "config": {"workload": f"BASELINE configs[0]: 1x{W}x{H} uint8, {codec} clevel 9 + {FILTER_TEXT[args.filter or 'shuffle']}, one chunk of 1 MiB in a "
                                       f"4 MiB + 32 buffer (32 blocks of 32 KiB), device-resident, family={args.family}; single-chunk calls",
                           "element_dtype": "uint8", "uncompressed_bytes_per_gpu": N, "compressed_bytes_per_gpu": Cb,
-                          "compression_ratio": round(N / Cb, 4) if Cb else None, "bytes_equal_oracle": bool(same_bytes),
+                          "compression_ratio": round(N / Cb, 4) if Cb else None, "bytes_equal_oracle": None if same_bytes is None else bool(same_bytes),
                           "us_per_chunk_roundtrip": round(elapsed / args.steps * 1e6, 1)},
                "roofline": {"kernel": "cimg_encode_streams_blosclz" if codec == "blosclz" else "cimg_encode_streams", "bound": "hbm",
                             "achieved": round((N + Cb) / (e_us * 1e-6) / 1e9, 1) if e_us else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -368,7 +375,7 @@ def run_config1(args, rank, world, local_rank, dist, red_dev):
                "roofline_decode": {"kernel": "cimg_decode_lean + cimg_decode_blocks", "bound": "hbm", "median_launch_us": round(d_us, 2),
                                    "achieved": round((N + Cb) / (d_us * 1e-6) / 1e9, 1) if d_us else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                    "frac": round((N + Cb) / (d_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5) if d_us else None}}
-        if args.family == "tiled" and world == 1:
+        if args.full and args.family == "tiled" and world == 1:
             # configs[0] as named is incompressible (four noise bits a byte: the chunk comes out memcpyed, ratio 1.000): a second leg on
             # the natural family, where the codec actually codes -- same calls, same geometry
             nat = synth.natural_channel(np.uint8, W, H).view(np.uint8).ravel()
@@ -396,7 +403,7 @@ def run_config1(args, rank, world, local_rank, dist, red_dev):
             if not args.no_cpu_baseline:
                 out["compressible"]["cpu_baseline"] = cpu_baseline(nat, budget_s=3.0, policy="blocks16", typesize=1, compcode=po.compcode, chunk=N, filt=filt, destsize=CHUNK + 32)
             d_raw.copy_(torch.from_numpy(host).cuda())
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the reference's own call: one thread team over the blocks of the one chunk (channel.h:127: hw / 2 threads) for compression,
             # ONE thread for decompression (wrapper.h:406)
             # (this GPU's share of the host -- 16 threads over the blocks of the one chunk --, then the reference's hw / 2 threads, which
@@ -519,7 +526,7 @@ def run_config3(args, rank, world, local_rank, dist, red_dev):
                "roofline_decode": {"kernel": "cimg_decode_lean + cimg_decode_blocks", "bound": "hbm", "median_launch_us": round(d_us, 2),
                                    "achieved": round((CHUNK + cmean) / (d_us * 1e-6) / 1e9, 1) if d_us else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                    "frac": round((CHUNK + cmean) / (d_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5) if d_us else None}}
-        if filt_name == "bitshuffle" and codec == "blosclz" and args.family == "tiled" and world == 1:
+        if args.full and filt_name == "bitshuffle" and codec == "blosclz" and args.family == "tiled" and world == 1:
             # configs[2] as named comes out memcpyed (BloscLZ 2.3.0 gives up on the noise bit rows: ratio 1.000): one pass of the same
             # loop with BYTE shuffle, where the codec actually codes
             cl = leg("shuffle", 1, 1, False)
@@ -531,7 +538,7 @@ def run_config3(args, rank, world, local_rank, dist, red_dev):
             if not args.no_cpu_baseline:
                 out["compressible"]["cpu_baseline"] = cpu_random_access(host, perm, compcode=O.BLOSCLZ, filt=hip.SHUFFLE, budget_s=5.0,
                                                                         cthreads=min(visible_cores(), 16), dthreads=min(visible_cores(), 16))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the same loop on the host: the reference's call structure (one chunk at a time; compression with hw / 2 threads over the
             # chunk's blocks, channel.h:127; decompression on one thread, wrapper.h:406; the + 1 in numpy) on a bounded sample of chunks
             cc = O.BLOSCLZ if codec == "blosclz" else O.LZ4
@@ -624,7 +631,7 @@ def run_config5(args, rank, world, local_rank, dist, red_dev):
     if not torch.equal(d_out, d_raw):
         print("bench.py --config 5: decompressed pixels differ from the input -- refusing to report a number", file=sys.stderr)
         sys.exit(3)
-    have_libzstd = O.zstd_available()
+    have_libzstd = args.full and O.zstd_available()
     if have_libzstd:                                               # the real library reads the engine's chunks too (a sample)
         sample = d_gcomp[:3 * gstride].cpu().numpy()
         for i in range(3):
@@ -697,7 +704,7 @@ def run_config5(args, rank, world, local_rank, dist, red_dev):
                         "cimg_decode_zstd": {"launches": zn, "avg_us": round(z_avg_s * 1e6, 1),
                                              "what": "the zstd read path of a batch, first launch to last (one event pair around them)", "launches_of_the_path": own_parts}},
         }
-    # ---- chunks as the reference writes them: libzstd on the host (outside the timed region), decoded by the same kernel -----------
+    # ---- --full: chunks as the reference writes them: libzstd on the host (outside the timed region), decoded by the same kernel ----
     if rank == 0 and world == 1 and have_libzstd and not args.no_cpu_baseline:
         stride = CHUNK + 64
         comp = np.zeros(nchunks * stride, np.uint8)
@@ -762,7 +769,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 50; 200 for --config 1, 5 for --config 3)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps in front of them (default: 10; 20 for --config 1, 1 for --config 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: CPU baselines, the "
+                         "copy peak, the natural family and other pixel types, the compressible legs (--config 1 / 3), the oracle and "
+                         "libzstd comparisons (--config 1 / 5), the exchange (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--family", default="tiled", choices=["tiled", "natural", "random", "zero"])
     ap.add_argument("--zstd-clevel", type=int, default=9, help="--config 5: blosc2 clevel the chunks are made with (9 = the reference's default = zstd level 22)")
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4, 5],
@@ -770,8 +781,8 @@ def main():
                          "the latency floor); 2 = configs[1], 4 x 4096^2 float16 per rank (the headline); "
                          "3 = configs[2], 3 x 8192^2 uint16 blosclz + bitshuffle, the seeded random-access get_chunk -> +1 -> set_chunk loop "
                          "(single-chunk calls; a step = one pass over the 96 chunks); "
-                         "4 = configs[3], 64 such images over 8 GPUs = 8 images per rank, with the gather of the finished chunks to rank 0; "
-                         "5 = configs[4], 16384^2 float32 zstd: one channel per rank, decode of libzstd-made chunks + compression ratio")
+                         "4 = configs[3], 64 such images over 8 GPUs = 8 images per rank (with --full: and the gather of the finished chunks to rank 0); "
+                         "5 = configs[4], 16384^2 float32 zstd: one channel per rank, compression ratio (with --full: + decode of libzstd-made chunks)")
     ap.add_argument("--codec", default=None, choices=["lz4", "blosclz"], help="default: what the configuration names (lz4 for 2 / 4, blosclz for 1 / 3)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="--config 2 with N > 1: weak = every rank owns its own 4 channels (per-GPU work fixed); strong = the ONE image's 32 chunks are "
@@ -962,7 +973,7 @@ def main():
         dist.all_reduce(tk, op=dist.ReduceOp.SUM)
         per_rank_us = [[round(float(tk[r, 0]), 2), round(float(tk[r, 1]), 2)] for r in range(world)]
 
-    # ---- the exchange step of SURVEY.md section 8e (N > 1): every rank's finished chunks travel to rank 0, packed,
+    # ---- the exchange step of SURVEY.md section 8e (N > 1, --full): every rank's finished chunks travel to rank 0, packed,
     # point to point with exact sizes (cimg/shard.py: gather_chunks; "nccl" = RCCL send/recv over xGMI).  Timed on its own,
     # after the codec region: it belongs to a caller that wants the whole result on one device, not to the codec path.
     # It runs LAST, behind a watchdog (below): nothing it does -- a refusal, a hang of the communicator -- may cost the line its
@@ -1019,12 +1030,12 @@ def main():
         # what the last timed step handed back (rank 0's share), before the legs below reuse the buffers
         dump_outputs(args.dump_outputs, d_comp.cpu().numpy(), comp_off, cbytes, d_out.cpu().numpy(), raw_off, nbytes, DTYPE)
 
-    # ---- a measured copy peak beside the 8 TB/s specification, and the OTHER face of the codec (natural family) in the same line ----
+    # ---- --full: a measured copy peak beside the 8 TB/s specification, and the OTHER face of the codec (natural family) in the same line ----
     copy_peak = natural = dtypes = None
     headline = args.family == "tiled" and args.filter == "shuffle" and args.codec == "lz4" and args.config == 2 and not strong
-    if rank == 0:
+    if rank == 0 and args.full:
         copy_peak = measure_copy_peak()
-    if rank == 0 and world == 1 and headline and not os.environ.get("CIMG_BENCH_NO_NATURAL"):
+    if rank == 0 and world == 1 and headline and args.full and not os.environ.get("CIMG_BENCH_NO_NATURAL"):
         nat = np.concatenate([synth.natural_channel(DTYPE, WIDTH, HEIGHT, c=c).view(np.uint8).ravel() for c in range(CHANNELS)])
         d_raw.copy_(torch.from_numpy(nat).cuda())
         step(); step()
@@ -1150,7 +1161,7 @@ def main():
             "step_calls": ("cimg_compress_batch_device + cimg_decompress_batch_device (one wait each)" if sync_calls else
                            "cimg_compress_batch_device_begin, cimg_decompress_batch_device_begin, then both _fetch (sizes and status on the host every step)"),
         }
-        if not args.no_cpu_baseline and world == 1 and args.filter == "shuffle" and args.config == 2 and args.codec == "lz4":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.filter == "shuffle" and args.config == 2 and args.codec == "lz4":
             # three labelled figures, none capped silently: this GPU's share of the host (16 threads), every visible hardware
             # thread, and the reference's own call structure (serial chunks, hw/2 threads inside a chunk for encode, 1 thread decode)
             out["cpu_baseline"] = cpu_baseline(host, budget_s=10.0, policy="share")
@@ -1171,7 +1182,7 @@ def main():
             real = cblosc2_baseline(host)                     # only where a c-blosc2 library is installed
             if real is not None:
                 out["cpu_baseline_cblosc2"] = real
-    if dist is not None:
+    if dist is not None and args.full:
         # the exchange, behind a watchdog: a rank whose exchange has not come back after EXCHANGE_TIMEOUT_S leaves -- rank 0 with the
         # line it has (exchange: the reason), the others silently -- instead of sitting in a collective until the job is killed
         import threading

@@ -4,9 +4,9 @@ tag=${1:-r05}
 out=gpurun_out/prof/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py --config 1 > $out/bench_config1.json 2> $out/bench_config1.err
-timeout -k 10 300 python bench.py --config 3 > $out/bench_config3.json 2> $out/bench_config3.err
-timeout -k 10 500 python bench.py --config 5 > $out/bench_config5.json 2> $out/bench_config5.err
+timeout -k 10 300 python bench.py --config 1 --full > $out/bench_config1.json 2> $out/bench_config1.err
+timeout -k 10 300 python bench.py --config 3 --full > $out/bench_config3.json 2> $out/bench_config3.err
+timeout -k 10 500 python bench.py --config 5 --full > $out/bench_config5.json 2> $out/bench_config5.err
 echo "[extra] config benches done"
 timeout -k 10 200 python tools/diag_stamps_hw.py > $out/decode_slots.txt 2>&1
 echo "[extra] slots done"
