@@ -15,12 +15,13 @@ LIB_PATH = os.environ.get("CIMG_LIB") or os.path.join(_PKG, "libcimg_hip.so")   
 K_ENCODE, K_LAYOUT, K_EMIT, K_DECODE, K_DEINTERLEAVE, K_DECODE_ZSTD, K_ENCODE_ZSTD, K_ZSTD_WALK, K_ZSTD_REPLAY, K_ZSTD_FUSED, K_ZSTD_SEQ, K_ZSTD_LIT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 K_ENCODE_WIDE, K_DECODE_WIDE = 12, 13          # blocks beyond the normal kernels' LDS (csrc/wide_kernel.h)
 K_ENCODE_WIDE_ZSTD, K_ZSTD_REPLAY_WIDE = 14, 15  # ... of zstd chunks
+K_DECODE_WINDOW = 16                           # windows: the blocks a window meets (csrc/window_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
 KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cimg_decode_blocks", "cimg_deinterleave",
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
-           "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide")
+           "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -40,10 +41,11 @@ EXPORTS = (
     "cimg_device_malloc", "cimg_device_free", "cimg_memcpy_h2d", "cimg_memcpy_d2h", "cimg_host_malloc", "cimg_host_free",
     "cimg_engine_enable_timing", "cimg_engine_reset_timing", "cimg_engine_kernel_time", "cimg_engine_kernel_samples", "cimg_engine_decode_stats", "cimg_engine_zstd_stats", "cimg_kernel_name",
     "cimg_engine_debug_stamps", "cimg_engine_read_stamps", "cimg_shared_engine", "cimg_context_cparams",
+    "cimg_decompress_windows_device", "cimg_decompress_windows_host", "cimg_engine_window_stats",
     # include/blosc2.h
     "blosc2_create_cctx", "blosc2_create_dctx", "blosc2_free_ctx", "blosc2_compress_ctx",
     "blosc2_decompress_ctx", "blosc2_cbuffer_sizes", "blosc2_schunk_new", "blosc2_schunk_free",
-    "blosc2_schunk_append_chunk", "register_filters", "print_error",
+    "blosc2_schunk_append_chunk", "register_filters", "print_error", "blosc2_getitem_ctx",
 )
 
 
@@ -57,6 +59,21 @@ class CParams(C.Structure):
     _fields_ = [("typesize", C.c_int32), ("clevel", C.c_int32), ("blocksize", C.c_int32),
                 ("compcode", C.c_int32), ("splitmode", C.c_int32),
                 ("filters", C.c_uint8 * 6), ("filters_meta", C.c_uint8 * 6)]
+
+
+class Window(C.Structure):
+    """cimg_window (include/cimg_hip.h)"""
+    _fields_ = [("chunk_first", C.c_int32), ("chunk_count", C.c_int32), ("origin", C.c_int64), ("row_pitch", C.c_int64),
+                ("width", C.c_int32), ("height", C.c_int32), ("out_off", C.c_int64), ("out_pitch", C.c_int64)]
+
+
+def windows(specs):
+    """dicts (or Window) with the fields of cimg_window -> a ctypes array"""
+    arr = (Window * max(len(specs), 1))()
+    for i, s in enumerate(specs):
+        for k, v in (s.items() if isinstance(s, dict) else ((f, getattr(s, f)) for f, _ in Window._fields_)):
+            setattr(arr[i], k, int(v))
+    return arr
 
 
 class Blosc2CParams(C.Structure):
@@ -137,6 +154,10 @@ def load():
     L.blosc2_decompress_ctx.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
     L.blosc2_cbuffer_sizes.argtypes = [vp, i32p, i32p, i32p]
     L.print_error.argtypes = [C.c_int]
+    L.cimg_decompress_windows_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.cimg_decompress_windows_host.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp]
+    L.cimg_engine_window_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.blosc2_getitem_ctx.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_int, vp, C.c_int32]
     L.print_error.restype = C.c_char_p
     _lib = L
     return L
@@ -370,6 +391,39 @@ class Engine:
         if check:
             self._check(rc)
         return [raw[o:o + n] for o, n in zip(raw_off, nb)], status
+
+    # ---- windows (include/cimg_hip.h: cimg_window) ----
+    def decompress_windows_device(self, d_comp, comp_off, nbytes, blocksize, typesize, specs, d_out, comp_size=None, check=True):
+        """windows of device-resident chunks into device memory at d_out; returns the per-chunk status"""
+        comp_off, nbytes, blocksize = _i64(comp_off), _i32(nbytes), _i32(blocksize)
+        cs = _i32(comp_size) if comp_size is not None else None
+        w = windows(specs)
+        status = np.zeros(nbytes.size, np.int32)
+        rc = load().cimg_decompress_windows_device(self.handle, nbytes.size, d_comp, _ptr(comp_off), _ptr(cs) if cs is not None else None,
+                                                   _ptr(nbytes), _ptr(blocksize), typesize, len(specs), w, d_out, _ptr(status))
+        if check:
+            self._check(rc)
+        return status if check else (rc, status)
+
+    def decompress_windows_host(self, chunks, specs, out, check=True):
+        """chunks: list of bytes; out: a writable uint8 numpy array the windows' out_off / out_pitch point into"""
+        sizes = [len(c) for c in chunks]
+        comp_off = _i64(np.concatenate([[0], np.cumsum(sizes[:-1], dtype=np.int64)]))
+        comp = np.frombuffer(b"".join(chunks) + bytes(16), np.uint8)
+        held = _i32(sizes)
+        w = windows(specs)
+        status = np.zeros(len(chunks), np.int32)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous
+        rc = load().cimg_decompress_windows_host(self.handle, len(chunks), _ptr(comp), _ptr(comp_off), _ptr(held), len(specs), w, _ptr(out),
+                                                 _ptr(status))
+        if check:
+            self._check(rc)
+        return status if check else (rc, status)
+
+    def window_stats(self):
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        load().cimg_engine_window_stats(self.handle, C.byref(a), C.byref(b), C.byref(c))
+        return {"blocks_decoded": a.value, "chunks_whole": b.value, "comp_bytes_uploaded": c.value}
 
     # ---- timing ----
     def enable_timing(self, on=True):

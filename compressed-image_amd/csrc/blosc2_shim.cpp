@@ -10,11 +10,7 @@
 #include "../../include/blosc2.h"
 #include "../../include/cimg_hip.h"
 
-struct blosc2_context_s {
-    bool compress;
-    cimg_cparams cp;
-    bool unsupported_params;     // prefilter / dict / non in-memory requests
-};
+#include "blosc2_context.h"
 
 namespace {
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 
 #include "plan.h"
 #include "wide_plan.h"
+#include "window_plan.h"
 #include "assemble_kernel.h"
 #include "deinterleave_kernel.h"
 #include "zstd_kernel.h"
@@ -201,6 +203,18 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_wide(WideDecodeArg
     }
 }
 
+// Windows (window_kernel.h): workgroup k decodes the block of work item k -- staged as cimg_decode_blocks stages it -- and writes only
+// the bytes of its window; copy-mode items cut a window out of a chunk the batch path decoded whole.
+extern "C" __global__ __launch_bounds__(256) void cimg_decode_window(WindowArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    WindowBlock wb(a, lds, (int)blockIdx.x);
+    wb.phase_a(wave);
+    __syncthreads();
+    wb.phase_w(wave);
+}
+
 // zstd blocks beyond the normal kernels' LDS.  Encode: cimg_encode_wide's waves with zstd_wide_encode (hash table and FSE tables in
 // LDS, sequences in a device-memory area per wave).  Decode, behind cimg_zstd_walk: the replay with its planes in a device-memory
 // slot per single-wave workgroup, which walks blocks blk_first + k, k + G, ... of the group.
@@ -318,7 +332,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block
+    int max_dyn_lds[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -352,6 +366,10 @@ struct cimg_engine {
     DevBuf wide_zseq, wide_zslots;        // zstd on the wide paths: per-wave sequence records (encode), per-workgroup replay slots (decode)
     PinBuf h_descs_wide, h_wst;
     std::vector<uint8_t> shadow_wide;
+    // window calls (window_plan.h): work items, descriptors, status words, chunks decoded whole, the host call's staged windows
+    DevBuf win_items, win_descs, win_whole, win_out;
+    PinBuf h_win_items, h_win_descs, h_win_st;
+    WindowStats win_stats;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
     bool claunched = false;               // compress_launch got past the planner and the allocations: h_out holds (or will hold) this batch's sizes
 
@@ -503,6 +521,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_ZSTD_FUSED: return "cimg_decode_zstd_fused";
     case CIMG_K_ZSTD_SEQ: return "cimg_zstd_seq";
     case CIMG_K_ZSTD_LIT: return "cimg_zstd_lit";
+    case CIMG_K_DECODE_WINDOW: return "cimg_decode_window";
     default: return "?";
     }
 }
@@ -1922,6 +1941,224 @@ int cimg_decompress_batch_host_sized(cimg_engine* e, int32_t nchunks, const void
     if ((rc = e->hip(hipStreamSynchronize(e->s_d2h), "pixels D2H"))) return rc;
     if (first_bad) e->err = chunk_error;
     return first_bad;
+}
+
+}  // extern "C"
+
+// ---- windows (window_plan.h, window_kernel.h) --------------------------------------------------------
+static_assert(sizeof(cimg_window) == sizeof(WindowSpec) && offsetof(cimg_window, out_pitch) == offsetof(WindowSpec, out_pitch), "cimg_window != WindowSpec");
+
+namespace {
+
+// run_windows' device side: chunks decoded whole go through the batch path into win_whole, the window launch runs on the stream
+struct EngineWindowEnv {
+    cimg_engine* e;
+    const uint8_t* d_comp;
+    const int64_t* comp_off;
+    const int32_t* comp_size;          // may be null
+    const int32_t* nbytes;
+    const int32_t* blocksize;
+    uint8_t* d_out;
+    int32_t typesize;                  // 0: the host checked every header's typesize already
+
+    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
+    {
+        int rc;
+        if ((rc = e->reserve(e->win_whole, (size_t)total + 64))) return rc;
+        const size_t n = list.size();
+        std::vector<int64_t> co(n);
+        std::vector<int32_t> cs(n), nb(n), bs(n);
+        for (size_t k = 0; k < n; k++) {
+            const int i = list[k];
+            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
+        }
+        rc = cimg_decompress_batch_device_sized(e, (int32_t)n, d_comp, co.data(), cs.data(), nb.data(), bs.data(), e->win_whole.p,
+                                                dst_off.data(), st);
+        if (rc < 0) {                  // refused before any chunk had a status of its own: it is every listed chunk's
+            bool any = false;
+            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
+            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
+        }
+        return 0;
+    }
+
+    int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
+    {
+        int rc;
+        const int nchunks = (int)plan.descs.size();
+        const size_t ib = items.size() * sizeof(WindowItem), db = plan.descs.size() * sizeof(ChunkDesc), sb = (size_t)nchunks * 4;
+        if ((rc = e->reserve(e->h_win_items, ib)) || (rc = e->reserve(e->win_items, ib))) return rc;
+        if ((rc = e->reserve(e->h_win_descs, db)) || (rc = e->reserve(e->win_descs, db))) return rc;
+        if ((rc = e->reserve(e->h_win_st, sb))) return rc;
+        ChunkDesc* hd = (ChunkDesc*)e->h_win_descs.p;
+        memcpy(hd, plan.descs.data(), db);
+        for (int i = 0; i < nchunks; i++) {
+            hd[i].comp_off = plan.touched[(size_t)i] ? comp_off[i] : 0;
+            hd[i].destsize = comp_size ? comp_size[i] : 0x7fffffff;
+        }
+        memcpy(e->h_win_items.p, items.data(), ib);
+        memset(e->h_win_st.p, 0, sb);
+        int32_t* d_st = nullptr;
+        if ((rc = e->device_alias(e->h_win_st, &d_st))) return rc;
+        if ((rc = e->hip(hipMemcpyAsync(e->win_items.p, e->h_win_items.p, ib, hipMemcpyHostToDevice, e->stream), "window items H2D"))) return rc;
+        if ((rc = e->hip(hipMemcpyAsync(e->win_descs.p, e->h_win_descs.p, db, hipMemcpyHostToDevice, e->stream), "window descs H2D"))) return rc;
+        WindowArgs wa{};
+        wa.d = DecodeArgs{(const ChunkDesc*)e->win_descs.p, nchunks, d_comp, d_out, d_st, plan.lds_bytes, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0};
+        wa.items = (const WindowItem*)e->win_items.p;
+        wa.whole = (const uint8_t*)e->win_whole.p;
+        wa.out = d_out;
+        wa.typesize = typesize;
+        wa.nitems = (int32_t)items.size();
+        if ((rc = e->allow_lds(cimg_decode_window, 12, plan.lds_bytes))) return rc;
+        e->begin_batch(1);
+        rc = e->launch(CIMG_K_DECODE_WINDOW, cimg_decode_window, wa, (int)items.size(), 256, plan.lds_bytes);
+        const int src = cimg_engine_synchronize(e);
+        if (rc || src) return rc ? rc : src;
+        const int32_t* hs = (const int32_t*)e->h_win_st.p;
+        for (int i = 0; i < nchunks; i++) if (hs[i] != 0 && status[i] == 0) status[i] = hs[i];
+        return 0;
+    }
+};
+
+int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
+                const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int32_t check_ts, const std::vector<uint8_t>& hint,
+                int32_t nwindows, const cimg_window* w, void* d_out, int32_t* status)
+{
+    EngineWindowEnv env{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize, (uint8_t*)d_out, check_ts};
+    WindowStats st;
+    const int rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, reinterpret_cast<const WindowSpec*>(w), hint, status, &st);
+    e->win_stats = st;
+    if (rc == ERR_INVALID_PARAM) return e->fail(rc, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
+                                                    "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
+    if (rc < 0) {
+        for (int i = 0; i < nchunks; i++) if (status[i] == rc) return e->fail(rc, "chunk %d failed to decode (code %d)", i, rc);
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
+                                   const int32_t* nbytes, const int32_t* blocksize, int32_t typesize, int32_t nwindows, const cimg_window* w,
+                                   void* d_out, int32_t* status)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->win_stats = WindowStats{};
+    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (nwindows == 0 || nchunks == 0) return nwindows == 0 ? 0 : e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    if (!w || !comp_off || !nbytes || !blocksize || !status || !d_comp || !d_out) return e->fail(ERR_INVALID_PARAM, "null argument");
+    if (typesize <= 0 || typesize > 255) return e->fail(ERR_INVALID_PARAM, "typesize %d", typesize);
+    (void)hipSetDevice(e->device);
+    e->dflight_open = false;
+    std::vector<int32_t> ts((size_t)nchunks, typesize);
+    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows, w, d_out, status);
+}
+
+int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
+                                 int32_t nwindows, const cimg_window* w, void* h_out, int32_t* status)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->win_stats = WindowStats{};
+    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (nwindows == 0 || nchunks == 0) return nwindows == 0 ? 0 : e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    if (!w || !comp_off || !status || !h_comp || !h_out) return e->fail(ERR_INVALID_PARAM, "null argument");
+    (void)hipSetDevice(e->device);
+    e->dflight_open = false;
+    e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
+    const uint8_t* hc = (const uint8_t*)h_comp;
+    // the headers of the chunks the windows name (the geometry of their planes); the others are not looked at
+    std::vector<uint8_t> named((size_t)nchunks, 0), hint((size_t)nchunks, 0);
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count)
+            return e->fail(ERR_INVALID_PARAM, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
+        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
+    }
+    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), ts((size_t)nchunks, 0), cb((size_t)nchunks, 0);
+    std::vector<int> flags((size_t)nchunks, 0), version((size_t)nchunks, 0);
+    for (int i = 0; i < nchunks; i++) {
+        if (!named[(size_t)i]) continue;
+        if (comp_size && comp_size[i] < HEADER_LEN) return e->fail(ERR_READ_BUFFER, "chunk %d: %d bytes cannot hold a header", i, comp_size[i]);
+        const uint8_t* c = hc + comp_off[i];
+        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
+        ts[(size_t)i] = c[OFF_TYPESIZE];
+        flags[(size_t)i] = c[OFF_FLAGS];
+        version[(size_t)i] = c[0];
+        hint[(size_t)i] = (flags[(size_t)i] >> 5) == 4 && !(flags[(size_t)i] & FLAG_MEMCPYED);   // zstd: decoded whole
+    }
+    WindowPlan plan;
+    int rc = plan_windows(nchunks, nb.data(), bs.data(), ts.data(), nwindows, reinterpret_cast<const WindowSpec*>(w), hint.data(), &plan);
+    if (rc == ERR_INVALID_PARAM) return e->fail(rc, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
+                                                    "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
+    if (rc < 0) return e->fail(rc, "invalid chunk header among the windows' chunks");
+    // the chunks some window row meets: full header checks, then only they go over PCIe
+    std::vector<int64_t> d_comp_off((size_t)nchunks, 0);
+    std::vector<int32_t> up((size_t)nchunks, 0);
+    int64_t comp_total = 0;
+    for (int i = 0; i < nchunks; i++) {
+        if (!plan.touched[(size_t)i]) continue;
+        int code = 0;
+        if (version[(size_t)i] > 5) code = ERR_VERSION_SUPPORT;
+        else if (cb[(size_t)i] < HEADER_LEN) code = ERR_INVALID_HEADER;
+        else if (comp_size && cb[(size_t)i] > comp_size[i]) code = ERR_READ_BUFFER;
+        if (code) { status[i] = code; return e->fail(code, "chunk %d: invalid header (code %d)", i, code); }
+        d_comp_off[(size_t)i] = comp_total;
+        up[(size_t)i] = cb[(size_t)i];
+        comp_total += ((int64_t)cb[(size_t)i] + 63) & ~63ll;
+    }
+    // the windows come back packed (row after row), and go to h_out at the callers' pitches
+    std::vector<cimg_window> dw(w, w + nwindows);
+    std::vector<int64_t> wbytes((size_t)nwindows, 0);
+    int64_t out_total = 0;
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].width == 0 || w[k].height == 0) continue;
+        const int64_t row = (int64_t)w[k].width * ts[(size_t)w[k].chunk_first];
+        dw[(size_t)k].out_off = out_total;
+        dw[(size_t)k].out_pitch = row;
+        wbytes[(size_t)k] = row * w[k].height;
+        out_total += (wbytes[(size_t)k] + 255) & ~255ll;
+    }
+    if ((rc = e->reserve(e->stage_comp, (size_t)comp_total + 64))) return rc;
+    if ((rc = e->reserve(e->win_out, (size_t)out_total + 64))) return rc;
+    uint8_t* sc = (uint8_t*)e->stage_comp.p;
+    uint8_t* so = (uint8_t*)e->win_out.p;
+    {
+        HostPin pin_in(e, h_comp, comp_off, up.data(), nchunks, false);
+        if ((rc = copy_in(e, e->stream, sc, d_comp_off.data(), hc, comp_off, up.data(), 0, nchunks, "chunk H2D"))) return rc;
+        if ((rc = e->hip(hipMemsetAsync(so, 0, (size_t)out_total, e->stream), "window memset"))) return rc;
+        rc = windows_run(e, nchunks, sc, d_comp_off.data(), cb.data(), nb.data(), bs.data(), ts.data(), 0, hint, nwindows, dw.data(), so, status);
+    }
+    e->win_stats.comp_bytes_uploaded = 0;
+    for (int i = 0; i < nchunks; i++) e->win_stats.comp_bytes_uploaded += up[(size_t)i];
+    if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return rc;
+    const std::string chunk_error = e->err;
+    uint8_t* ho = (uint8_t*)h_out;
+    for (int k = 0; k < nwindows; k++) {
+        if (!wbytes[(size_t)k]) continue;
+        const int64_t row = dw[(size_t)k].out_pitch;
+        int crc;
+        if (w[k].out_pitch == row || w[k].height == 1)
+            crc = e->hip(hipMemcpyAsync(ho + w[k].out_off, so + dw[(size_t)k].out_off, (size_t)wbytes[(size_t)k], hipMemcpyDeviceToHost, e->stream), "window D2H");
+        else
+            crc = e->hip(hipMemcpy2DAsync(ho + w[k].out_off, (size_t)w[k].out_pitch, so + dw[(size_t)k].out_off, (size_t)row, (size_t)row,
+                                          (size_t)w[k].height, hipMemcpyDeviceToHost, e->stream), "window D2H");
+        if (crc) { (void)cimg_engine_synchronize(e); return crc; }
+    }
+    int src;
+    if ((src = cimg_engine_synchronize(e))) return src;
+    if (rc) e->err = chunk_error;
+    return rc;
+}
+
+void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    if (blocks_decoded) *blocks_decoded = e->win_stats.blocks_decoded;
+    if (chunks_whole) *chunks_whole = e->win_stats.chunks_whole;
+    if (comp_bytes_uploaded) *comp_bytes_uploaded = e->win_stats.comp_bytes_uploaded;
 }
 
 }  // extern "C"

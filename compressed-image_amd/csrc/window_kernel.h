@@ -1,0 +1,158 @@
+// window_kernel.h -- cimg_decode_window: decode a chosen set of blocks and store only the bytes of a strided 2-D window
+// (window_plan.h builds the work items).  One 256-thread workgroup per item (window, batch-wide block): the block is staged
+// by DecodeBlock::phase_a (decode_kernel.h) exactly as cimg_decode_blocks stages it, and phase_w then writes, for every
+// window row that meets the block, the row's bytes inside the block -- unfiltered straight out of LDS -- to
+// out + out_off + r * out_pitch + (column * typesize).  Nothing outside the window is written.  Memcpyed and special-zero
+// chunks are cut from the chunk (or from nothing) without staging; items of chunks that were decoded whole beforehand
+// (zstd, blocks beyond LDS: the batch path into engine scratch) are cut from that copy (`b < 0`).
+#pragma once
+#include "decode_kernel.h"
+
+namespace cimg {
+
+struct WindowItem {
+    int32_t chunk;        // batch chunk (its status word)
+    int32_t b;            // batch-wide block to decode; < 0: copy mode, the chunk lies decoded at whole + src_off
+    int32_t r0, r1;       // window rows [r0, r1) that meet the block (or the chunk)
+    int64_t p0;           // plane byte offset of the block's (chunk's) first byte
+    int64_t len;          // copy mode: bytes of the decoded chunk
+    int64_t src_off;      // copy mode: offset of the decoded chunk in `whole`
+    int64_t row0;         // plane byte offset of window row 0
+    int64_t rpitch;       // plane bytes between the starts of consecutive window rows
+    int64_t wbytes;       // bytes of a window row
+    int64_t out_off, out_pitch;
+};
+
+struct WindowArgs {
+    DecodeArgs d;         // descs over the whole batch (raw_off unused), status per chunk, lds_bytes of the launch
+    const WindowItem* items;
+    const uint8_t* whole; // chunks decoded whole (copy-mode items)
+    uint8_t* out;
+    int32_t typesize;     // every decoded chunk's header must say this (0: the host has checked the headers)
+    int32_t nitems;
+};
+
+struct WindowBlock {
+    const WindowArgs& a;
+    uint8_t* lds;
+    WindowItem it;
+    DecodeBlock blk;
+    int mode = 3;          // 0 staged in LDS, 1 memcpyed chunk, 2 zeros, 3 nothing to write, 4 copy mode
+    int64_t blen = 0;      // bytes of the block (chunk) the item covers
+    const uint8_t* src = nullptr;   // memcpyed / copy mode: the block's first byte
+    int lg = -1;           // log2(typesize) when it is a power of two
+
+    CIMG_DEV static WindowItem uniform_item(const WindowItem* p)
+    {
+        WindowItem t = *p;
+        t.chunk = uni(t.chunk); t.b = uni(t.b); t.r0 = uni(t.r0); t.r1 = uni(t.r1);
+        t.p0 = uni64(t.p0); t.len = uni64(t.len); t.src_off = uni64(t.src_off); t.row0 = uni64(t.row0);
+        t.rpitch = uni64(t.rpitch); t.wbytes = uni64(t.wbytes); t.out_off = uni64(t.out_off); t.out_pitch = uni64(t.out_pitch);
+        return t;
+    }
+
+    CIMG_DEV WindowBlock(const WindowArgs& a_, uint8_t* lds_, int k)
+        : a(a_), lds(lds_), it(uniform_item(a_.items + k)), blk(a_.d, lds_, it.b < 0 ? 0 : it.b) {}
+
+    CIMG_DEV void fail(int code) { a.d.status[it.chunk] = code; mode = 3; }
+
+    CIMG_DEV void phase_a(int wave)
+    {
+        mode = 3;
+        if (it.b < 0) {
+            mode = 4;
+            blen = it.len;
+            src = a.whole + it.src_off;
+            return;
+        }
+        const ChunkDesc d = uniform_desc(a.d.descs + it.chunk);
+        const int j = it.b - d.blk0;
+        blen = (j == d.nblocks - 1 && d.leftover) ? d.leftover : d.blocksize;
+        const uint8_t* c = a.d.comp + d.comp_off;
+        // the header checks of phase_a for the two kinds of chunk it would copy straight to the batch's output
+        const u128 h0 = ld128u(c), h1 = ld128u(c + 16);
+        const uint32_t w0 = uni(h0.x);
+        const int flags = (int)((w0 >> 16) & 0xFF), ts = (int)(w0 >> 24);
+        const int nbytes = (int)uni(h0.y), blocksize = (int)uni(h0.z), cbytes = (int)uni(h0.w);
+        const uint32_t b2 = uni(h1.w);
+        if ((w0 & 0xFF) > 5) { fail(ERR_VERSION_SUPPORT); return; }
+        if (nbytes != d.nbytes || blocksize != d.blocksize || (a.typesize && ts != a.typesize) || cbytes < HEADER_LEN) { fail(ERR_INVALID_HEADER); return; }
+        if (cbytes > d.destsize) { fail(ERR_READ_BUFFER); return; }
+        if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) { fail(ERR_VERSION_SUPPORT); return; }
+        const int special = (int)((b2 >> 28) & 7);
+        if (special == SPECIAL_ZERO) { mode = 2; return; }
+        if (special != 0) { fail(ERR_DATA); return; }
+        if (flags & FLAG_MEMCPYED) {
+            if (cbytes != nbytes + HEADER_LEN) { fail(ERR_DATA); return; }
+            mode = 1;
+            src = c + HEADER_LEN + (int64_t)j * blocksize;
+            return;
+        }
+        blk.phase_a(wave);
+        mode = blk.mode == 0 ? 0 : 3;
+        if (mode == 0 && (blk.ts & (blk.ts - 1)) == 0) lg = __builtin_ctz((unsigned)blk.ts);
+    }
+
+    // unfiltered byte k of the staged block (the inverse filters of DecodeBlock::phase_b, one byte at a time)
+    CIMG_DEV uint8_t staged(int k) const
+    {
+        const int ts = blk.ts;
+        if (blk.filter == FILTER_BITSHUFFLE) {
+            const int ne8 = (blk.bsize / ts) & ~7, rowbytes = ne8 >> 3;
+            if (k >= ne8 * ts) return lds[k];
+            const int e = lg >= 0 ? k >> lg : k / ts, jb = lg >= 0 ? k & (ts - 1) : k % ts;
+            const int g = e >> 3, i = e & 7;
+            uint32_t v = 0;
+            for (int bit = 0; bit < 8; bit++) v |= (uint32_t)((lds[(8 * jb + bit) * rowbytes + g] >> i) & 1) << bit;
+            return (uint8_t)v;
+        }
+        if (blk.filter == FILTER_NONE || ts == 1) return lds[blk.ns > 1 ? (k / blk.neblock) * blk.rs + k % blk.neblock : k];
+        const int ne = blk.bsize / ts;
+        if (k >= ne * ts) return lds[k];
+        return lg >= 0 ? lds[blk.plane_base(k & (ts - 1)) + (k >> lg)] : lds[blk.plane_base(k % ts) + k / ts];
+    }
+
+    CIMG_DEV uint8_t byte_at(int64_t k) const
+    {
+        if (mode == 0) return staged((int)k);
+        if (mode == 2) return 0;
+        return src[k];
+    }
+
+    CIMG_DEV void phase_w(int wave)
+    {
+        if (mode == 3) return;
+        const int tid0 = wave * 64;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rs = it.row0 + (int64_t)r * it.rpitch, re = rs + it.wbytes;
+            const int64_t s = rs > it.p0 ? rs : it.p0;
+            const int64_t e = re < it.p0 + blen ? re : it.p0 + blen;
+            if (s >= e) continue;
+            uint8_t* dst = a.out + it.out_off + (int64_t)r * it.out_pitch + (s - rs);
+            const int64_t n = e - s, k0 = s - it.p0;
+            // 4-byte units aligned on the destination: whole units are one dword store, the ragged ends go byte by byte
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += 256) {
+                FOR_LANES(l) {
+                    const int64_t u = u0 + l;
+                    if (u < units) {
+                        const int64_t q0 = 4 * u - mis;
+                        if (q0 >= 0 && q0 + 4 <= n) {
+                            const uint32_t v = (uint32_t)byte_at(k0 + q0) | ((uint32_t)byte_at(k0 + q0 + 1) << 8) |
+                                               ((uint32_t)byte_at(k0 + q0 + 2) << 16) | ((uint32_t)byte_at(k0 + q0 + 3) << 24);
+                            *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                        } else {
+                            for (int i = 0; i < 4; i++) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) dst[q] = byte_at(k0 + q);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+}  // namespace cimg

@@ -1,0 +1,198 @@
+// window_plan.h -- the planner of cimg_decode_window (window_kernel.h) and the order in which a window call runs.  Pure C++,
+// shared by the engine (engine.hip) and the emulator tests (tests/emu/window_emu.cpp, tests/emu/mock_window.cpp), like
+// wide_plan.h.
+//
+// A window is a strided 2-D view over the element space of one PLANE: chunks chunk_first .. chunk_first + chunk_count - 1 of the
+// batch, read back to back.  Its row r covers elements [origin + r * row_pitch, + width) of the plane and goes to the output at
+// out_off + r * out_pitch.  The planner validates every window before anything runs, then lists the blocks that meet some window
+// row -- each once per window -- as work items.  Chunks whose blocks the window kernel cannot stage (zstd, blocks beyond LDS)
+// are decoded whole through the batch path first and cut from there (copy-mode items).
+#pragma once
+#include "wide_plan.h"
+#include "window_kernel.h"
+#include <vector>
+
+namespace cimg {
+
+// = cimg_window (include/cimg_hip.h)
+struct WindowSpec {
+    int32_t chunk_first, chunk_count;
+    int64_t origin;
+    int64_t row_pitch;
+    int32_t width, height;
+    int64_t out_off, out_pitch;
+};
+
+struct WindowPlan {
+    std::vector<ChunkDesc> descs;       // every chunk of the batch (raw_off 0; untouched chunks are never read)
+    std::vector<int64_t> plane_start;   // plane byte offset of each chunk in its window's plane (the last window that names it)
+    std::vector<uint8_t> touched;       // 1: some window row meets the chunk
+    std::vector<uint8_t> whole;         // 1: decoded whole (copy-mode items)
+    std::vector<WindowItem> items;      // decode items (b >= 0) and copy items (b < 0, src_off filled in by the caller)
+    int32_t lds_bytes = 0;              // LDS of the window launch (largest staging among the chunks it decodes block by block)
+    int64_t blocks = 0;                 // decode items
+};
+
+// nbytes / blocksize / typesize: per chunk, from the chunk headers.  whole_hint[i] = 1: chunk i must be decoded whole (its codec says
+// so; wide blocks are found here).  Chunks outside every window's range are not looked at.
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const WindowSpec* w, const uint8_t* whole_hint, WindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan->descs.assign((size_t)nchunks, ChunkDesc{});
+    plan->plane_start.assign((size_t)nchunks, 0);
+    plan->touched.assign((size_t)nchunks, 0);
+    plan->whole.assign((size_t)nchunks, 0);
+    plan->items.clear();
+    plan->lds_bytes = 0;
+    plan->blocks = 0;
+    // validation first: nothing is listed unless every window is good
+    for (int k = 0; k < nwindows; k++) {
+        const WindowSpec& s = w[k];
+        if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
+        if (s.width < 0 || s.height < 0) return ERR_INVALID_PARAM;
+        const int ts = typesize[s.chunk_first];
+        if (ts <= 0) return ERR_INVALID_PARAM;
+        int64_t total = 0;
+        for (int i = s.chunk_first; i < s.chunk_first + s.chunk_count; i++) {
+            if (nbytes[i] < 0 || blocksize[i] <= 0 || (nbytes[i] > 0 && blocksize[i] > nbytes[i])) return ERR_INVALID_HEADER;
+            if (typesize[i] != ts) return ERR_INVALID_PARAM;
+            if (i + 1 < s.chunk_first + s.chunk_count && nbytes[i] % ts) return ERR_INVALID_PARAM;
+            total += nbytes[i];
+        }
+        if (s.width == 0 || s.height == 0) continue;
+        const int64_t elems = total / ts;
+        if (s.height > 1 && s.row_pitch < s.width) return ERR_INVALID_PARAM;
+        if (s.out_pitch < (int64_t)s.width * ts || s.out_off < 0) return ERR_INVALID_PARAM;
+        if (s.origin < 0 || s.origin > elems || s.width > elems) return ERR_INVALID_PARAM;
+        if (s.height > 1 && (s.row_pitch > elems || (int64_t)(s.height - 1) > elems / (s.row_pitch ? s.row_pitch : 1))) return ERR_INVALID_PARAM;
+        const int64_t last = s.origin + (int64_t)(s.height - 1) * (s.height > 1 ? s.row_pitch : 0) + s.width;
+        if (last > elems) return ERR_INVALID_PARAM;
+    }
+    // descriptors
+    int32_t blk = 0;
+    for (int i = 0; i < nchunks; i++) {
+        ChunkDesc& d = plan->descs[(size_t)i];
+        d.nbytes = nbytes[i];
+        d.blocksize = blocksize[i] > 0 ? blocksize[i] : 1;
+        d.nblocks = d.nbytes > 0 ? d.nbytes / d.blocksize : 0;
+        d.leftover = d.nbytes > 0 ? d.nbytes % d.blocksize : 0;
+        if (d.leftover) d.nblocks++;
+        d.blk0 = blk;
+        blk += d.nblocks;
+        plan->whole[(size_t)i] = (whole_hint && whole_hint[i]) || decode_is_wide(d.blocksize);
+    }
+    // items: rows run forward through the plane, so a block met again by the next row is the window's last item
+    for (int k = 0; k < nwindows; k++) {
+        const WindowSpec& s = w[k];
+        if (s.width == 0 || s.height == 0) continue;
+        const int ts = typesize[s.chunk_first];
+        const int cf = s.chunk_first, cn = s.chunk_count;
+        std::vector<int64_t> start((size_t)cn + 1, 0);
+        for (int i = 0; i < cn; i++) start[(size_t)i + 1] = start[(size_t)i] + nbytes[cf + i];
+        for (int i = 0; i < cn; i++) plan->plane_start[(size_t)(cf + i)] = start[(size_t)i];
+        const size_t first_item = plan->items.size();
+        const int64_t rpitch = (int64_t)ts * (s.height > 1 ? s.row_pitch : 0), wbytes = (int64_t)ts * s.width, row0 = (int64_t)ts * s.origin;
+        int ci = 0;
+        for (int r = 0; r < s.height; r++) {
+            const int64_t rs = row0 + (int64_t)r * rpitch, re = rs + wbytes;
+            while (ci + 1 < cn && start[(size_t)ci + 1] <= rs) ci++;
+            for (int c = ci; c < cn && start[(size_t)c] < re; c++) {
+                const int chunk = cf + c;
+                const ChunkDesc& d = plan->descs[(size_t)chunk];
+                const int64_t cs = start[(size_t)c], ce = start[(size_t)c + 1];
+                if (ce <= rs || d.nbytes == 0) continue;
+                plan->touched[(size_t)chunk] = 1;
+                const int64_t lo = (rs > cs ? rs : cs) - cs, hi = (re < ce ? re : ce) - cs;   // [lo, hi) inside the chunk
+                const bool whole = plan->whole[(size_t)chunk] != 0;
+                const int jf = whole ? -1 : (int)(lo / d.blocksize), jl = whole ? -1 : (int)((hi - 1) / d.blocksize);
+                for (int j = jf; j <= jl; j++) {
+                    const int b = whole ? -1 : d.blk0 + j;
+                    if (plan->items.size() > first_item) {
+                        WindowItem& last = plan->items.back();
+                        if (last.chunk == chunk && last.b == b) { last.r1 = r + 1; continue; }
+                    }
+                    WindowItem t{};
+                    t.chunk = chunk; t.b = b; t.r0 = r; t.r1 = r + 1;
+                    t.p0 = whole ? cs : cs + (int64_t)j * d.blocksize;
+                    t.len = whole ? d.nbytes : 0;
+                    t.row0 = row0; t.rpitch = rpitch; t.wbytes = wbytes;
+                    t.out_off = s.out_off; t.out_pitch = s.out_pitch;
+                    plan->items.push_back(t);
+                }
+            }
+        }
+    }
+    for (int i = 0; i < nchunks; i++)
+        if (plan->touched[(size_t)i] && !plan->whole[(size_t)i]) plan->lds_bytes = imax(plan->lds_bytes, decode_lds_bound(plan->descs[(size_t)i].blocksize));
+    for (const WindowItem& t : plan->items) if (t.b >= 0) plan->blocks++;
+    return 0;
+}
+
+struct WindowStats {
+    int64_t blocks_decoded = 0, chunks_whole = 0, comp_bytes_uploaded = 0;
+};
+
+// One window call, in the order the engine and the emulators run it.  Env provides
+//   int decode_whole(const std::vector<int>& chunks, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
+//       -- the batch path over the listed chunks into its scratch (st: one status per listed chunk); < 0 only when the
+//          device itself failed;
+//   int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
+//       -- one window launch over `items`, waited for; a chunk's status word is set when one of its blocks fails.
+// A zstd chunk is recognised by its header: the host call knows it up front (whole_hint), the device call when its blocks come
+// back pending from the window launch -- those chunks then go the whole-chunk way in a second round.
+template <class Env>
+int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                const WindowSpec* w, std::vector<uint8_t> hint, int32_t* status, WindowStats* stats)
+{
+    WindowPlan plan;
+    int rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.empty() ? nullptr : hint.data(), &plan);
+    if (rc < 0) return rc;
+    for (int i = 0; i < nchunks; i++) status[i] = 0;
+    *stats = WindowStats{};
+    std::vector<uint8_t> done_whole((size_t)nchunks, 0);
+    for (int round = 0; round < 2; round++) {
+        std::vector<int> list;
+        std::vector<int64_t> off;
+        std::vector<int64_t> at((size_t)nchunks, -1);
+        int64_t total = 0;
+        for (int i = 0; i < nchunks; i++)
+            if (plan.touched[(size_t)i] && plan.whole[(size_t)i] && !done_whole[(size_t)i]) {
+                list.push_back(i); off.push_back(total); at[(size_t)i] = total;
+                total += ((int64_t)nbytes[i] + 255) & ~(int64_t)255;
+            }
+        if (!list.empty()) {
+            std::vector<int32_t> st(list.size(), 0);
+            if ((rc = env.decode_whole(list, off, total, st.data())) < 0) return rc;
+            for (size_t k = 0; k < list.size(); k++) { status[list[k]] = st[k]; done_whole[(size_t)list[k]] = 1; }
+            stats->chunks_whole += (int64_t)list.size();
+        }
+        std::vector<WindowItem> items;
+        for (const WindowItem& t : plan.items) {
+            if (t.b < 0) {
+                if (at[(size_t)t.chunk] < 0 || status[t.chunk] != 0) continue;          // (a chunk that failed whole: nothing to cut)
+                WindowItem c = t;
+                c.src_off = at[(size_t)t.chunk];
+                items.push_back(c);
+            } else if (round == 0) {
+                items.push_back(t);
+            }
+        }
+        if (!items.empty() && (rc = env.run_items(plan, items, status)) < 0) return rc;
+        std::vector<uint8_t> pending((size_t)nchunks, 0);
+        bool any = false;
+        for (int i = 0; i < nchunks; i++)
+            if (status[i] == STATUS_ZSTD_PENDING || status[i] == STATUS_ZSTD_PENDING_SPLIT) { pending[(size_t)i] = 1; status[i] = 0; any = true; }
+        if (round == 0)
+            for (const WindowItem& t : plan.items) if (t.b >= 0 && !pending[(size_t)t.chunk]) stats->blocks_decoded++;
+        if (!any || round == 1) break;
+        // second round: the chunks found to be zstd, decoded whole and cut
+        if (hint.empty()) hint.assign((size_t)nchunks, 0);
+        for (int i = 0; i < nchunks; i++) if (pending[(size_t)i]) hint[(size_t)i] = 1;
+        if ((rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.data(), &plan)) < 0) return rc;
+    }
+    for (int i = 0; i < nchunks; i++) if (status[i] != 0) return status[i];
+    return 0;
+}
+
+}  // namespace cimg

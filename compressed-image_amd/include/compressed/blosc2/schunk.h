@@ -144,6 +144,63 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					}
 				}
 
+				/// Batch building block of get_region: the rectangle (x, y, w, h) of this table seen as rows of `row_len` elements goes to
+				/// `out` (w elements a row, rows `out_pitch` elements apart).  Lazy chunks are filled here for the part of the rectangle
+				/// they hold; every run of compressed chunks becomes up to three windows of `job` (a partial first row, the rows wholly
+				/// inside the run, a partial last row), so that one engine call serves many tables.
+				void plan_region(T* out, size_t out_pitch, size_t row_len, size_t x, size_t y, size_t w, size_t h, batch::window_job& job) const
+				{
+					if (w == 0 || h == 0) return;
+					auto row_start = [&](size_t r) { return (y + r) * row_len + x; };
+					size_t cs = 0;
+					for (size_t i = 0; i < m_Chunks.size();)
+					{
+						const bool lazy = m_Chunks[i].is_lazy();
+						size_t j = i, ce = cs;
+						while (j < m_Chunks.size() && m_Chunks[j].is_lazy() == lazy) { ce += m_Chunks[j].num_elements; ++j; if (lazy) break; }
+						// rows [r0, r1) meet the run [cs, ce)
+						const size_t r0 = row_start(0) + w > cs ? 0 : (cs - row_start(0) - w) / row_len + 1;
+						size_t r1 = h;
+						if (row_start(0) >= ce) r1 = 0;
+						else if (row_start(h - 1) >= ce) r1 = (ce - row_start(0) + row_len - 1) / row_len;
+						if (lazy)
+						{
+							const T v = std::get<T>(m_Chunks[i].value);
+							for (size_t r = r0; r < r1; ++r)
+							{
+								const size_t a = std::max(row_start(r), cs), b = std::min(row_start(r) + w, ce);
+								if (a < b) std::fill(out + r * out_pitch + (a - row_start(r)), out + r * out_pitch + (b - row_start(r)), v);
+							}
+						}
+						else if (r0 < r1)
+						{
+							const int32_t first = static_cast<int32_t>(job.chunks.size());
+							for (size_t k = i; k < j; ++k) { job.chunks.push_back(m_Chunks[k].bytes().data()); job.held.push_back(m_Chunks[k].bytes().size()); }
+							auto add = [&](size_t ra, size_t rb, bool partial) {
+								if (ra >= rb) return;
+								const size_t a = partial ? std::max(row_start(ra), cs) : row_start(ra);
+								const size_t b = partial ? std::min(row_start(ra) + w, ce) : a + w;
+								cimg_window win{};
+								win.chunk_first = first;
+								win.chunk_count = static_cast<int32_t>(j - i);
+								win.origin = static_cast<int64_t>(a - cs);
+								win.row_pitch = static_cast<int64_t>(row_len);
+								win.width = static_cast<int32_t>(b - a);
+								win.height = static_cast<int32_t>(rb - ra);
+								win.out_pitch = static_cast<int64_t>(out_pitch * sizeof(T));
+								job.windows.push_back(win);
+								job.outs.push_back(reinterpret_cast<std::byte*>(out + ra * out_pitch + (a - row_start(ra))));
+							};
+							size_t ra = r0, rb = r1;
+							if (row_start(ra) < cs) { add(ra, ra + 1, true); ++ra; }
+							if (rb > ra && row_start(rb - 1) + w > ce) { --rb; add(rb, rb + 1, true); }
+							add(ra, rb, false);
+						}
+						cs = ce;
+						i = j;
+					}
+				}
+
 				std::vector<T> chunk(context_ptr& ctx, size_t index) const { return chunk(ctx.get(), index); }
 				std::vector<T> chunk(context_raw_ptr ctx, size_t index) const
 				{

@@ -330,6 +330,41 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				return out;
 			}
 
+			// Windows of several planes in one engine call (cimg_decompress_windows_host): only the blocks the windows meet are decoded
+			// and only the windows' bytes come back.  windows[i] names chunks by their index in `chunks`; its out_off is filled in
+			// here from outs[i], where its first element goes.
+			struct window_job
+			{
+				std::vector<const std::byte*> chunks;
+				std::vector<size_t> held;               // bytes each chunk buffer holds
+				std::vector<cimg_window> windows;
+				std::vector<std::byte*> outs;
+			};
+
+			inline void decompress_windows(window_job& job)
+			{
+				if (job.windows.empty()) return;
+				const std::byte* cbase = job.chunks.empty() ? nullptr : job.chunks[0];
+				for (const auto* c : job.chunks) if (c < cbase) cbase = c;
+				std::byte* obase = job.outs[0];
+				for (auto* o : job.outs) if (o < obase) obase = o;
+				const size_t n = job.chunks.size();
+				std::vector<int64_t> comp_off(n);
+				std::vector<int32_t> held(n), status(n);
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (job.held[i] > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+						throw std::out_of_range(detail::text("Blosc2 chunk size may not exceed numeric limit of int32_t, got ", job.held[i]));
+					comp_off[i] = job.chunks[i] - cbase;
+					held[i] = static_cast<int32_t>(job.held[i]);
+				}
+				for (size_t k = 0; k < job.windows.size(); ++k) job.windows[k].out_off = job.outs[k] - obase;
+				const int rc = cimg_decompress_windows_host(engine(), static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+					static_cast<int32_t>(job.windows.size()), job.windows.data(), obase, status.data());
+				if (rc < 0)
+					throw std::runtime_error(detail::text("Error code ", rc, " while decompressing a region of blosc2 chunks (", cimg_last_error(engine()), ")"));
+			}
+
 			// one chunk -> its pixels; chunk_bytes = what the chunk buffer really holds (0: unknown, trust the header)
 			struct target { const std::byte* chunk; std::byte* out; size_t capacity; size_t chunk_bytes = 0; };
 

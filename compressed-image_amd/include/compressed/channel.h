@@ -137,6 +137,35 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return std::visit([&](const auto& s) { return s.to_uncompressed(const_cast<blosc2::context_ptr&>(m_DecompressionContext)); }, *m_Schunk);
 		}
 
+		/// The rectangle [x, x + width) x [y, y + height) of the channel, row-major (width elements a row).  Only the blocks the
+		/// rectangle meets are decoded, on the device, and only its pixels come back; lazy chunks fill their part on the host.
+		std::vector<T> get_region(size_t x, size_t y, size_t width, size_t height) const
+		{
+			std::vector<T> out(width * height);
+			get_region(std::span<T>(out), x, y, width, height);
+			return out;
+		}
+		void get_region(std::span<T> out, size_t x, size_t y, size_t width, size_t height) const
+		{
+			check_region(x, y, width, height);
+			if (out.size() < width * height)
+				throw std::invalid_argument(detail::text("get_region: buffer holds ", out.size(), " elements, the region has ", width * height));
+			blosc2::batch::window_job job;
+			plan_region(out.data(), width, x, y, width, height, job);
+			blosc2::batch::decompress_windows(job);
+		}
+		/// Batch building block of image<T>::get_region: queue this channel's windows (rows out_pitch elements apart).
+		void plan_region(T* out, size_t out_pitch, size_t x, size_t y, size_t width, size_t height, blosc2::batch::window_job& job) const
+		{
+			visit([&](const auto& s) { s.plan_region(out, out_pitch, m_Width, x, y, width, height, job); return 0; });
+		}
+		void check_region(size_t x, size_t y, size_t width, size_t height) const
+		{
+			if (x > m_Width || y > m_Height || width > m_Width - x || height > m_Height - y)
+				throw std::out_of_range(detail::text("Region (x ", x, ", y ", y, ", width ", width, ", height ", height, ") is out of bounds for a channel of ",
+					m_Width, " x ", m_Height));
+		}
+
 		/// The chunk table itself (used by image<T> to batch across channels).
 		blosc2::schunk_var<T>& chunks() { require(); return *m_Schunk; }
 		const blosc2::schunk_var<T>& chunks() const { require(); return *m_Schunk; }

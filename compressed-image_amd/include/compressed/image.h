@@ -186,6 +186,22 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return out;
 		}
 
+		/// The rectangle [x, x + width) x [y, y + height) of every channel (row-major, width elements a row) -- one engine call
+		/// that decodes only the blocks the rectangle meets.
+		std::vector<std::vector<T>> get_region(size_t x, size_t y, size_t width, size_t height) const
+		{
+			std::vector<std::vector<T>> out(m_Channels.size());
+			blosc2::batch::window_job job;
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				m_Channels[ch].check_region(x, y, width, height);
+				out[ch].resize(width * height);
+				m_Channels[ch].plan_region(out[ch].data(), width, x, y, width, height, job);
+			}
+			blosc2::batch::decompress_windows(job);
+			return out;
+		}
+
 		/// All channels into caller-owned memory (num_channels * height * width elements, channel-major): no
 		/// intermediate vectors, no zero fill -- what the Python binding uses to decode straight into a numpy array.
 		void decompress_into(std::span<T> out) const

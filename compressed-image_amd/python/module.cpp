@@ -165,6 +165,19 @@ namespace
 			});
 		}
 
+		// the rectangle (x, y, width, height) as a (height, width) array: only the blocks it meets are decoded
+		py::array get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height) const
+		{
+			if (x < 0 || y < 0 || width < 0 || height < 0) throw py::value_error("region coordinates and sizes must be >= 0");
+			return visit([&]<typename T>(compressed::channel<T>& ch) {
+				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				py::array out(np_dtype<T>(), std::vector<py::ssize_t>{ height, width });
+				ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(width * height)), static_cast<size_t>(x),
+					static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				return out;
+			});
+		}
+
 		template <typename T> static void check_chunk_array(const py::array& a, size_t elems, bool exact)
 		{
 			if (!a.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
@@ -240,6 +253,27 @@ namespace
 			for (size_t i = 0; i < n; ++i) out.push_back(channel(i));
 			return out;
 		}
+		// the rectangle of every channel, one engine call: a list of (height, width) arrays
+		py::list get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height) const
+		{
+			if (x < 0 || y < 0 || width < 0 || height < 0) throw py::value_error("region coordinates and sizes must be >= 0");
+			return visit([&]<typename T>(const img_ptr<T>& img) {
+				compressed::blosc2::batch::window_job job;
+				std::vector<py::array> arrays;
+				for (const auto& ch : img->channels())
+				{
+					ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+					py::array a(np_dtype<T>(), std::vector<py::ssize_t>{ height, width });
+					ch.plan_region(static_cast<T*>(a.mutable_data()), static_cast<size_t>(width), static_cast<size_t>(x), static_cast<size_t>(y),
+						static_cast<size_t>(width), static_cast<size_t>(height), job);
+					arrays.push_back(a);
+				}
+				compressed::blosc2::batch::decompress_windows(job);
+				py::list out;
+				for (auto& a : arrays) out.append(a);
+				return out;
+			});
+		}
 		py::array get_decompressed() const
 		{
 			return visit([]<typename T>(const img_ptr<T>& img) {
@@ -295,7 +329,8 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_chunk", &Channel::get_chunk, py::arg("chunk_index"))
 		.def("get_chunk", &Channel::get_chunk_into, py::arg("chunk_index"), py::arg("array"))
 		.def("set_chunk", &Channel::set_chunk, py::arg("chunk_index"), py::arg("array"))
-		.def("get_decompressed", &Channel::get_decompressed);
+		.def("get_decompressed", &Channel::get_decompressed)
+		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"));
 
 	py::class_<Image>(m, "Image", py::module_local())
 		.def(py::init<const py::object&, const std::vector<py::array>&, size_t, size_t, std::vector<std::string>, codec, size_t, size_t, size_t>(),
@@ -309,6 +344,7 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("channel", &Image::channel, py::arg("key"))
 		.def("channels", &Image::channels)
 		.def("get_decompressed", &Image::get_decompressed)
+		.def("get_region", &Image::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("print_statistics", [](const Image& i) { i.visit([](auto& img) { img->print_statistics(); return 0; }); })
 		.def("compression_ratio", [](const Image& i) { return i.visit([](auto& img) { return img->compression_ratio(); }); })

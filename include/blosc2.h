@@ -127,6 +127,11 @@ int blosc2_compress_ctx(blosc2_context* context, const void* src, int32_t srcsiz
 /* Decompress one chunk; returns the number of decompressed bytes or < 0. */
 int blosc2_decompress_ctx(blosc2_context* context, const void* src, int32_t srcsize, void* dest, int32_t destsize);
 int blosc2_cbuffer_sizes(const void* cbuffer, int32_t* nbytes, int32_t* cbytes, int32_t* blocksize);
+/* Items [start, start + nitems) of one chunk (items of the header's typesize) into dest; only the blocks that hold them are
+ * decoded.  Returns nitems * typesize, or BLOSC2_ERROR_INVALID_PARAM (start < 0, or past the chunk's end), BLOSC2_ERROR_WRITE_BUFFER
+ * (dest too small), BLOSC2_ERROR_READ_BUFFER (srcsize below the header's cbytes), BLOSC2_ERROR_NULL_POINTER, or the context checks
+ * of blosc2_decompress_ctx. */
+int blosc2_getitem_ctx(blosc2_context* context, const void* src, int32_t srcsize, int start, int nitems, void* dest, int32_t destsize);
 
 blosc2_schunk* blosc2_schunk_new(blosc2_storage* storage);
 int blosc2_schunk_free(blosc2_schunk* schunk);

@@ -166,6 +166,42 @@ int cimg_decompress_batch_host_sized(cimg_engine* e, int32_t nchunks,
                                      void* h_raw, const int64_t* raw_off, const int32_t* raw_capacity,
                                      int32_t* status);
 
+/* ---- windows: random access into compressed planes -------------------------------------------------
+ * A window is a strided 2-D view over the element space of one PLANE: chunks chunk_first .. chunk_first + chunk_count - 1 of the
+ * batch, read back to back (what to_uncompressed concatenates).  Row r of the window is the `width` elements starting at plane
+ * element origin + r * row_pitch; it goes to out + out_off + r * out_pitch.  Only the blocks that meet some window row are decoded,
+ * and nothing outside the window's rows is written (the gaps between output rows are the caller's).  Examples: a rectangle of a
+ * W-wide channel (origin = y0 * W + x0, row_pitch = W), an item range of one chunk (height 1), one window per channel of an image.
+ * Every window is checked before anything runs; a window outside its plane, width or height < 0, row_pitch < width with height > 1,
+ * out_pitch < width * typesize, chunks of one plane with different typesizes, a chunk other than the plane's last whose nbytes is no
+ * multiple of the typesize, or a chunk range outside the batch is BLOSC2_ERROR_INVALID_PARAM, and the engine stays usable.  A window
+ * of width or height 0 does nothing.  status[i] receives chunk i's code; chunks no window row meets get 0 and are not read.  zstd
+ * chunks and chunks with blocks beyond the normal decoder's LDS are decoded whole on the device (engine scratch) and the window is
+ * cut from there.  Both calls return the first failing chunk's code (or 0), take the engine's lock, and void a pending
+ * cimg_decompress_batch_device_begin (its _fetch then fails); the host call reuses the staging area as well, so it also voids a
+ * pending cimg_compress_batch_host_begin / _fetch. */
+typedef struct cimg_window {
+    int32_t chunk_first, chunk_count;   /* the batch's chunks that form this window's plane, in order */
+    int64_t origin;                     /* element index (within that plane) of the window's first element */
+    int64_t row_pitch;                  /* elements between the starts of consecutive window rows in the plane */
+    int32_t width, height;              /* elements per row, rows */
+    int64_t out_off, out_pitch;         /* byte offset of the first element in the output; bytes between output rows */
+} cimg_window;
+
+/* Device-resident chunks (offsets and sizes as cimg_decompress_batch_device_sized; comp_size may be NULL) and a device-resident
+ * output.  nbytes[i] / blocksize[i] are the values in chunk i's header; every chunk must say `typesize`. */
+int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                   const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize,
+                                   int32_t typesize, int32_t nwindows, const cimg_window* w, void* d_out, int32_t* status);
+/* Host-resident chunks and output: the headers are read on the host, only the chunks some window row meets go over PCIe (through
+ * the engine's staging area), and only the windows' bytes come back, to h_out at the callers' offsets and pitches.  comp_size may
+ * be NULL (the headers' cbytes are trusted). */
+int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                 const int32_t* comp_size, int32_t nwindows, const cimg_window* w, void* h_out, int32_t* status);
+/* The last window call on this engine: blocks decoded by the window launch, chunks decoded whole, compressed bytes uploaded (host
+ * call only).  Any pointer may be NULL. */
+void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded);
+
 /* ---- glue between the blosc2 shim and the batched calls ----------------------------------------------
  * The single-chunk blosc2_*_ctx calls run on one process-wide engine (device $CIMG_DEVICE, else the
  * current HIP device); cimg_shared_engine() hands it out so that host code holding blosc2 contexts
@@ -196,7 +232,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* blocks beyond the normal kernels' LDS (up to 256 KiB): */
        CIMG_K_ENCODE_WIDE = 12, CIMG_K_DECODE_WIDE = 13,
        /* zstd blocks beyond the normal kernels' LDS: the wide encoder's zstd instance, the replay out of device-memory slots */
-       CIMG_K_ENCODE_WIDE_ZSTD = 14, CIMG_K_ZSTD_REPLAY_WIDE = 15, CIMG_K_COUNT = 16 };
+       CIMG_K_ENCODE_WIDE_ZSTD = 14, CIMG_K_ZSTD_REPLAY_WIDE = 15,
+       /* the window launch of cimg_decompress_windows_device / _host */
+       CIMG_K_DECODE_WINDOW = 16, CIMG_K_COUNT = 17 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);
