@@ -586,7 +586,8 @@ CIMG_DEV int blosclz_decode_wave(uint8_t* lds, int base, int n, int cs, int csiz
                 k += 2;
                 ref = op - ofs - BLZ_MAX_DISTANCE;
             }
-            if (len > oend - op || ref - 1 < base) { bad = true; break; }
+            // a match that ends the input is not copied (the library stops in front of it and comes up short): an error
+            if (len > oend - op || ref - 1 < base || wbase + k >= iend) { bad = true; break; }
             ip = wbase + k;
             ref--;
             if (len <= 64) {
