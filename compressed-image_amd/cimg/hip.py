@@ -16,12 +16,14 @@ K_ENCODE, K_LAYOUT, K_EMIT, K_DECODE, K_DEINTERLEAVE, K_DECODE_ZSTD, K_ENCODE_ZS
 K_ENCODE_WIDE, K_DECODE_WIDE = 12, 13          # blocks beyond the normal kernels' LDS (csrc/wide_kernel.h)
 K_ENCODE_WIDE_ZSTD, K_ZSTD_REPLAY_WIDE = 14, 15  # ... of zstd chunks
 K_DECODE_WINDOW = 16                           # windows: the blocks a window meets (csrc/window_kernel.h)
+K_UPDATE_PATCH, K_UPDATE_LAYOUT, K_UPDATE_EMIT = 17, 18, 19   # window writes (csrc/update_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
 KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cimg_decode_blocks", "cimg_deinterleave",
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
-           "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window")
+           "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
+           "cimg_update_patch", "cimg_update_layout", "cimg_update_emit")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -42,6 +44,7 @@ EXPORTS = (
     "cimg_engine_enable_timing", "cimg_engine_reset_timing", "cimg_engine_kernel_time", "cimg_engine_kernel_samples", "cimg_engine_decode_stats", "cimg_engine_zstd_stats", "cimg_kernel_name",
     "cimg_engine_debug_stamps", "cimg_engine_read_stamps", "cimg_shared_engine", "cimg_context_cparams",
     "cimg_decompress_windows_device", "cimg_decompress_windows_host", "cimg_engine_window_stats",
+    "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
     # include/blosc2.h
     "blosc2_create_cctx", "blosc2_create_dctx", "blosc2_free_ctx", "blosc2_compress_ctx",
     "blosc2_decompress_ctx", "blosc2_cbuffer_sizes", "blosc2_schunk_new", "blosc2_schunk_free",
@@ -59,6 +62,9 @@ class CParams(C.Structure):
     _fields_ = [("typesize", C.c_int32), ("clevel", C.c_int32), ("blocksize", C.c_int32),
                 ("compcode", C.c_int32), ("splitmode", C.c_int32),
                 ("filters", C.c_uint8 * 6), ("filters_meta", C.c_uint8 * 6)]
+
+
+_ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)   # cimg_alloc_fn
 
 
 class Window(C.Structure):
@@ -157,6 +163,9 @@ def load():
     L.cimg_decompress_windows_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
     L.cimg_decompress_windows_host.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp]
     L.cimg_engine_window_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.cimg_update_windows_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.cimg_update_windows_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
+    L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
     L.blosc2_getitem_ctx.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_int, vp, C.c_int32]
     L.print_error.restype = C.c_char_p
     _lib = L
@@ -419,6 +428,57 @@ class Engine:
         if check:
             self._check(rc)
         return status if check else (rc, status)
+
+    # ---- window writes (include/cimg_hip.h: cimg_update_windows_*) ----
+    def update_windows_device(self, p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size=None,
+                              check=True):
+        """windows of d_src written into device-resident chunks; the touched chunks' new forms go to d_new + new_off[i].
+        Returns (new_cbytes, status) (with check=False: (rc, new_cbytes, status))."""
+        comp_off, nbytes, blocksize, destsize, new_off = _i64(comp_off), _i32(nbytes), _i32(blocksize), _i32(destsize), _i64(new_off)
+        cs = _i32(comp_size) if comp_size is not None else None
+        w = windows(specs)
+        status = np.zeros(nbytes.size, np.int32)
+        ncb = np.zeros(nbytes.size, np.int32)
+        rc = load().cimg_update_windows_device(self.handle, C.byref(p), nbytes.size, d_comp, _ptr(comp_off),
+                                               _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), _ptr(destsize),
+                                               len(specs), w, d_src, d_new, _ptr(new_off), _ptr(ncb), _ptr(status))
+        if check:
+            self._check(rc)
+            return ncb, status
+        return rc, ncb, status
+
+    def update_windows_host(self, p, chunks, destsize, specs, src, check=True):
+        """chunks: list of bytes; src: a uint8 numpy array the windows' out_off / out_pitch point into.  Returns (list of new chunk
+        bytes, None where untouched, status) (with check=False: (rc, new chunks, status))."""
+        sizes = [len(c) for c in chunks]
+        comp_off = _i64(np.concatenate([[0], np.cumsum(sizes[:-1], dtype=np.int64)]))
+        comp = np.frombuffer(b"".join(chunks) + bytes(16), np.uint8)
+        held, destsize = _i32(sizes), _i32(destsize)
+        w = windows(specs)
+        n = len(chunks)
+        status = np.zeros(n, np.int32)
+        ncb = np.zeros(n, np.int32)
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep = []
+
+        def alloc(_user, nbytes):
+            b = C.create_string_buffer(max(int(nbytes), 1))
+            keep.append(b)
+            return C.addressof(b)
+        cb = _ALLOC_FN(alloc)
+        src = np.ascontiguousarray(src).view(np.uint8)
+        rc = load().cimg_update_windows_host(self.handle, C.byref(p), n, _ptr(comp), _ptr(comp_off), _ptr(held), _ptr(destsize), len(specs),
+                                             w, _ptr(src), cb, None, ptrs, _ptr(ncb), _ptr(status))
+        new = [C.string_at(ptrs[i], int(ncb[i])) if ptrs[i] else None for i in range(n)]
+        if check:
+            self._check(rc)
+            return new, status
+        return rc, new, status
+
+    def update_stats(self):
+        v = [C.c_int64(0) for _ in range(4)]
+        load().cimg_engine_update_stats(self.handle, *[C.byref(x) for x in v])
+        return {"blocks_decoded": v[0].value, "blocks_encoded": v[1].value, "chunks_whole": v[2].value, "bytes_uploaded": v[3].value}
 
     def window_stats(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)

@@ -16,6 +16,7 @@
 #include "plan.h"
 #include "wide_plan.h"
 #include "window_plan.h"
+#include "update_plan.h"
 #include "assemble_kernel.h"
 #include "deinterleave_kernel.h"
 #include "zstd_kernel.h"
@@ -234,6 +235,37 @@ extern "C" __global__ __launch_bounds__(64) void cimg_zstd_replay_wide(WideDecod
     }
 }
 
+// Window writes (update_kernel.h).  Patch: workgroup k stages block k as cimg_decode_window does (or not at all: a block the windows
+// cover, a chunk decoded whole), writes it unfiltered to its slot and copies the window rows over it, one window after the other.
+extern "C" __global__ __launch_bounds__(256) void cimg_update_patch(PatchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    PatchBlock pb(a, lds, (int)blockIdx.x);
+    pb.phase_a(wave);
+    __syncthreads();
+    pb.phase_base(wave);
+    for (int k = 0; k < pb.u.nitems; k++) {
+        __syncthreads();                                         // (a later window wins where two overlap)
+        pb.overlay(wave, k);
+    }
+}
+
+// Splice: one wave lays out each spliced chunk (old streams of untouched blocks, new streams of re-encoded ones); then one workgroup
+// per block copies the streams into place.
+extern "C" __global__ __launch_bounds__(64) void cimg_update_layout(SpliceArgs a)
+{
+    SpliceLayout sl(a, (int)blockIdx.x);
+    sl.run();
+}
+
+extern "C" __global__ __launch_bounds__(256) void cimg_update_emit(SpliceArgs a)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    SpliceEmit se(a, (int)blockIdx.x);
+    se.run(wave);
+}
+
 // ====================================================================================================
 //  engine
 // ====================================================================================================
@@ -332,7 +364,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12)
+    int max_dyn_lds[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -370,6 +402,10 @@ struct cimg_engine {
     DevBuf win_items, win_descs, win_whole, win_out;
     PinBuf h_win_items, h_win_descs, h_win_st;
     WindowStats win_stats;
+    // window writes (update_plan.h): patched blocks, the launches' tables, the host call's staged sources and new chunks
+    DevBuf upd_patch, upd_units, upd_stage, upd_items, upd_descs, upd_chunks, upd_blocks, upd_layout, upd_src, upd_new;
+    PinBuf h_upd_st, h_upd_hdr;
+    UpdateStats upd_stats;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
     bool claunched = false;               // compress_launch got past the planner and the allocations: h_out holds (or will hold) this batch's sizes
 
@@ -522,6 +558,9 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_ZSTD_SEQ: return "cimg_zstd_seq";
     case CIMG_K_ZSTD_LIT: return "cimg_zstd_lit";
     case CIMG_K_DECODE_WINDOW: return "cimg_decode_window";
+    case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
+    case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
+    case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
     default: return "?";
     }
 }
@@ -593,9 +632,11 @@ void cimg_engine_destroy(cimg_engine* e)
     e->drain_timing();
     for (EventPair& ev : e->free_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
-                    &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots})
+                    &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots,
+                    &e->upd_patch, &e->upd_units, &e->upd_stage, &e->upd_items, &e->upd_descs, &e->upd_chunks, &e->upd_blocks, &e->upd_layout,
+                    &e->upd_src, &e->upd_new})
         if (b->p) (void)hipFree(b->p);
-    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst})
+    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr})
         if (b->p) (void)hipHostFree(b->p);
     (void)hipStreamDestroy(e->stream);
     if (e->s_h2d) { (void)hipStreamSynchronize(e->s_h2d); (void)hipStreamDestroy(e->s_h2d); }
@@ -780,6 +821,8 @@ static int compress_launch_wide(cimg_engine* e, EncodePlan& plan, int32_t nchunk
 // inputs_behind_stream: the pixels are produced by work already enqueued on e->stream (a copy the stream waits for, the
 // deinterleave kernel): a launch on another stream has to wait for that too.  The device-resident entry points pass false --
 // their caller's pixels are there when the call is made.
+static int encode_launch(cimg_engine* e, EncodePlan& plan, int32_t nchunks, const void* d_raw, void* d_comp, bool assemble);
+
 static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
                            const void* d_raw, const int64_t* raw_off, const int32_t* nbytes,
                            void* d_comp, const int64_t* comp_off, const int32_t* destsize, bool inputs_behind_stream = true)
@@ -793,6 +836,14 @@ static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
         return compress_launch_wide(e, plan, nchunks, d_raw, d_comp);
     if (rc < 0) return e->fail(rc, "compress batch rejected by the planner (code %d): codec %d / filter pipeline / block size %d not available on the GPU path",
                                rc, p->compcode, p->blocksize);
+    return encode_launch(e, plan, nchunks, d_raw, d_comp, true);
+}
+
+// The encode launches of a planned batch, and with `assemble` the chunks' assembly (inside the launches or behind them).  Window writes
+// run it without assembly over one-block pseudo-chunks (update_plan.h): records and scratch slots are all they need.
+static int encode_launch(cimg_engine* e, EncodePlan& plan, int32_t nchunks, const void* d_raw, void* d_comp, bool assemble)
+{
+    int rc;
     if ((rc = e->reserve(e->recs, sizeof(StreamRec) * (size_t)plan.total_blocks * plan.cp.streams_per_block))) return rc;
     if ((rc = e->reserve(e->layout, sizeof(ChunkLayout) * (size_t)nchunks))) return rc;
     if ((rc = e->reserve(e->h_out, sizeof(ChunkLayout) * ((size_t)nchunks + 1)))) return rc;
@@ -802,7 +853,7 @@ static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     // Chunks whose streams all belong to one encode launch are assembled INSIDE that launch (encode_kernel.h: ChunkDesc::assemble,
     // set by the planner); the two assembly kernels run behind the launches only when a chunk is left for them (memcpyed up front,
     // or full blocks split into planes plus an unsplit leftover block).
-    const bool fold = !e->no_fold;
+    const bool fold = assemble && !e->no_fold;
     bool leftovers = false;                         // some chunk is NOT assembled in a launch
     if (!fold) for (ChunkDesc& d : plan.descs) d.assemble = 0;
     for (const ChunkDesc& d : plan.descs) if (!d.assemble) leftovers = true;
@@ -951,7 +1002,7 @@ static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
         e->qpar[split] ^= 1;                          // the next launch of this kind pops the heads this one zeroes
     }
     if (side && (rc = e->hip(hipStreamWaitEvent(e->stream, e->ev_side_done, 0), "stream wait"))) return rc;
-    if (leftovers) {
+    if (leftovers && assemble) {
         AssembleArgs aa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (const uint8_t*)e->scratch.p,
                         (const StreamRec*)e->recs.p, (uint8_t*)d_comp, (ChunkLayout*)e->layout.p, plan.uniform_nblocks, lay_host, 1};
         if ((rc = e->launch(CIMG_K_LAYOUT, cimg_layout_chunks, aa, nchunks, 64, 0))) return rc;
@@ -2159,6 +2210,292 @@ void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* 
     if (blocks_decoded) *blocks_decoded = e->win_stats.blocks_decoded;
     if (chunks_whole) *chunks_whole = e->win_stats.chunks_whole;
     if (comp_bytes_uploaded) *comp_bytes_uploaded = e->win_stats.comp_bytes_uploaded;
+}
+
+}  // extern "C"
+
+// ---- window writes (update_plan.h, update_kernel.h) --------------------------------------------------
+namespace {
+
+// run_update's device side.  Every step ends in a stream synchronize: the planner reads its results on the host.
+struct EngineUpdateEnv {
+    cimg_engine* e;
+    const cimg_cparams* p;
+    const uint8_t* d_comp;
+    const int64_t* comp_off;
+    const int32_t* comp_size;          // may be null
+    const int32_t* nbytes;
+    const int32_t* blocksize;
+    const uint8_t* d_src;
+    uint8_t* d_new;
+    const uint8_t* h_comp;             // host call: the headers are read here, at h_off
+    const int64_t* h_off;
+
+    int upload(DevBuf& b, const void* src, size_t bytes, const char* what)
+    {
+        int rc;
+        if ((rc = e->reserve(b, bytes + 64))) return rc;
+        return bytes ? e->hip(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream), what) : 0;
+    }
+
+    // the touched chunks' headers: the host call has them in host memory; the device call gathers them into page-locked memory with
+    // one copy per chunk, all on the stream, and waits once
+    int headers(const std::vector<int>& list, uint8_t* out)
+    {
+        if (h_comp) {
+            for (size_t k = 0; k < list.size(); k++) memcpy(out + k * HEADER_LEN, h_comp + h_off[list[k]], HEADER_LEN);
+            return 0;
+        }
+        int rc;
+        const size_t bytes = list.size() * HEADER_LEN;
+        if ((rc = e->reserve(e->h_upd_hdr, bytes))) return rc;
+        uint8_t* h = (uint8_t*)e->h_upd_hdr.p;
+        for (size_t k = 0; k < list.size(); k++)
+            if ((rc = e->hip(hipMemcpyAsync(h + k * HEADER_LEN, d_comp + comp_off[list[k]], HEADER_LEN, hipMemcpyDeviceToHost, e->stream),
+                             "header D2H"))) { (void)cimg_engine_synchronize(e); return rc; }
+        if ((rc = e->hip(hipStreamSynchronize(e->stream), "header D2H"))) return rc;
+        memcpy(out, h, bytes);
+        return 0;
+    }
+
+    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
+    {
+        int rc;
+        if ((rc = e->reserve(e->win_whole, (size_t)total + 64))) return rc;
+        const size_t n = list.size();
+        std::vector<int64_t> co(n);
+        std::vector<int32_t> cs(n), nb(n), bs(n);
+        for (size_t k = 0; k < n; k++) {
+            const int i = list[k];
+            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
+        }
+        rc = cimg_decompress_batch_device_sized(e, (int32_t)n, d_comp, co.data(), cs.data(), nb.data(), bs.data(), e->win_whole.p,
+                                                dst_off.data(), st);
+        if (rc < 0) {
+            bool any = false;
+            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
+            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
+        }
+        return 0;
+    }
+
+    int patch(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<WindowItem>& stage,
+              const std::vector<WindowItem>& items, int to_whole, int64_t patch_bytes, int32_t* status)
+    {
+        int rc;
+        const int nchunks = (int)descs.size();
+        if (!to_whole && (rc = e->reserve(e->upd_patch, (size_t)patch_bytes + 64))) return rc;
+        if ((rc = upload(e->upd_descs, descs.data(), descs.size() * sizeof(ChunkDesc), "update descs H2D"))) return rc;
+        if ((rc = upload(e->upd_units, units.data(), units.size() * sizeof(PatchUnit), "update units H2D"))) return rc;
+        if ((rc = upload(e->upd_stage, stage.data(), stage.size() * sizeof(WindowItem), "update items H2D"))) return rc;
+        if ((rc = upload(e->upd_items, items.data(), items.size() * sizeof(WindowItem), "update items H2D"))) return rc;
+        if ((rc = e->reserve(e->h_upd_st, (size_t)nchunks * 4))) return rc;
+        memset(e->h_upd_st.p, 0, (size_t)nchunks * 4);
+        int32_t* d_st = nullptr;
+        if ((rc = e->device_alias(e->h_upd_st, &d_st))) return rc;
+        PatchArgs pa{};
+        pa.w.d = DecodeArgs{(const ChunkDesc*)e->upd_descs.p, nchunks, d_comp, nullptr, d_st, lds_bytes, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0};
+        pa.w.items = (const WindowItem*)e->upd_stage.p;
+        pa.w.nitems = (int32_t)stage.size();
+        pa.units = (const PatchUnit*)e->upd_units.p;
+        pa.items = (const WindowItem*)e->upd_items.p;
+        pa.src = d_src;
+        pa.dst = (uint8_t*)(to_whole ? e->win_whole.p : e->upd_patch.p);
+        pa.nunits = (int32_t)units.size();
+        if ((rc = e->allow_lds(cimg_update_patch, 13, lds_bytes))) return rc;
+        rc = e->launch(CIMG_K_UPDATE_PATCH, cimg_update_patch, pa, (int)units.size(), 256, lds_bytes);
+        const int src = cimg_engine_synchronize(e);
+        if (rc || src) return rc ? rc : src;
+        const int32_t* hs = (const int32_t*)e->h_upd_st.p;
+        for (int i = 0; i < nchunks; i++) if (hs[i] != 0 && status[i] == 0) status[i] = hs[i];
+        return 0;
+    }
+
+    int encode(const EncodePlan& plan)
+    {
+        EncodePlan ep = plan;
+        e->begin_batch(0);
+        int rc = encode_launch(e, ep, (int32_t)ep.descs.size(), e->upd_patch.p, nullptr, false);
+        const int src = cimg_engine_synchronize(e);
+        return rc ? rc : src;
+    }
+
+    int splice(const CodecParams& cp, const std::vector<SpliceChunk>& chunks, const std::vector<SpliceBlock>& blocks, std::vector<ChunkLayout>& lay)
+    {
+        int rc;
+        if ((rc = upload(e->upd_chunks, chunks.data(), chunks.size() * sizeof(SpliceChunk), "splice chunks H2D"))) return rc;
+        if ((rc = upload(e->upd_blocks, blocks.data(), blocks.size() * sizeof(SpliceBlock), "splice blocks H2D"))) return rc;
+        if ((rc = e->reserve(e->upd_layout, chunks.size() * sizeof(ChunkLayout)))) return rc;
+        SpliceArgs sa{(const SpliceChunk*)e->upd_chunks.p, (int32_t)chunks.size(), (int32_t)blocks.size(), (SpliceBlock*)e->upd_blocks.p, cp,
+                      d_comp, d_new, (const uint8_t*)e->scratch.p, (const StreamRec*)e->recs.p, (ChunkLayout*)e->upd_layout.p};
+        if ((rc = e->launch(CIMG_K_UPDATE_LAYOUT, cimg_update_layout, sa, (int)chunks.size(), 64, 0))) return rc;
+        if ((rc = e->launch(CIMG_K_UPDATE_EMIT, cimg_update_emit, sa, (int)blocks.size(), 256, 0))) return rc;
+        if ((rc = e->hip(hipMemcpyAsync(lay.data(), e->upd_layout.p, lay.size() * sizeof(ChunkLayout), hipMemcpyDeviceToHost, e->stream),
+                         "splice layout D2H"))) return rc;
+        return cimg_engine_synchronize(e);
+    }
+
+    int compress(const HostCParams&, const std::vector<int>&, const std::vector<int64_t>& raw_off, const std::vector<int32_t>& nb,
+                 const std::vector<int32_t>& ds, const std::vector<int64_t>& new_off, int32_t* cbytes)
+    {
+        return cimg_compress_batch_device(e, p, (int32_t)nb.size(), e->win_whole.p, raw_off.data(), nb.data(), d_new, new_off.data(),
+                                          ds.data(), cbytes);
+    }
+};
+
+int update_result(cimg_engine* e, int rc, int32_t nchunks, const int32_t* status)
+{
+    if (rc == ERR_INVALID_PARAM)
+        return e->fail(rc, "invalid update: every window must pass the window checks, every touched chunk's header must agree with the "
+                           "cparams (typesize, codec, filters, split, blocksize) and every destsize must be >= 32");
+    if (rc < 0)
+        for (int i = 0; i < nchunks; i++) if (status[i] == rc) return e->fail(rc, "chunk %d failed to decode (code %d)", i, rc);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                               const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                               int32_t nwindows, const cimg_window* w, const void* d_src, void* d_new, const int64_t* new_off,
+                               int32_t* new_cbytes, int32_t* status)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->upd_stats = UpdateStats{};
+    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (new_cbytes) for (int i = 0; i < nchunks; i++) new_cbytes[i] = 0;
+    if (nwindows == 0) return 0;
+    if (!p || !w || !comp_off || !nbytes || !blocksize || !destsize || !status || !new_cbytes || !new_off || !d_comp || !d_src || !d_new)
+        return e->fail(ERR_INVALID_PARAM, "null argument");
+    (void)hipSetDevice(e->device);
+    e->dflight_open = false;
+    e->cflight_chunks = -1;
+    EngineUpdateEnv env{e, p, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr};
+    UpdateStats st;
+    const int rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
+                              reinterpret_cast<const WindowSpec*>(w), new_off, new_cbytes, status, &st);
+    e->upd_stats = st;
+    return update_result(e, rc, nchunks, status);
+}
+
+int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                             const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
+                             const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->upd_stats = UpdateStats{};
+    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (new_cbytes) for (int i = 0; i < nchunks; i++) new_cbytes[i] = 0;
+    if (new_chunks) for (int i = 0; i < nchunks; i++) new_chunks[i] = nullptr;
+    if (nwindows == 0) return 0;
+    if (!p || !w || !comp_off || !destsize || !status || !new_cbytes || !new_chunks || !h_comp || !h_src || !alloc)
+        return e->fail(ERR_INVALID_PARAM, "null argument");
+    if (nchunks == 0) return e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    (void)hipSetDevice(e->device);
+    e->dflight_open = false;
+    e->cflight_chunks = -1;
+    e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
+    const uint8_t* hc = (const uint8_t*)h_comp;
+    // the headers of the chunks the windows name (the geometry of their planes); the others are not looked at
+    std::vector<uint8_t> named((size_t)nchunks, 0);
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count)
+            return e->fail(ERR_INVALID_PARAM, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
+        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
+    }
+    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), cb((size_t)nchunks, 0);
+    for (int i = 0; i < nchunks; i++) {
+        if (!named[(size_t)i]) continue;
+        if (comp_size && comp_size[i] < HEADER_LEN) { status[i] = ERR_READ_BUFFER; return e->fail(ERR_READ_BUFFER, "chunk %d: %d bytes cannot hold a header", i, comp_size[i]); }
+        const uint8_t* c = hc + comp_off[i];
+        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
+    }
+    const int ts = p->typesize > 255 ? 1 : (p->typesize > 0 ? p->typesize : 1);
+    const std::vector<int32_t> tsv((size_t)nchunks, ts);
+    WindowPlan plan;
+    if (p->typesize <= 0 || plan_windows(nchunks, nb.data(), bs.data(), tsv.data(), nwindows, reinterpret_cast<const WindowSpec*>(w), nullptr, &plan) < 0)
+        return update_result(e, ERR_INVALID_PARAM, nchunks, status);
+    // only the touched chunks go up (a header that claims more than the buffer holds is the chunk's error, found by run_update)
+    std::vector<int64_t> d_comp_off((size_t)nchunks, 0), new_off((size_t)nchunks, 0);
+    std::vector<int32_t> up((size_t)nchunks, 0), held((size_t)nchunks, 0);
+    int64_t comp_total = 0, new_total = 0;
+    for (int i = 0; i < nchunks; i++) {
+        held[(size_t)i] = comp_size ? comp_size[i] : cb[(size_t)i];
+        if (!plan.touched[(size_t)i]) continue;
+        d_comp_off[(size_t)i] = comp_total;
+        up[(size_t)i] = std::max((int32_t)HEADER_LEN, std::min(cb[(size_t)i], held[(size_t)i]));
+        comp_total += ((int64_t)up[(size_t)i] + 63) & ~63ll;
+        new_off[(size_t)i] = new_total;
+        new_total += ((int64_t)std::max(destsize[i], 0) + 63) & ~63ll;
+    }
+    // the windows' rows go up packed (row after row)
+    std::vector<cimg_window> dw(w, w + nwindows);
+    std::vector<int64_t> wbytes((size_t)nwindows, 0);
+    int64_t src_total = 0;
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].width <= 0 || w[k].height <= 0) continue;
+        const int64_t row = (int64_t)w[k].width * ts;
+        dw[(size_t)k].out_off = src_total;
+        dw[(size_t)k].out_pitch = row;
+        wbytes[(size_t)k] = row * w[k].height;
+        src_total += (wbytes[(size_t)k] + 255) & ~255ll;
+    }
+    int rc;
+    if ((rc = e->reserve(e->stage_comp, (size_t)comp_total + 64))) return rc;
+    if ((rc = e->reserve(e->upd_src, (size_t)src_total + 64))) return rc;
+    if ((rc = e->reserve(e->upd_new, (size_t)new_total + 64))) return rc;
+    uint8_t* sc = (uint8_t*)e->stage_comp.p;
+    uint8_t* ss = (uint8_t*)e->upd_src.p;
+    const uint8_t* hs = (const uint8_t*)h_src;
+    {
+        HostPin pin_in(e, h_comp, comp_off, up.data(), nchunks, false);
+        if ((rc = copy_in(e, e->stream, sc, d_comp_off.data(), hc, comp_off, up.data(), 0, nchunks, "chunk H2D"))) return rc;
+        for (int k = 0; k < nwindows; k++) {
+            if (!wbytes[(size_t)k]) continue;
+            const int64_t row = dw[(size_t)k].out_pitch;
+            if (w[k].out_pitch == row || w[k].height == 1)
+                rc = e->hip(hipMemcpyAsync(ss + dw[(size_t)k].out_off, hs + w[k].out_off, (size_t)wbytes[(size_t)k], hipMemcpyHostToDevice, e->stream), "window H2D");
+            else
+                rc = e->hip(hipMemcpy2DAsync(ss + dw[(size_t)k].out_off, (size_t)row, hs + w[k].out_off, (size_t)w[k].out_pitch, (size_t)row,
+                                             (size_t)w[k].height, hipMemcpyHostToDevice, e->stream), "window H2D");
+            if (rc) { (void)cimg_engine_synchronize(e); return rc; }
+        }
+        EngineUpdateEnv env{e, p, sc, d_comp_off.data(), held.data(), nb.data(), bs.data(), ss, (uint8_t*)e->upd_new.p, hc, comp_off};
+        UpdateStats st;
+        rc = run_update(env, to_host(p), nchunks, d_comp_off.data(), held.data(), nb.data(), bs.data(), destsize, nwindows,
+                        reinterpret_cast<const WindowSpec*>(dw.data()), new_off.data(), new_cbytes, status, &st);
+        e->upd_stats = st;
+    }
+    for (int i = 0; i < nchunks; i++) e->upd_stats.bytes_uploaded += up[(size_t)i];
+    for (int k = 0; k < nwindows; k++) e->upd_stats.bytes_uploaded += wbytes[(size_t)k];
+    if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return update_result(e, rc, nchunks, status);
+    const std::string chunk_error = e->err;
+    // the new chunks come back into memory from `alloc`
+    for (int i = 0; i < nchunks; i++) {
+        if (new_cbytes[i] <= 0) continue;
+        void* m = alloc(user, (size_t)new_cbytes[i]);
+        if (!m) { (void)cimg_engine_synchronize(e); return e->fail(-4, "alloc returned NULL for %d bytes", new_cbytes[i]); }
+        new_chunks[i] = m;
+        int crc = e->hip(hipMemcpyAsync(m, (uint8_t*)e->upd_new.p + new_off[(size_t)i], (size_t)new_cbytes[i], hipMemcpyDeviceToHost, e->stream), "chunk D2H");
+        if (crc) { (void)cimg_engine_synchronize(e); return crc; }
+    }
+    int src;
+    if ((src = cimg_engine_synchronize(e))) return src;
+    if (rc) { e->err = chunk_error; return update_result(e, rc, nchunks, status); }
+    return 0;
+}
+
+void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole, int64_t* bytes_uploaded)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    if (blocks_decoded) *blocks_decoded = e->upd_stats.blocks_decoded;
+    if (blocks_encoded) *blocks_encoded = e->upd_stats.blocks_encoded;
+    if (chunks_whole) *chunks_whole = e->upd_stats.chunks_whole;
+    if (bytes_uploaded) *bytes_uploaded = e->upd_stats.bytes_uploaded;
 }
 
 }  // extern "C"

@@ -1,0 +1,332 @@
+// update_kernel.h -- window writes (update_plan.h plans them): the kernels that turn old chunks plus window bytes into the chunks a
+// from-scratch compress of the edited pixels gives.
+//
+//   cimg_update_patch   one 256-thread workgroup per unit.  A unit is one block of a spliced chunk -- staged by
+//                       DecodeBlock::phase_a through WindowBlock exactly as cimg_decode_window stages it, written UNFILTERED to its
+//                       slot of the patch buffer -- or one chunk the batch path decoded whole.  Then the window rows that meet the
+//                       unit are copied over it from the source, one window after the other in call order (a later window wins).  A
+//                       block the windows cover completely is not staged: only the source bytes are copied.
+//   cimg_update_layout  one wave per spliced chunk.  Lane j takes block j: a touched block's size comes from the stream records the
+//                       encode launch left for it; an untouched block's streams are harvested from the old chunk (a negative csize
+//                       word is a run, csize == neblock raw, anything else a coded stream whose payload stays where it is).  A wave
+//                       prefix sum gives the new bstarts; blosc2's running-destsize rule, special-zero and the header are re-applied
+//                       as LayoutChunk applies them.  A chunk that would not fit, or whose running total enters the clipped regime
+//                       at a harvested coded stream (its LZ4 `need` is not known), is handed back to the whole route.
+//   cimg_update_emit    one 256-thread workgroup per block of a spliced chunk: an untouched block is one contiguous copy from the old
+//                       chunk (its csize words and payloads are the bytes a fresh encode writes); a touched block gets its csize
+//                       words and payloads from the encode launch's scratch slot, as EmitBlock writes them.
+//
+// Why splicing is exact: a stream's bytes depend only on the stream, never on the capacity left in the chunk; a clipped budget can only
+// turn "coded" into "does not fit", which makes the whole chunk memcpyed.  So old streams of untouched blocks are what a fresh encode
+// would write, and only the chunk-level rules need re-applying.
+#pragma once
+#include "window_kernel.h"
+#include "assemble_kernel.h"
+
+namespace cimg {
+
+// ---- patch ----------------------------------------------------------------------------------------------------------------------
+struct PatchUnit {
+    int32_t chunk;        // batch chunk (its status word)
+    int32_t stage;        // 1: stage the block first (WindowArgs::items[k] names it); 0: the unit's bytes are there already, or
+                          //    every byte of it comes from the windows
+    int32_t item0, nitems;// overlays of the unit: PatchArgs::items[item0 .. item0 + nitems), in call order (an item's p0 is the
+                          //    unit's first byte in that item's plane)
+    int64_t len;          // bytes of the unit
+    int64_t dst_off;      // the unit's bytes in PatchArgs::dst
+};
+
+struct PatchArgs {
+    WindowArgs w;            // w.d: descs over the batch, status per chunk, lds_bytes; w.items[k]: chunk and block of unit k
+    const PatchUnit* units;
+    const WindowItem* items; // overlays: rows r0 .. r1 of a window (out_off / out_pitch locate the SOURCE rows)
+    const uint8_t* src;      // the windows' bytes
+    uint8_t* dst;            // patch buffer
+    int32_t nunits;
+};
+
+struct PatchBlock {
+    const PatchArgs& a;
+    PatchUnit u;
+    WindowBlock wb;
+
+    CIMG_DEV static PatchUnit uniform_unit(const PatchUnit* p)
+    {
+        PatchUnit t = *p;
+        t.chunk = uni(t.chunk); t.stage = uni(t.stage); t.item0 = uni(t.item0); t.nitems = uni(t.nitems);
+        t.len = uni64(t.len); t.dst_off = uni64(t.dst_off);
+        return t;
+    }
+
+    CIMG_DEV PatchBlock(const PatchArgs& a_, uint8_t* lds, int k) : a(a_), u(uniform_unit(a_.units + k)), wb(a_.w, lds, k) {}
+
+    CIMG_DEV void phase_a(int wave) { if (u.stage) wb.phase_a(wave); }
+
+    // the staged block, unfiltered, into its slot (a block that failed to stage has its status word set and is left alone)
+    CIMG_DEV void phase_base(int wave)
+    {
+        if (!u.stage || wb.mode == 3) return;
+        uint8_t* dst = a.dst + u.dst_off;
+        const int64_t units = u.len >> 2;
+        for (int64_t u0 = wave * 64; u0 < units; u0 += 256) {
+            FOR_LANES(l) {
+                const int64_t q = u0 + l;
+                if (q < units) {
+                    const int64_t k = 4 * q;
+                    const uint32_t v = (uint32_t)wb.byte_at(k) | ((uint32_t)wb.byte_at(k + 1) << 8) |
+                                       ((uint32_t)wb.byte_at(k + 2) << 16) | ((uint32_t)wb.byte_at(k + 3) << 24);
+                    *reinterpret_cast<uint32_t*>(dst + k) = v;
+                }
+            }
+        }
+        if (wave == 0) {
+            FOR_LANES(l) { const int64_t k = 4 * units + l; if (k < u.len) dst[k] = wb.byte_at(k); }
+        }
+    }
+
+    // overlay k of the unit: the rows of one window that meet it
+    CIMG_DEV void overlay(int wave, int k)
+    {
+        const WindowItem it = WindowBlock::uniform_item(a.items + u.item0 + k);
+        const int tid0 = wave * 64;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rs = it.row0 + (int64_t)r * it.rpitch, re = rs + it.wbytes;
+            const int64_t s = rs > it.p0 ? rs : it.p0;
+            const int64_t e = re < it.p0 + u.len ? re : it.p0 + u.len;
+            if (s >= e) continue;
+            const uint8_t* src = a.src + it.out_off + (int64_t)r * it.out_pitch + (s - rs);
+            uint8_t* dst = a.dst + u.dst_off + (s - it.p0);
+            const int64_t n = e - s;
+            // 4-byte units aligned on the destination: whole units are one dword store, the ragged ends go byte by byte
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += 256) {
+                FOR_LANES(l) {
+                    const int64_t q0 = 4 * (u0 + l) - mis;
+                    if (u0 + l < units) {
+                        if (q0 >= 0 && q0 + 4 <= n) {
+                            const uint32_t v = (uint32_t)src[q0] | ((uint32_t)src[q0 + 1] << 8) | ((uint32_t)src[q0 + 2] << 16) |
+                                               ((uint32_t)src[q0 + 3] << 24);
+                            *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                        } else {
+                            for (int i = 0; i < 4; i++) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) dst[q] = src[q];
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// ---- splice ---------------------------------------------------------------------------------------------------------------------
+enum : int { SPLICE_REGULAR = 0, SPLICE_ZERO = 2, SPLICE_WHOLE = 4, SPLICE_DAMAGED = 5 };
+
+struct SpliceChunk {
+    int64_t old_off;      // the old chunk at old_comp + old_off
+    int64_t new_off;      // its new form at new_comp + new_off
+    int32_t old_cbytes;   // bytes of the old chunk (its header's cbytes, checked against what the buffer holds)
+    int32_t destsize;     // capacity of the new chunk (the running-destsize rule)
+    int32_t nbytes, blocksize, nblocks, leftover;
+    int32_t split;        // 1: full blocks are cut into typesize streams
+    int32_t flags;        // header flags byte of the new chunk
+    int32_t blk0;         // its first entry in SpliceArgs::blocks
+    int32_t nstreams;     // streams of the chunk
+};
+
+struct SpliceBlock {
+    int32_t chunk;        // SpliceArgs::chunks index
+    int32_t j;            // block of the chunk
+    int32_t unit;         // >= 0: re-encoded (its records and slot are those of encode-plan block `unit`); -1: harvested
+    int32_t new_pos;      // layout: where the block starts in the new chunk
+    int32_t old_pos;      // layout: where it starts in the old chunk
+    int32_t len;          // layout: its bytes (csize words and payloads)
+};
+
+struct SpliceArgs {
+    const SpliceChunk* chunks;
+    int32_t nchunks;
+    int32_t nblocks;
+    SpliceBlock* blocks;
+    CodecParams p;            // the encode plan's
+    const uint8_t* old_comp;
+    uint8_t* new_comp;
+    const uint8_t* scratch;   // payloads of re-encoded streams: block `unit`'s slot, stream s at s * neblock
+    const StreamRec* recs;
+    ChunkLayout* layout;      // per chunk: cbytes (SPLICE_DAMAGED: the error code) and mode (SPLICE_*)
+};
+
+CIMG_DEV SpliceChunk uniform_splice_chunk(const SpliceChunk* p)
+{
+    SpliceChunk c = *p;
+    c.old_off = uni64(c.old_off); c.new_off = uni64(c.new_off);
+    c.old_cbytes = uni(c.old_cbytes); c.destsize = uni(c.destsize); c.nbytes = uni(c.nbytes); c.blocksize = uni(c.blocksize);
+    c.nblocks = uni(c.nblocks); c.leftover = uni(c.leftover); c.split = uni(c.split); c.flags = uni(c.flags); c.blk0 = uni(c.blk0);
+    c.nstreams = uni(c.nstreams);
+    return c;
+}
+
+struct SpliceLayout {
+    const SpliceArgs& a;
+    int chunk;
+    CIMG_DEV SpliceLayout(const SpliceArgs& a_, int chunk_) : a(a_), chunk(chunk_) {}
+
+    // stream s of lane's block: csize word (harvested) or record (re-encoded) -> payload bytes, and whether the block is damaged
+    CIMG_DEV void run()
+    {
+        const SpliceChunk d = uniform_splice_chunk(a.chunks + chunk);
+        const uint8_t* o = a.old_comp + d.old_off;
+        uint8_t* c = a.new_comp + d.new_off;
+        const int ts = a.p.typesize;
+        int nt = HEADER_LEN + 4 * d.nblocks;
+        int mode = SPLICE_REGULAR, code = 0;
+        if (nt > d.destsize) mode = SPLICE_WHOLE;
+        if (d.old_cbytes < nt) { mode = SPLICE_DAMAGED; code = ERR_READ_BUFFER; }
+        for (int j0 = 0; j0 < d.nblocks && mode == SPLICE_REGULAR; j0 += 64) {
+            LV<int> sz, pre, opos, unit;
+            LV<bool> bad, hand;
+            FOR_LANES(l) {
+                const int j = j0 + l;
+                sz[l] = 0; opos[l] = 0; unit[l] = -1; bad[l] = false; hand[l] = false;
+                if (j < d.nblocks) {
+                    const SpliceBlock& sb = a.blocks[d.blk0 + j];
+                    const bool lb = j == d.nblocks - 1 && d.leftover;
+                    const int bsize = lb ? d.leftover : d.blocksize;
+                    const int ns = (d.split && !lb) ? ts : 1;
+                    const int neblock = bsize / ns;
+                    unit[l] = sb.unit;
+                    if (sb.unit >= 0) {
+                        for (int s = 0; s < ns; s++) sz[l] += 4 + rec_payload(a.recs[(int64_t)sb.unit * a.p.streams_per_block + s]);
+                    } else {
+                        const int b0 = ld32s(o + HEADER_LEN + 4 * j);
+                        opos[l] = b0;
+                        if (b0 < HEADER_LEN + 4 * d.nblocks || b0 > d.old_cbytes) { bad[l] = true; }
+                        else {
+                            int pos = b0;
+                            for (int s = 0; s < ns; s++) {
+                                if (d.old_cbytes - pos < 4) { bad[l] = true; break; }
+                                const int cs = ld32s(o + pos);
+                                pos += 4;
+                                const int payload = cs > 0 ? cs : (cs < 0 ? 1 : 0);
+                                if (cs > neblock || cs < -255 || payload > d.old_cbytes - pos) { bad[l] = true; break; }
+                                pos += payload;
+                            }
+                            sz[l] = pos - b0;
+                        }
+                    }
+                }
+            }
+            if (ballot(bad)) { mode = SPLICE_DAMAGED; code = ERR_DATA; break; }
+            int tile_total;
+            wave_exscan(sz, pre, tile_total);
+            FOR_LANES(l) {
+                const int j = j0 + l;
+                if (j < d.nblocks) {
+                    SpliceBlock& sb = a.blocks[d.blk0 + j];
+                    const bool lb = j == d.nblocks - 1 && d.leftover;
+                    const int bsize = lb ? d.leftover : d.blocksize;
+                    const int ns = (d.split && !lb) ? ts : 1;
+                    const int neblock = bsize / ns;
+                    sb.new_pos = nt + pre[l]; sb.old_pos = opos[l]; sb.len = sz[l];
+                    st32(c + HEADER_LEN + 4 * j, nt + pre[l]);
+                    // LayoutChunk's running-destsize rule, stream by stream
+                    int pos = nt + pre[l], hp = opos[l];
+                    bool f = false;
+                    for (int s = 0; s < ns; s++) {
+                        const int N = pos + 4;
+                        int kind, value, csize, need = 0;
+                        bool known = true;
+                        if (unit[l] >= 0) {
+                            const StreamRec r = a.recs[(int64_t)unit[l] * a.p.streams_per_block + s];
+                            kind = r.kind; value = r.value; csize = r.csize; need = r.need;
+                        } else {
+                            const int cs = ld32s(o + hp);
+                            kind = cs <= 0 ? REC_RUN : cs == neblock ? REC_RAW : REC_LZ4;
+                            value = cs < 0 ? -cs : 0; csize = cs > 0 ? cs : 0;
+                            known = kind != REC_LZ4;
+                            hp += 4 + (cs > 0 ? cs : (cs < 0 ? 1 : 0));
+                        }
+                        if (kind == REC_RUN) {
+                            f |= N > d.destsize || (value > 0 && N + 1 > d.destsize);
+                            pos += 4 + (value > 0 ? 1 : 0);
+                        } else {
+                            int maxout = neblock;
+                            if (N + maxout > d.destsize) {
+                                if (!known) hand[l] = true;
+                                maxout = d.destsize - N;
+                                if (maxout <= 0) f = true;
+                            }
+                            if (!f && known) {
+                                if (kind == REC_LZ4) { if (need > maxout) f = true; }
+                                else if (N + neblock > d.destsize) f = true;
+                            }
+                            pos += 4 + csize;
+                        }
+                    }
+                    hand[l] = hand[l] || f;
+                }
+            }
+            if (ballot(hand)) mode = SPLICE_WHOLE;
+            nt += tile_total;
+        }
+        int cbytes = 0;
+        if (mode == SPLICE_REGULAR) {
+            AssembleArgs aa{};
+            aa.p = a.p;
+            LayoutChunk lc(aa, 0);
+            ChunkDesc hd{};
+            hd.nbytes = d.nbytes; hd.blocksize = d.blocksize;
+            if (nt == HEADER_LEN + 4 * d.nblocks + 4 * d.nstreams) {
+                mode = SPLICE_ZERO; cbytes = HEADER_LEN;
+                lc.write_header(hd, c, d.flags, HEADER_LEN, SPECIAL_ZERO << 4);
+            } else {
+                cbytes = nt;
+                lc.write_header(hd, c, d.flags, nt, 0);
+            }
+        }
+        if (mode == SPLICE_DAMAGED) cbytes = code;
+        FOR_LANES_W(l) { if (l == 0) { a.layout[chunk].cbytes = cbytes; a.layout[chunk].mode = mode; } }
+    }
+};
+
+struct SpliceEmit {
+    const SpliceArgs& a;
+    int k;
+    CIMG_DEV SpliceEmit(const SpliceArgs& a_, int k_) : a(a_), k(k_) {}
+
+    CIMG_DEV void run(int wave, int nwaves = 4)
+    {
+        const SpliceBlock* bp = a.blocks + k;
+        const int chunk = uni(bp->chunk), j = uni(bp->j), unit = uni(bp->unit);
+        const int new_pos = uni(bp->new_pos), old_pos = uni(bp->old_pos), len = uni(bp->len);
+        if (uni(a.layout[chunk].mode) != SPLICE_REGULAR) return;
+        const SpliceChunk d = uniform_splice_chunk(a.chunks + chunk);
+        uint8_t* c = a.new_comp + d.new_off;
+        if (unit < 0) { wave_copy_g2g(a.old_comp + d.old_off + old_pos, c + new_pos, len, wave, nwaves); return; }
+        const bool lb = j == d.nblocks - 1 && d.leftover;
+        const int bsize = lb ? d.leftover : d.blocksize;
+        const int ns = (d.split && !lb) ? a.p.typesize : 1;
+        const int neblock = bsize / ns;
+        const uint8_t* slot = a.scratch + (int64_t)unit * a.p.slot_bytes;
+        const StreamRec* rp = a.recs + (int64_t)unit * a.p.streams_per_block;
+        int pos = new_pos;
+        for (int s = 0; s < ns; s++) {
+            StreamRec r;
+            r.kind = uni(rp[s].kind); r.value = uni(rp[s].value); r.csize = uni(rp[s].csize); r.need = 0;
+            if (wave == 0) {
+                const int word = r.kind == REC_RUN ? -r.value : r.csize;
+                FOR_LANES(l) {
+                    if (l < 4) c[pos + l] = (uint8_t)(((uint32_t)word >> (8 * l)) & 0xFF);
+                    if (l == 4 && r.kind == REC_RUN && r.value > 0) c[pos + 4] = 0x01;
+                }
+            }
+            pos += 4;
+            if (r.kind != REC_RUN) wave_copy_g2g(slot + (int64_t)s * neblock, c + pos, r.csize, wave, nwaves);
+            pos += rec_payload(r);
+        }
+    }
+};
+
+}  // namespace cimg

@@ -1,0 +1,269 @@
+// update_plan.h -- window writes: validation, routing and the order in which an update call runs.  Pure C++, shared by the engine
+// (engine.hip) and the emulator tests (tests/emu/window_write_emu.cpp, tests/emu/mock_window_write.cpp), like window_plan.h.
+//
+// Windows are cimg_window / WindowSpec, with out_off / out_pitch locating the SOURCE rows.  Every touched chunk's new bytes are what a
+// from-scratch compress of its decoded pixels with the windows written in gives.  Two routes:
+//   splice  regular lz4 / lz4hc / blosclz chunks whose blocks the window kernel can stage and the batch encoder can take: the touched
+//           blocks are staged and patched (cimg_update_patch), re-encoded as one-block pseudo-chunks (the batch encode launch, no
+//           assembly behind it), and spliced with the old streams of the untouched blocks (cimg_update_layout + cimg_update_emit).
+//   whole   everything else (zstd, wide blocks, memcpyed or special-zero chunks, a chunk whose new form clipped at an old coded stream
+//           or fell back to memcpyed): decoded whole through the batch path, patched in place, compressed through the batch path.
+#pragma once
+#include "plan.h"
+#include "window_plan.h"
+#include "update_kernel.h"
+#include <algorithm>
+#include <cstring>
+
+namespace cimg {
+
+struct UpdateStats {
+    int64_t blocks_decoded = 0, blocks_encoded = 0, chunks_whole = 0, bytes_uploaded = 0;
+};
+
+enum : int { ROUTE_NONE = 0, ROUTE_SPLICE = 1, ROUTE_WHOLE = 2, ROUTE_FAILED = 3 };
+
+// true: the rows of items[first .. first + count) cover all `len` bytes of their unit (each item's p0 is the unit's first byte in
+// that item's plane)
+inline bool items_cover(const std::vector<WindowItem>& items, size_t first, size_t count, int64_t len)
+{
+    int64_t written = 0;
+    for (size_t k = first; k < first + count; k++) written += (int64_t)(items[k].r1 - items[k].r0) * items[k].wbytes;
+    if (written < len) return false;
+    std::vector<std::pair<int64_t, int64_t>> iv;
+    for (size_t k = first; k < first + count; k++) {
+        const WindowItem& t = items[k];
+        for (int r = t.r0; r < t.r1; r++) {
+            const int64_t rs = t.row0 + (int64_t)r * t.rpitch - t.p0;
+            const int64_t s = std::max<int64_t>(rs, 0), e = std::min(rs + t.wbytes, len);
+            if (s < e) iv.push_back({s, e});
+        }
+    }
+    std::sort(iv.begin(), iv.end());
+    int64_t reach = 0;
+    for (const auto& x : iv) {
+        if (x.first > reach) return false;
+        reach = std::max(reach, x.second);
+    }
+    return reach >= len;
+}
+
+// Env provides (each step waited for before it returns; < 0 only when the device itself failed):
+//   int headers(list, out)                                 -- the first 32 bytes of every listed chunk, back to back (ONE round trip)
+//   int decode_whole(list, dst_off, total, st)             -- the batch path into the env's whole buffer (st per listed chunk)
+//   int patch(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
+//                                                          -- cimg_update_patch into the patch buffer (to_whole 0, patch_bytes long)
+//                                                             or into the whole buffer (1); a chunk's status word is set on failure
+//   int encode(const EncodePlan&)                          -- the batch encode launch over the patch buffer, records + slots left
+//   int splice(cp, chunks, blocks, layout)                 -- cimg_update_layout + cimg_update_emit, layout back on the host
+//   int compress(p, list, raw_off, nbytes, destsize, new_off, cbytes)
+//                                                          -- the batch compress of chunks lying in the whole buffer
+template <class Env>
+int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
+               const int32_t* blocksize, const int32_t* destsize, int nwindows, const WindowSpec* w, const int64_t* new_off,
+               int32_t* new_cbytes, int32_t* status, UpdateStats* stats)
+{
+    *stats = UpdateStats{};
+    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
+    for (int i = 0; i < nchunks; i++) { status[i] = 0; new_cbytes[i] = 0; }
+    if (nwindows == 0) return 0;
+    if (nchunks == 0 || p.typesize <= 0) return ERR_INVALID_PARAM;
+    int filter = 0;
+    if (single_filter(p, &filter) < 0) return ERR_INVALID_PARAM;
+    const int ts = p.typesize > 255 ? 1 : p.typesize;
+    for (int i = 0; i < nchunks; i++) if (destsize[i] < HEADER_LEN) return ERR_INVALID_PARAM;
+    const std::vector<int32_t> tsv((size_t)nchunks, ts);
+    WindowPlan plan;
+    if (plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, nullptr, &plan) < 0) return ERR_INVALID_PARAM;
+
+    // the touched chunks' headers: damage is the chunk's status, disagreement with p the call's error
+    std::vector<uint8_t> route((size_t)nchunks, ROUTE_NONE);
+    std::vector<ChunkDesc> nd((size_t)nchunks);
+    std::vector<int32_t> old_cbytes((size_t)nchunks, 0);
+    std::vector<int> tl;
+    for (int i = 0; i < nchunks; i++) if (plan.touched[(size_t)i]) tl.push_back(i);
+    std::vector<uint8_t> hdrs(tl.size() * HEADER_LEN);
+    if (!tl.empty()) {
+        const int rc = env.headers(tl, hdrs.data());
+        if (rc < 0) return rc;
+    }
+    for (size_t t = 0; t < tl.size(); t++) {
+        const int i = tl[t];
+        const uint8_t* h = hdrs.data() + t * HEADER_LEN;
+        int32_t hnb, hbs, hcb;
+        memcpy(&hnb, h + OFF_NBYTES, 4); memcpy(&hbs, h + OFF_BLOCKSIZE, 4); memcpy(&hcb, h + OFF_CBYTES, 4);
+        int code = 0;
+        if (h[0] > 5) code = ERR_VERSION_SUPPORT;
+        else if (hcb < HEADER_LEN) code = ERR_INVALID_HEADER;
+        else if (comp_size && hcb > comp_size[i]) code = ERR_READ_BUFFER;
+        if (code) { status[i] = code; route[(size_t)i] = ROUTE_FAILED; continue; }
+        ChunkDesc& d = nd[(size_t)i];
+        if (plan_chunk(p, nbytes[i], destsize[i], &d) < 0) return ERR_INVALID_PARAM;
+        const int flags = h[OFF_FLAGS];
+        bool agree = hnb == nbytes[i] && hbs == blocksize[i] && hbs == d.blocksize && h[OFF_TYPESIZE] == ts &&
+                     ((flags ^ d.flags) & ~FLAG_MEMCPYED) == 0 && h[OFF_COMPCODE] == p.compcode && h[OFF_FILTERS + 5] == filter;
+        for (int k = 0; k < 5; k++) agree = agree && h[OFF_FILTERS + k] == 0;
+        if (!agree) return ERR_INVALID_PARAM;
+        old_cbytes[(size_t)i] = hcb;
+        const int fmt = flags >> 5, special = (h[OFF_BLOSC2_FLAGS] >> 4) & 7;
+        bool splice = !(flags & FLAG_MEMCPYED) && special == 0 && (fmt == 0 || fmt == 1) && !d.memcpyed && !decode_is_wide(hbs);
+        if (splice) {
+            EncodePlan ep;
+            const int64_t zero = 0;
+            splice = plan_encode_batch(p, 1, &zero, &nbytes[i], &zero, &destsize[i], &ep) == 0;
+        }
+        route[(size_t)i] = splice ? ROUTE_SPLICE : ROUTE_WHOLE;
+    }
+
+    // ---- splice route ----
+    std::vector<uint8_t> hint((size_t)nchunks, 0);
+    for (int i = 0; i < nchunks; i++) hint[(size_t)i] = route[(size_t)i] != ROUTE_SPLICE;
+    if (plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, hint.data(), &plan) < 0) return ERR_INVALID_PARAM;
+    for (int i = 0; i < nchunks; i++) {
+        plan.descs[(size_t)i].comp_off = plan.touched[(size_t)i] ? comp_off[i] : 0;
+        plan.descs[(size_t)i].destsize = comp_size ? comp_size[i] : 0x7fffffff;
+    }
+    std::vector<WindowItem> blk_items;
+    for (const WindowItem& t : plan.items) if (t.b >= 0 && route[(size_t)t.chunk] == ROUTE_SPLICE) blk_items.push_back(t);
+    std::stable_sort(blk_items.begin(), blk_items.end(), [](const WindowItem& x, const WindowItem& y) { return x.b < y.b; });
+    std::vector<PatchUnit> units;
+    std::vector<WindowItem> stage;
+    std::vector<int32_t> unit_b;
+    int64_t patch_bytes = 0;
+    for (size_t k = 0; k < blk_items.size();) {
+        size_t e = k;
+        while (e < blk_items.size() && blk_items[e].b == blk_items[k].b) e++;
+        const WindowItem& t = blk_items[k];
+        const ChunkDesc& d = plan.descs[(size_t)t.chunk];
+        const int j = t.b - d.blk0;
+        const int64_t blen = (j == d.nblocks - 1 && d.leftover) ? d.leftover : d.blocksize;
+        PatchUnit u{};
+        u.chunk = t.chunk;
+        u.stage = items_cover(blk_items, k, e - k, blen) ? 0 : 1;
+        u.item0 = (int32_t)k; u.nitems = (int32_t)(e - k);
+        u.len = blen; u.dst_off = patch_bytes;
+        patch_bytes += (blen + 63) & ~(int64_t)63;
+        WindowItem s{};
+        s.chunk = t.chunk; s.b = u.stage ? t.b : -1;
+        units.push_back(u); stage.push_back(s); unit_b.push_back(t.b);
+        k = e;
+    }
+    if (!units.empty()) {
+        int rc = env.patch(plan.descs, plan.lds_bytes, units, stage, blk_items, 0, patch_bytes, status);
+        if (rc < 0) return rc;
+        for (int i = 0; i < nchunks; i++) if (route[(size_t)i] == ROUTE_SPLICE && status[i] != 0) route[(size_t)i] = ROUTE_FAILED;
+        // one-block pseudo-chunks with the parent's geometry (a short last block stays unsplit), no assembly
+        std::vector<int> sl;
+        std::vector<int64_t> zoff;
+        std::vector<int32_t> snb, sds;
+        for (int i = 0; i < nchunks; i++)
+            if (route[(size_t)i] == ROUTE_SPLICE) { sl.push_back(i); snb.push_back(nbytes[i]); sds.push_back(destsize[i]); zoff.push_back(0); }
+        EncodePlan ep;
+        std::vector<int32_t> enc_of(units.size(), -1);
+        if (!sl.empty()) {
+            if (plan_encode_batch(p, (int)sl.size(), zoff.data(), snb.data(), zoff.data(), sds.data(), &ep) < 0) return ERR_INVALID_PARAM;
+            std::vector<ChunkDesc> pd;
+            ep.lds_split = ep.lds_unsplit = 0;
+            for (size_t k = 0; k < units.size(); k++) {
+                const PatchUnit& u = units[k];
+                if (route[(size_t)u.chunk] != ROUTE_SPLICE) continue;
+                const ChunkDesc& par = nd[(size_t)u.chunk];
+                ChunkDesc q{};
+                q.raw_off = u.dst_off; q.comp_off = 0; q.nbytes = (int32_t)u.len; q.destsize = (int32_t)u.len + HEADER_LEN + 4 * MAX_STREAMS + 64;
+                q.blocksize = par.blocksize; q.nblocks = 1; q.leftover = u.len != par.blocksize ? (int32_t)u.len : 0;
+                q.blk0 = (int32_t)pd.size(); q.flags = par.flags; q.split = par.split; q.memcpyed = 0;
+                q.nstreams = (q.split && !q.leftover) ? ep.cp.typesize : 1;
+                q.assemble = 0;
+                const bool multi = q.split && ep.cp.typesize > 1;
+                if (q.leftover) ep.lds_unsplit = imax(ep.lds_unsplit, encode_lds_bytes(q.leftover, p.compcode));
+                else if (multi) ep.lds_split = imax(ep.lds_split, encode_lds_bytes(q.blocksize / ep.cp.typesize, p.compcode));
+                else ep.lds_unsplit = imax(ep.lds_unsplit, encode_lds_bytes(q.blocksize, p.compcode));
+                enc_of[k] = (int32_t)pd.size();
+                pd.push_back(q);
+            }
+            ep.descs = pd;
+            ep.total_blocks = (int32_t)pd.size();
+            ep.uniform_nblocks = 1;
+            if (!pd.empty() && (rc = env.encode(ep)) < 0) return rc;
+            stats->blocks_encoded = (int64_t)pd.size();
+            for (size_t k = 0; k < units.size(); k++) if (enc_of[k] >= 0 && units[k].stage) stats->blocks_decoded++;
+            // the splice tables
+            std::vector<SpliceChunk> sc;
+            std::vector<SpliceBlock> sb;
+            for (int i : sl) {
+                const ChunkDesc& d = nd[(size_t)i];
+                SpliceChunk c{};
+                c.old_off = comp_off[i]; c.new_off = new_off[i]; c.old_cbytes = old_cbytes[(size_t)i]; c.destsize = destsize[i];
+                c.nbytes = d.nbytes; c.blocksize = d.blocksize; c.nblocks = d.nblocks; c.leftover = d.leftover;
+                c.split = d.split; c.flags = d.flags; c.blk0 = (int32_t)sb.size(); c.nstreams = d.nstreams;
+                for (int j = 0; j < d.nblocks; j++) sb.push_back(SpliceBlock{(int32_t)sc.size(), j, -1, 0, 0, 0});
+                sc.push_back(c);
+            }
+            std::vector<int32_t> sc_of((size_t)nchunks, -1);
+            for (size_t k = 0; k < sl.size(); k++) sc_of[(size_t)sl[k]] = (int32_t)k;
+            for (size_t k = 0; k < units.size(); k++) {
+                if (enc_of[k] < 0) continue;
+                const int i = units[k].chunk;
+                const int j = unit_b[k] - plan.descs[(size_t)i].blk0;
+                sb[(size_t)(sc[(size_t)sc_of[(size_t)i]].blk0 + j)].unit = enc_of[k];
+            }
+            std::vector<ChunkLayout> lay(sc.size());
+            if ((rc = env.splice(ep.cp, sc, sb, lay)) < 0) return rc;
+            for (size_t k = 0; k < sl.size(); k++) {
+                const int i = sl[k];
+                const ChunkLayout& L = lay[k];
+                if (L.mode == SPLICE_REGULAR || L.mode == SPLICE_ZERO) new_cbytes[i] = L.cbytes;
+                else if (L.mode == SPLICE_WHOLE) route[(size_t)i] = ROUTE_WHOLE;
+                else { status[i] = L.cbytes < 0 ? L.cbytes : ERR_DATA; route[(size_t)i] = ROUTE_FAILED; }
+            }
+        }
+    }
+
+    // ---- whole route (and the splice route's hand-backs) ----
+    std::vector<int> wl;
+    std::vector<int64_t> woff;
+    int64_t wtotal = 0;
+    for (int i = 0; i < nchunks; i++)
+        if (route[(size_t)i] == ROUTE_WHOLE) { wl.push_back(i); woff.push_back(wtotal); wtotal += ((int64_t)nbytes[i] + 255) & ~(int64_t)255; }
+    if (!wl.empty()) {
+        std::vector<int32_t> st(wl.size(), 0);
+        int rc = env.decode_whole(wl, woff, wtotal, st.data());
+        if (rc < 0) return rc;
+        stats->chunks_whole = (int64_t)wl.size();
+        for (int i = 0; i < nchunks; i++) hint[(size_t)i] = route[(size_t)i] == ROUTE_WHOLE;
+        if (plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, hint.data(), &plan) < 0) return ERR_INVALID_PARAM;
+        std::vector<int64_t> at((size_t)nchunks, -1);
+        std::vector<int> ok;
+        std::vector<int64_t> okoff;
+        for (size_t k = 0; k < wl.size(); k++) {
+            if (st[k] != 0) { status[wl[k]] = st[k]; route[(size_t)wl[k]] = ROUTE_FAILED; continue; }
+            at[(size_t)wl[k]] = woff[k];
+            ok.push_back(wl[k]); okoff.push_back(woff[k]);
+        }
+        std::vector<WindowItem> items;
+        std::vector<PatchUnit> wunits;
+        std::vector<WindowItem> wstage;
+        for (int i : ok) {
+            PatchUnit u{};
+            u.chunk = i; u.stage = 0; u.item0 = (int32_t)items.size();
+            u.len = nbytes[i]; u.dst_off = at[(size_t)i];
+            for (const WindowItem& t : plan.items) if (t.b < 0 && t.chunk == i) items.push_back(t);
+            u.nitems = (int32_t)items.size() - u.item0;
+            WindowItem s{};
+            s.chunk = i; s.b = -1;
+            wunits.push_back(u); wstage.push_back(s);
+        }
+        if (!ok.empty()) {
+            if ((rc = env.patch(plan.descs, 0, wunits, wstage, items, 1, wtotal, status)) < 0) return rc;
+            std::vector<int32_t> nb, ds, cb(ok.size(), 0);
+            std::vector<int64_t> no;
+            for (int i : ok) { nb.push_back(nbytes[i]); ds.push_back(destsize[i]); no.push_back(new_off[i]); }
+            if ((rc = env.compress(p, ok, okoff, nb, ds, no, cb.data())) < 0) return rc;
+            for (size_t k = 0; k < ok.size(); k++) new_cbytes[ok[k]] = cb[k];
+        }
+    }
+    for (int i = 0; i < nchunks; i++) if (status[i] != 0) return status[i];
+    return 0;
+}
+
+}  // namespace cimg

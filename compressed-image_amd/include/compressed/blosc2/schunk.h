@@ -201,6 +201,108 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					}
 				}
 
+				/// What set_region changes in a table: the compressed chunks it queued (job index -> chunk index) and the lazy chunks
+				/// the rectangle meets, filled and patched on the host.
+				struct region_write
+				{
+					size_t job_first = 0;
+					std::vector<size_t> compressed;
+					std::vector<size_t> lazy;
+					std::vector<std::vector<T>> lazy_pixels;
+					std::vector<byte_buffer> new_bytes;              // prepare_region_write: the compressed chunks' new forms (empty: unchanged)
+					std::vector<byte_buffer> lazy_bytes;             // ... and the lazy chunks' compressed forms
+				};
+
+				/// Batch building block of set_region: the rectangle (x, y, w, h) of this table seen as rows of `row_len` elements is
+				/// taken from `src` (w elements a row, rows `src_pitch` elements apart).  Runs of compressed chunks become windows of
+				/// `job` as in plan_region; a lazy chunk the rectangle meets is filled with its value and the rectangle's part written in.
+				void plan_region_write(const T* src, size_t src_pitch, size_t row_len, size_t x, size_t y, size_t w, size_t h,
+					batch::update_job& job, region_write& rw) const
+				{
+					rw.job_first = job.chunks.size();
+					if (w == 0 || h == 0) return;
+					auto row_start = [&](size_t r) { return (y + r) * row_len + x; };
+					size_t cs = 0;
+					for (size_t i = 0; i < m_Chunks.size();)
+					{
+						const bool lazy = m_Chunks[i].is_lazy();
+						size_t j = i, ce = cs;
+						while (j < m_Chunks.size() && m_Chunks[j].is_lazy() == lazy) { ce += m_Chunks[j].num_elements; ++j; if (lazy) break; }
+						const size_t r0 = row_start(0) + w > cs ? 0 : (cs - row_start(0) - w) / row_len + 1;
+						size_t r1 = h;
+						if (row_start(0) >= ce) r1 = 0;
+						else if (row_start(h - 1) >= ce) r1 = (ce - row_start(0) + row_len - 1) / row_len;
+						bool met = false;
+						for (size_t r = r0; r < r1 && !met; ++r) met = std::max(row_start(r), cs) < std::min(row_start(r) + w, ce);
+						if (lazy && met)
+						{
+							std::vector<T> px(m_Chunks[i].num_elements, std::get<T>(m_Chunks[i].value));
+							for (size_t r = r0; r < r1; ++r)
+							{
+								const size_t a = std::max(row_start(r), cs), b = std::min(row_start(r) + w, ce);
+								if (a < b) std::copy(src + r * src_pitch + (a - row_start(r)), src + r * src_pitch + (b - row_start(r)), px.begin() + (a - cs));
+							}
+							rw.lazy.push_back(i);
+							rw.lazy_pixels.push_back(std::move(px));
+						}
+						else if (!lazy && met)
+						{
+							const int32_t first = static_cast<int32_t>(job.chunks.size());
+							for (size_t k = i; k < j; ++k)
+							{
+								job.chunks.push_back(m_Chunks[k].bytes().data());
+								job.held.push_back(m_Chunks[k].bytes().size());
+								job.destsize.push_back(static_cast<int32_t>(min_compressed_size(m_ChunkSize)));
+								rw.compressed.push_back(k);
+							}
+							auto add = [&](size_t ra, size_t rb, bool partial) {
+								if (ra >= rb) return;
+								const size_t a = partial ? std::max(row_start(ra), cs) : row_start(ra);
+								const size_t b = partial ? std::min(row_start(ra) + w, ce) : a + w;
+								cimg_window win{};
+								win.chunk_first = first;
+								win.chunk_count = static_cast<int32_t>(j - i);
+								win.origin = static_cast<int64_t>(a - cs);
+								win.row_pitch = static_cast<int64_t>(row_len);
+								win.width = static_cast<int32_t>(b - a);
+								win.height = static_cast<int32_t>(rb - ra);
+								win.out_pitch = static_cast<int64_t>(src_pitch * sizeof(T));
+								job.windows.push_back(win);
+								job.srcs.push_back(reinterpret_cast<const std::byte*>(src + ra * src_pitch + (a - row_start(ra))));
+							};
+							size_t ra = r0, rb = r1;
+							if (row_start(ra) < cs) { add(ra, ra + 1, true); ++ra; }
+							if (rb > ra && row_start(rb - 1) + w > ce) { --rb; add(rb, rb + 1, true); }
+							add(ra, rb, false);
+						}
+						cs = ce;
+						i = j;
+					}
+				}
+
+				/// After the engine call succeeded: take this table's new chunks out of the call's results and compress the patched lazy
+				/// chunks (one batch call).  May throw; nothing of the table has changed yet.
+				void prepare_region_write(context_raw_ptr cctx, region_write& rw, std::vector<std::vector<std::byte>>& made) const
+				{
+					for (size_t k = 0; k < rw.compressed.size(); ++k)
+					{
+						auto& b = made[rw.job_first + k];
+						rw.new_bytes.push_back(b.empty() ? byte_buffer() : byte_buffer(std::move(b)));
+					}
+					if (rw.lazy.empty()) return;
+					std::vector<batch::piece> pieces;
+					for (const auto& px : rw.lazy_pixels) pieces.push_back({ reinterpret_cast<const std::byte*>(px.data()), px.size() * sizeof(T) });
+					rw.lazy_bytes = batch::compress(cctx, pieces, m_ChunkSize);
+				}
+
+				/// Replace every touched chunk: moves only, so a caller that prepared every table commits them all.
+				void commit_region_write(region_write& rw) noexcept
+				{
+					for (size_t k = 0; k < rw.compressed.size(); ++k)
+						if (rw.new_bytes[k].size() > 0) m_Chunks[rw.compressed[k]].value = std::move(rw.new_bytes[k]);
+					for (size_t k = 0; k < rw.lazy.size(); ++k) m_Chunks[rw.lazy[k]].value = std::move(rw.lazy_bytes[k]);
+				}
+
 				std::vector<T> chunk(context_ptr& ctx, size_t index) const { return chunk(ctx.get(), index); }
 				std::vector<T> chunk(context_raw_ptr ctx, size_t index) const
 				{

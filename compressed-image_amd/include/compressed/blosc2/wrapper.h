@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -363,6 +364,57 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					static_cast<int32_t>(job.windows.size()), job.windows.data(), obase, status.data());
 				if (rc < 0)
 					throw std::runtime_error(detail::text("Error code ", rc, " while decompressing a region of blosc2 chunks (", cimg_last_error(engine()), ")"));
+			}
+
+			// Window writes of several planes in one engine call (cimg_update_windows_host): only the blocks the windows meet are decoded
+			// and re-encoded, and only the touched chunks and the windows' bytes travel.  windows[i] names chunks by their index in
+			// `chunks`; its out_off is filled in here from srcs[i], where its first source element lies.  Every new chunk gets destsize[i]
+			// (what set_chunk passes: min_compressed_size of the nominal chunk size).  Returns the new form of every chunk, empty where
+			// no window row meets it; throws on any error, and the caller's chunks stay as they were.
+			struct update_job
+			{
+				std::vector<const std::byte*> chunks;
+				std::vector<size_t> held;               // bytes each chunk buffer holds
+				std::vector<int32_t> destsize;
+				std::vector<cimg_window> windows;
+				std::vector<const std::byte*> srcs;
+				cimg_cparams cparams{};
+			};
+
+			inline std::vector<std::vector<std::byte>> update_windows(update_job& job)
+			{
+				const size_t n = job.chunks.size();
+				std::vector<std::vector<std::byte>> out(n);
+				if (job.windows.empty()) return out;
+				const std::byte* cbase = job.chunks.empty() ? nullptr : job.chunks[0];
+				for (const auto* c : job.chunks) if (c < cbase) cbase = c;
+				const std::byte* sbase = job.srcs[0];
+				for (const auto* s : job.srcs) if (s < sbase) sbase = s;
+				std::vector<int64_t> comp_off(n);
+				std::vector<int32_t> held(n), status(n), ncb(n);
+				std::vector<void*> made(n, nullptr);
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (job.held[i] > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+						throw std::out_of_range(detail::text("Blosc2 chunk size may not exceed numeric limit of int32_t, got ", job.held[i]));
+					comp_off[i] = job.chunks[i] - cbase;
+					held[i] = static_cast<int32_t>(job.held[i]);
+				}
+				for (size_t k = 0; k < job.windows.size(); ++k) job.windows[k].out_off = job.srcs[k] - sbase;
+				const auto alloc = [](void*, size_t bytes) -> void* { return std::malloc(bytes ? bytes : 1); };
+				const int rc = cimg_update_windows_host(engine(), &job.cparams, static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+					job.destsize.data(), static_cast<int32_t>(job.windows.size()), job.windows.data(), sbase, alloc, nullptr, made.data(),
+					ncb.data(), status.data());
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (!made[i]) continue;
+					const auto* b = static_cast<const std::byte*>(made[i]);
+					out[i].assign(b, b + ncb[i]);
+					std::free(made[i]);
+				}
+				if (rc < 0)
+					throw std::runtime_error(detail::text("Error code ", rc, " while writing a region into blosc2 chunks (", cimg_last_error(engine()), ")"));
+				return out;
 			}
 
 			// one chunk -> its pixels; chunk_bytes = what the chunk buffer really holds (0: unknown, trust the header)

@@ -154,6 +154,36 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			plan_region(out.data(), width, x, y, width, height, job);
 			blosc2::batch::decompress_windows(job);
 		}
+		/// Write `data` (width * height elements, row-major) over the rectangle [x, x + width) x [y, y + height).  Only the blocks
+		/// the rectangle meets are decoded and re-encoded, on the device; the result is what compressing the edited pixels from
+		/// scratch gives.  Lazy chunks the rectangle meets become real.  Nothing changes unless the whole call succeeds.
+		void set_region(std::span<const T> data, size_t x, size_t y, size_t width, size_t height)
+		{
+			check_region(x, y, width, height);
+			if (data.size() != width * height)
+				throw std::invalid_argument(detail::text("set_region: span holds ", data.size(), " elements, the region has ", width * height));
+			require();
+			require_encoder();
+			blosc2::batch::update_job job;
+			region_cparams(job.cparams);
+			std::visit([&](auto& s) {
+				using table_t = std::decay_t<decltype(s)>;
+				typename table_t::region_write rw;
+				s.plan_region_write(data.data(), width, m_Width, x, y, width, height, job, rw);
+				auto made = blosc2::batch::update_windows(job);
+				s.prepare_region_write(m_CompressionContext.get(), rw, made);
+				s.commit_region_write(rw);
+			}, *m_Schunk);
+		}
+		/// The codec parameters of this channel's compression context (what set_region hands the engine).
+		void region_cparams(cimg_cparams& out) const
+		{
+			require_encoder();
+			const int rc = cimg_context_cparams(m_CompressionContext.get(), &out);
+			if (rc < 0) throw std::runtime_error(detail::text("Unable to read the compression parameters, error code ", rc));
+		}
+		blosc2::context_raw_ptr compression_context() const { return m_CompressionContext.get(); }
+
 		/// Batch building block of image<T>::get_region: queue this channel's windows (rows out_pitch elements apart).
 		void plan_region(T* out, size_t out_pitch, size_t x, size_t y, size_t width, size_t height, blosc2::batch::window_job& job) const
 		{

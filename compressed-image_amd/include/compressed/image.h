@@ -9,6 +9,7 @@
 // JSON metadata (nlohmann-json is absent; metadata is an ordered string map here).
 #pragma once
 #include <cstddef>
+#include <cstring>
 #include <iostream>
 #include <map>
 #include <optional>
@@ -200,6 +201,53 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			}
 			blosc2::batch::decompress_windows(job);
 			return out;
+		}
+
+		/// Write one span per channel (width * height elements each, row-major) over the rectangle of every channel: one engine call
+		/// for all channels that share their codec parameters.  Nothing changes unless the whole call succeeds.
+		void set_region(const std::vector<std::span<const T>>& data, size_t x, size_t y, size_t width, size_t height)
+		{
+			if (data.size() != m_Channels.size())
+				throw std::invalid_argument(detail::text("set_region: got ", data.size(), " spans for ", m_Channels.size(), " channels"));
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				m_Channels[ch].check_region(x, y, width, height);
+				if (data[ch].size() != width * height)
+					throw std::invalid_argument(detail::text("set_region: span ", ch, " holds ", data[ch].size(), " elements, the region has ", width * height));
+			}
+			// one engine call per distinct set of codec parameters (one for an image whose channels share them); every call and every
+			// lazy chunk's compress happens before the first chunk of any channel is replaced
+			std::vector<blosc2::batch::update_job> jobs;
+			std::vector<size_t> job_of(m_Channels.size());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				cimg_cparams c{};
+				m_Channels[ch].region_cparams(c);
+				size_t k = 0;
+				while (k < jobs.size() && std::memcmp(&jobs[k].cparams, &c, sizeof c) != 0) ++k;
+				if (k == jobs.size()) { jobs.emplace_back(); jobs.back().cparams = c; }
+				job_of[ch] = k;
+			}
+			using table_var = std::variant<typename blosc2::schunk<T>::region_write, typename blosc2::lazy_schunk<T>::region_write>;
+			std::vector<table_var> rws;
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					typename std::decay_t<decltype(table)>::region_write rw;
+					table.plan_region_write(data[ch].data(), width, m_Channels[ch].width(), x, y, width, height, jobs[job_of[ch]], rw);
+					rws.emplace_back(std::move(rw));
+				}, m_Channels[ch].chunks());
+			std::vector<std::vector<std::vector<std::byte>>> made;
+			for (auto& job : jobs) made.push_back(blosc2::batch::update_windows(job));
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.prepare_region_write(m_Channels[ch].compression_context(), std::get<rw_t>(rws[ch]), made[job_of[ch]]);
+				}, m_Channels[ch].chunks());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.commit_region_write(std::get<rw_t>(rws[ch]));
+				}, m_Channels[ch].chunks());
 		}
 
 		/// All channels into caller-owned memory (num_channels * height * width elements, channel-major): no

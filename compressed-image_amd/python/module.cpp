@@ -178,6 +178,26 @@ namespace
 			});
 		}
 
+		// the (height, width) array over the rectangle at (x, y): only the blocks it meets are decoded and re-encoded
+		void set_region(py::ssize_t x, py::ssize_t y, const py::array& array)
+		{
+			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			visit([&]<typename T>(compressed::channel<T>& ch) {
+				const auto [h, w] = region_shape<T>(array);
+				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				auto [keep, px] = elements<T>(array);
+				ch.set_region(px, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				return 0;
+			});
+		}
+
+		template <typename T> static std::pair<size_t, size_t> region_shape(const py::array& a)
+		{
+			if (!a.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+			if (a.ndim() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(a.ndim()) + " dimensions");
+			return { static_cast<size_t>(a.shape(0)), static_cast<size_t>(a.shape(1)) };
+		}
+
 		template <typename T> static void check_chunk_array(const py::array& a, size_t elems, bool exact)
 		{
 			if (!a.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
@@ -274,6 +294,30 @@ namespace
 				return out;
 			});
 		}
+		// one (height, width) array per channel over the rectangle at (x, y): one engine call
+		void set_region(py::ssize_t x, py::ssize_t y, const std::vector<py::array>& arrays)
+		{
+			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			visit([&]<typename T>(const img_ptr<T>& img) {
+				if (arrays.size() != img->num_channels())
+					throw py::value_error("got " + std::to_string(arrays.size()) + " arrays for " + std::to_string(img->num_channels()) + " channels");
+				std::vector<py::array> keep;
+				std::vector<std::span<const T>> spans;
+				size_t h = 0, w = 0;
+				for (size_t i = 0; i < arrays.size(); ++i)
+				{
+					const auto [hi, wi] = Channel::region_shape<T>(arrays[i]);
+					if (i > 0 && (hi != h || wi != w)) throw py::value_error("region arrays must all have the same shape");
+					h = hi; w = wi;
+					auto [k, px] = elements<T>(arrays[i]);
+					keep.push_back(k);
+					spans.push_back(px);
+				}
+				for (const auto& ch : img->channels()) ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				img->set_region(spans, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				return 0;
+			});
+		}
 		py::array get_decompressed() const
 		{
 			return visit([]<typename T>(const img_ptr<T>& img) {
@@ -330,7 +374,8 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_chunk", &Channel::get_chunk_into, py::arg("chunk_index"), py::arg("array"))
 		.def("set_chunk", &Channel::set_chunk, py::arg("chunk_index"), py::arg("array"))
 		.def("get_decompressed", &Channel::get_decompressed)
-		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"));
+		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"))
+		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"));
 
 	py::class_<Image>(m, "Image", py::module_local())
 		.def(py::init<const py::object&, const std::vector<py::array>&, size_t, size_t, std::vector<std::string>, codec, size_t, size_t, size_t>(),
@@ -345,6 +390,7 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("channels", &Image::channels)
 		.def("get_decompressed", &Image::get_decompressed)
 		.def("get_region", &Image::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"))
+		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("print_statistics", [](const Image& i) { i.visit([](auto& img) { img->print_statistics(); return 0; }); })
 		.def("compression_ratio", [](const Image& i) { return i.visit([](auto& img) { return img->compression_ratio(); }); })

@@ -202,6 +202,36 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
  * call only).  Any pointer may be NULL. */
 void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded);
 
+/* ---- window writes: edit compressed planes in place of get_chunk + set_chunk ------------------------
+ * The windows are cimg_window, with out_off / out_pitch describing the SOURCE: row r of a window is taken from
+ * src + out_off + r * out_pitch.  Windows apply in call order (a later window wins where two overlap).  Every touched chunk's new
+ * bytes equal what cimg_compress_batch_* with `p` and destsize[i] produces from the chunk's decoded pixels with the windows
+ * written in (for lz4 and blosclz: blosc2_compress_ctx's bytes).  Only the blocks a window row meets are decoded and re-encoded;
+ * the other blocks' streams are copied from the old chunk.  zstd chunks, blocks beyond the normal kernels' LDS, memcpyed and
+ * special-zero chunks are decoded, patched and compressed whole on the device.  The input chunks are never modified.
+ * Nothing runs, and the call returns BLOSC2_ERROR_INVALID_PARAM, unless every window passes the checks of the window reads, every
+ * touched chunk's header agrees with `p` (typesize, codec, filters, split decision, effective blocksize for its nbytes) and every
+ * destsize[i] >= 32.  A damaged touched chunk gets its decode error in status[i] and new_cbytes[i] = 0; the others are still
+ * written; the call returns the first failing code.  clevel is not in the header: passing the one the chunks were made with is
+ * the caller's job, as it is for compress. */
+/* Device-resident chunks in, device-resident new chunks out.  Chunk i is read at d_comp + comp_off[i] (comp_size may be NULL);
+ * if some window row meets it, its new form is written to d_new + new_off[i] (capacity destsize[i]) and new_cbytes[i] > 0;
+ * otherwise new_cbytes[i] = 0 and neither area is touched.  d_new must not overlap the input chunks. */
+int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                               const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                               int32_t nwindows, const cimg_window* w, const void* d_src, void* d_new, const int64_t* new_off,
+                               int32_t* new_cbytes, int32_t* status);
+/* Host-resident: headers read on the host, only the touched chunks and the window bytes go up; each touched chunk's new form comes
+ * back in memory from `alloc` (as cimg_compress_batch_host_packed does), new_chunks[i] = NULL for the rest. */
+int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                             const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
+                             const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
+                             int32_t* status);
+/* The last update call on this engine: blocks staged from their old streams, blocks re-encoded on the splice route, chunks decoded
+ * and compressed whole, bytes uploaded (host call only: touched chunks and window bytes).  Any pointer may be NULL. */
+void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole,
+                              int64_t* bytes_uploaded);
+
 /* ---- glue between the blosc2 shim and the batched calls ----------------------------------------------
  * The single-chunk blosc2_*_ctx calls run on one process-wide engine (device $CIMG_DEVICE, else the
  * current HIP device); cimg_shared_engine() hands it out so that host code holding blosc2 contexts
@@ -234,7 +264,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* zstd blocks beyond the normal kernels' LDS: the wide encoder's zstd instance, the replay out of device-memory slots */
        CIMG_K_ENCODE_WIDE_ZSTD = 14, CIMG_K_ZSTD_REPLAY_WIDE = 15,
        /* the window launch of cimg_decompress_windows_device / _host */
-       CIMG_K_DECODE_WINDOW = 16, CIMG_K_COUNT = 17 };
+       CIMG_K_DECODE_WINDOW = 16,
+       /* window writes: stage-and-patch, splice layout, splice copy */
+       CIMG_K_UPDATE_PATCH = 17, CIMG_K_UPDATE_LAYOUT = 18, CIMG_K_UPDATE_EMIT = 19, CIMG_K_COUNT = 20 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

@@ -4,6 +4,12 @@
       events (K_DECODE + K_DECODE_ZSTD / K_DECODE_WINDOW) and wall time of the call, medians of REPS;
   (2) the Python module: Channel.get_region(1024, 1024, 512, 512) on a 4096^2 float16 channel (4 MiB chunks) against
       get_decompressed()[1024:1536, 1024:1536], wall time, medians of REPS.
+Write legs, each against what it replaces, the chunk round trip on the same chunks:
+  (3) one 1024^2 window written into the device-resident plane of (1) (cimg_update_windows_device, 17 chunks touched) against a
+      decode of those 17 chunks plus their compress (cimg_decompress_batch_device_sized + cimg_compress_batch_device) -- kernel and
+      wall time; the stats of the update (blocks staged / re-encoded);
+  (4) the Python module: Channel.set_region of a 64^2 and a 512^2 window at (1024, 1024) into a 4096^2 float16 channel against
+      get_chunk(2) + numpy edit + set_chunk(2), wall time; and the bytes the host call uploads (cimg_update_windows_host).
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -61,8 +67,35 @@ assert np.array_equal(got, img[y0:y0 + w, x0:x0 + w])
 res.update(full_decode_kernel_us=round(full_k, 1), full_decode_wall_us=round(full_w, 1), window_kernel_us=round(win_k, 1),
            window_wall_us=round(win_w, 1), window_blocks=eng.window_stats()["blocks_decoded"], plane_blocks=nch * (chunk // 32768),
            kernel_ratio=round(full_k / win_k, 2), wall_ratio=round(full_w / win_w, 2))
+# (3) write: a 1024^2 window into the plane, against decode + compress of the chunks it touches
+rows = chunk // (n * 4)
+first, last = y0 // rows, (y0 + w - 1) // rows
+tc = list(range(first, last + 1))
+win = np.random.default_rng(1).integers(0, 1 << 20, (w, w)).astype(np.float32)
+d_src = eng.alloc(w * w * 4)
+d_src.upload(win.view(np.uint8).ravel())
+d_new = eng.alloc(nch * dest)
+wspec = dict(spec, out_off=0, out_pitch=w * 4)
+upd_k, upd_w = timed(lambda: eng.update_windows_device(hip.cparams(4), d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, [chunk + 32] * nch,
+                                                       [wspec], d_src.ptr, d_new.ptr, comp_off, comp_size=cb),
+                     (hip.K_UPDATE_PATCH, hip.K_UPDATE_LAYOUT, hip.K_UPDATE_EMIT, hip.K_ENCODE, hip.K_DECODE, hip.K_DECODE_ZSTD, hip.K_LAYOUT,
+                      hip.K_EMIT))
+ust = eng.update_stats()
+tco, tro = comp_off[tc], np.arange(len(tc), dtype=np.int64) * chunk
+
+
+def round_trip():
+    eng.decompress_device(d_comp.ptr, tco, [chunk] * len(tc), [32768] * len(tc), d_raw.ptr, tro, comp_size=cb[tc])
+    eng.compress_device(hip.cparams(4), d_raw.ptr, tro, [chunk] * len(tc), d_new.ptr, tco, [chunk + 32] * len(tc))
+
+
+rt_k, rt_w = timed(round_trip, (hip.K_DECODE, hip.K_DECODE_ZSTD, hip.K_ENCODE, hip.K_LAYOUT, hip.K_EMIT))
+res.update(write_chunks=len(tc), write_blocks_decoded=ust["blocks_decoded"], write_blocks_encoded=ust["blocks_encoded"],
+           write_chunks_whole=ust["chunks_whole"], write_kernel_us=round(upd_k, 1), write_wall_us=round(upd_w, 1),
+           roundtrip_kernel_us=round(rt_k, 1), roundtrip_wall_us=round(rt_w, 1), write_kernel_ratio=round(rt_k / upd_k, 2),
+           write_wall_ratio=round(rt_w / upd_w, 2))
+d_src.free(); d_new.free()
 d_raw.free(); d_comp.free(); d_win.free()
-eng.close()
 
 path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
 spec_m = importlib.util.spec_from_file_location("compressed_image", path)
@@ -86,6 +119,34 @@ reg_us, a = wall(lambda: ch.get_region(1024, 1024, 512, 512))
 dec_us, b = wall(lambda: ch.get_decompressed()[1024:1536, 1024:1536].copy())
 assert np.array_equal(a, b) and np.array_equal(a, arr[1024:1536, 1024:1536])
 res.update(region_wall_us=round(reg_us, 1), decompressed_slice_wall_us=round(dec_us, 1), region_speedup=round(dec_us / reg_us, 2))
+
+# (4) write through the module: set_region against get_chunk + edit + set_chunk of the chunk it lies in (chunk 2: rows 1024 .. 1535)
+for side in (64, 512):
+    p = np.random.default_rng(side).integers(0, 1000, (side, side)).astype(np.float16)
+    set_us, _ = wall(lambda: ch.set_region(1024, 1024, p))
+
+    def chunk_trip():
+        c = ch.get_chunk(2).reshape(512, 4096)
+        c[:side, 1024:1024 + side] = p
+        ch.set_chunk(2, c.ravel())
+
+    trip_us, _ = wall(chunk_trip)
+    res["set_region_%d_wall_us" % side] = round(set_us, 1)
+    res["chunk_trip_%d_wall_us" % side] = round(trip_us, 1)
+    res["set_region_%d_speedup" % side] = round(trip_us / set_us, 2)
+ref = arr.copy()
+ref[1024:1536, 1024:1536] = np.random.default_rng(512).integers(0, 1000, (512, 512)).astype(np.float16)
+assert np.array_equal(ch.get_decompressed(), ref)
+# the host call's traffic for the 64^2 window: the touched chunk up, the window up, the new chunk down
+plane16 = np.ascontiguousarray(arr).view(np.uint8).ravel()
+chunks16 = eng.compress_host(hip.cparams(2), plane16, [chunk] * 8, [chunk + 32] * 8)
+src16 = np.random.default_rng(2).integers(0, 1000, (64, 64)).astype(np.float16).view(np.uint8).ravel()
+new16, _ = eng.update_windows_host(hip.cparams(2), chunks16, [chunk + 32] * 8, [dict(chunk_first=0, chunk_count=8, origin=1024 * 4096 + 1024,
+                                   row_pitch=4096, width=64, height=64, out_off=0, out_pitch=128)], src16)
+hst = eng.update_stats()
+res.update(host_64_bytes_up=hst["bytes_uploaded"], host_64_bytes_down=sum(len(c) for c in new16 if c is not None),
+           host_64_blocks_decoded=hst["blocks_decoded"], chunk_trip_bytes_each_way=chunk + len(chunks16[2]))
+eng.close()
 line = json.dumps(res)
 print(line)
 if len(sys.argv) > 2 and sys.argv[1] == "--out":
