@@ -17,13 +17,14 @@ K_ENCODE_WIDE, K_DECODE_WIDE = 12, 13          # blocks beyond the normal kernel
 K_ENCODE_WIDE_ZSTD, K_ZSTD_REPLAY_WIDE = 14, 15  # ... of zstd chunks
 K_DECODE_WINDOW = 16                           # windows: the blocks a window meets (csrc/window_kernel.h)
 K_UPDATE_PATCH, K_UPDATE_LAYOUT, K_UPDATE_EMIT = 17, 18, 19   # window writes (csrc/update_kernel.h)
+K_PACK, K_INTERLEAVE = 20, 21                  # packed device storage (csrc/pack_kernel.h, csrc/interleave_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
 KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cimg_decode_blocks", "cimg_deinterleave",
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
-           "cimg_update_patch", "cimg_update_layout", "cimg_update_emit")
+           "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -45,6 +46,8 @@ EXPORTS = (
     "cimg_engine_debug_stamps", "cimg_engine_read_stamps", "cimg_shared_engine", "cimg_context_cparams",
     "cimg_decompress_windows_device", "cimg_decompress_windows_host", "cimg_engine_window_stats",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
+    "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
+    "cimg_interleave_device", "cimg_engine_wait_stream", "cimg_device_range_check",
     # include/blosc2.h
     "blosc2_create_cctx", "blosc2_create_dctx", "blosc2_free_ctx", "blosc2_compress_ctx",
     "blosc2_decompress_ctx", "blosc2_cbuffer_sizes", "blosc2_schunk_new", "blosc2_schunk_free",
@@ -166,6 +169,12 @@ def load():
     L.cimg_update_windows_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_update_windows_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
     L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
+    L.cimg_compress_batch_device_packed_begin.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp]
+    L.cimg_compress_batch_device_packed_fetch.argtypes = [vp, C.c_int32, vp, vp]
+    L.cimg_pack_chunks_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    L.cimg_interleave_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, vp]
+    L.cimg_engine_wait_stream.argtypes = [vp, vp]
+    L.cimg_device_range_check.argtypes = [vp, vp, C.c_size_t]
     L.blosc2_getitem_ctx.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_int, vp, C.c_int32]
     L.print_error.restype = C.c_char_p
     _lib = L
@@ -400,6 +409,37 @@ class Engine:
         if check:
             self._check(rc)
         return [raw[o:o + n] for o, n in zip(raw_off, nb)], status
+
+    # ---- packed device storage (include/cimg_hip.h) ----
+    def compress_device_packed_begin(self, p, d_raw, raw_off, nbytes, destsize):
+        """compress device-resident pixels into the engine's staging area; returns cbytes (the sizes _fetch will move)"""
+        raw_off, nbytes, destsize = _i64(raw_off), _i32(nbytes), _i32(destsize)
+        cbytes = np.zeros(nbytes.size, np.int32)
+        self._check(load().cimg_compress_batch_device_packed_begin(self.handle, C.byref(p), nbytes.size, d_raw, _ptr(raw_off), _ptr(nbytes),
+                                                                   _ptr(destsize), _ptr(cbytes)))
+        return cbytes
+
+    def compress_device_packed_fetch(self, nchunks, d_dst, dst_off):
+        dst_off = _i64(dst_off)
+        self._check(load().cimg_compress_batch_device_packed_fetch(self.handle, nchunks, d_dst, _ptr(dst_off)))
+
+    def pack_chunks_device(self, d_src, nbytes, d_dst, dst_off):
+        """d_src: device ADDRESSES of the pieces (a host list); piece i (nbytes[i] bytes) goes to d_dst + dst_off[i]"""
+        src = np.ascontiguousarray(np.asarray(d_src, dtype=np.uint64))
+        nbytes, dst_off = _i32(nbytes), _i64(dst_off)
+        self._check(load().cimg_pack_chunks_device(self.handle, nbytes.size, _ptr(src), _ptr(nbytes), d_dst, _ptr(dst_off)))
+
+    def interleave_device(self, d_planar, plane_stride, nchannels, typesize, npixels, d_interleaved):
+        """one plane per channel (plane c at d_planar + c * plane_stride) -> interleaved pixels"""
+        self._check(load().cimg_interleave_device(self.handle, d_planar, plane_stride, nchannels, typesize, npixels, d_interleaved))
+
+    def wait_stream(self, stream=None):
+        """the engine's stream waits for what `stream` (an integer hipStream_t; None: the null stream) holds now"""
+        self._check(load().cimg_engine_wait_stream(self.handle, stream))
+
+    def device_range_check(self, ptr, nbytes):
+        """0 if [ptr, ptr + nbytes) is memory of the engine's device inside one allocation, else the (negative) error code"""
+        return load().cimg_device_range_check(self.handle, ptr, nbytes)
 
     # ---- windows (include/cimg_hip.h: cimg_window) ----
     def decompress_windows_device(self, d_comp, comp_off, nbytes, blocksize, typesize, specs, d_out, comp_size=None, check=True):

@@ -19,6 +19,8 @@
 #include "update_plan.h"
 #include "assemble_kernel.h"
 #include "deinterleave_kernel.h"
+#include "interleave_kernel.h"
+#include "pack_kernel.h"
 #include "zstd_kernel.h"
 #include "zstd_walk_kernel.h"
 #include "zstd_seq_kernel.h"
@@ -83,6 +85,19 @@ extern "C" __global__ __launch_bounds__(64) void cimg_deinterleave(DeinterleaveA
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     deinterleave_wave(a, lds, (int64_t)blockIdx.x);
+}
+
+// planes -> interleaved pixels, one wave per tile of the same size (interleave_kernel.h)
+extern "C" __global__ __launch_bounds__(64) void cimg_interleave(InterleaveArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    interleave_wave(a, lds, (int64_t)blockIdx.x);
+}
+
+// batched gather copy of variable-sized pieces, one wave per 16 KiB tile of a piece (pack_kernel.h)
+extern "C" __global__ __launch_bounds__(64) void cimg_pack_chunks(PackArgs a)
+{
+    pack_wave(a, (int)blockIdx.x);
 }
 
 extern "C" __global__ __launch_bounds__(64) void cimg_layout_chunks(AssembleArgs a)
@@ -405,6 +420,10 @@ struct cimg_engine {
     // window writes (update_plan.h): patched blocks, the launches' tables, the host call's staged sources and new chunks
     DevBuf upd_patch, upd_units, upd_stage, upd_items, upd_descs, upd_chunks, upd_blocks, upd_layout, upd_src, upd_new;
     PinBuf h_upd_st, h_upd_hdr;
+    // the pack launch's piece table (pack_kernel.h), and the event cimg_engine_wait_stream records on the caller's stream
+    DevBuf pack_tab;
+    PinBuf h_pack_tab;
+    hipEvent_t ev_wait = nullptr;
     UpdateStats upd_stats;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
     bool claunched = false;               // compress_launch got past the planner and the allocations: h_out holds (or will hold) this batch's sizes
@@ -561,6 +580,8 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
+    case CIMG_K_PACK: return "cimg_pack_chunks";
+    case CIMG_K_INTERLEAVE: return "cimg_interleave";
     default: return "?";
     }
 }
@@ -634,9 +655,9 @@ void cimg_engine_destroy(cimg_engine* e)
     for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
                     &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots,
                     &e->upd_patch, &e->upd_units, &e->upd_stage, &e->upd_items, &e->upd_descs, &e->upd_chunks, &e->upd_blocks, &e->upd_layout,
-                    &e->upd_src, &e->upd_new})
+                    &e->upd_src, &e->upd_new, &e->pack_tab})
         if (b->p) (void)hipFree(b->p);
-    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr})
+    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr, &e->h_pack_tab})
         if (b->p) (void)hipHostFree(b->p);
     (void)hipStreamDestroy(e->stream);
     if (e->s_h2d) { (void)hipStreamSynchronize(e->s_h2d); (void)hipStreamDestroy(e->s_h2d); }
@@ -646,6 +667,7 @@ void cimg_engine_destroy(cimg_engine* e)
     if (e->ev_side_done) (void)hipEventDestroy(e->ev_side_done);
     for (int k = 0; k < 2; k++) if (e->ev_h2d[k]) (void)hipEventDestroy(e->ev_h2d[k]);
     if (e->ev_done) (void)hipEventDestroy(e->ev_done);
+    if (e->ev_wait) (void)hipEventDestroy(e->ev_wait);
     delete e;
 }
 
@@ -2496,6 +2518,145 @@ void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* 
     if (blocks_encoded) *blocks_encoded = e->upd_stats.blocks_encoded;
     if (chunks_whole) *chunks_whole = e->upd_stats.chunks_whole;
     if (bytes_uploaded) *bytes_uploaded = e->upd_stats.bytes_uploaded;
+}
+
+
+// ---- packed device storage: batched gather copy, compress to exact-size chunks, planes -> pixels ---------------------------
+// the pack launch for a piece table (enqueued on the engine's stream; the caller synchronises)
+static int pack_launch(cimg_engine* e, int32_t n, const void* const* src, const int32_t* bytes, void* d_dst, const int64_t* dst_off)
+{
+    std::vector<PackPiece> pieces;
+    int64_t ntiles = 0;
+    const int prc = pack_plan(n, src, bytes, (uint8_t*)d_dst, dst_off, pieces, &ntiles);
+    if (prc == -1) return e->fail(ERR_INVALID_PARAM, "pack: negative piece size");
+    if (prc == -2) return e->fail(ERR_INVALID_PARAM, "pack: a destination range overlaps a source or another destination range of the call");
+    if (prc) return e->fail(ERR_INVALID_PARAM, "pack: too many bytes for one call");
+    if (pieces.empty()) return 0;
+    for (const PackPiece& p : pieces) if (!p.src) return e->fail(ERR_INVALID_PARAM, "pack: null source address");
+    int rc;
+    const size_t tab = pieces.size() * sizeof(PackPiece);
+    if ((rc = e->reserve(e->pack_tab, tab))) return rc;
+    if ((rc = e->reserve(e->h_pack_tab, tab))) return rc;
+    // (every call that launches this kernel ends with a stream synchronize: the pinned table is free again)
+    memcpy(e->h_pack_tab.p, pieces.data(), tab);
+    if ((rc = e->hip(hipMemcpyAsync(e->pack_tab.p, e->h_pack_tab.p, tab, hipMemcpyHostToDevice, e->stream), "pack table H2D"))) return rc;
+    PackArgs a{(const PackPiece*)e->pack_tab.p, (int32_t)pieces.size(), (int32_t)ntiles};
+    return e->launch(CIMG_K_PACK, cimg_pack_chunks, a, (int)ntiles, 64, 0);
+}
+
+int cimg_pack_chunks_device(cimg_engine* e, int32_t nchunks, const void* const* d_src, const int32_t* bytes, void* d_dst, const int64_t* dst_off)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    if (nchunks <= 0) return nchunks < 0 ? e->fail(ERR_INVALID_PARAM, "negative piece count") : 0;
+    if (!d_src || !bytes || !d_dst || !dst_off) return e->fail(ERR_INVALID_PARAM, "null argument");
+    (void)hipSetDevice(e->device);
+    e->begin_batch(0);
+    const int rc = pack_launch(e, nchunks, d_src, bytes, d_dst, dst_off);
+    const int src = cimg_engine_synchronize(e);
+    return rc ? rc : src;
+}
+
+int cimg_compress_batch_device_packed_begin(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_raw, const int64_t* raw_off,
+                                            const int32_t* nbytes, const int32_t* destsize, int32_t* cbytes)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->fetch_off.clear();
+    if (nchunks <= 0) return 0;
+    if (!p || !d_raw || !raw_off || !nbytes || !destsize || !cbytes) return e->fail(ERR_INVALID_PARAM, "null argument");
+    (void)hipSetDevice(e->device);
+    e->cflight_chunks = -1;
+    // every chunk gets its full destsize in the staging area; _fetch moves what the encoder really wrote
+    std::vector<int64_t> d_comp_off((size_t)nchunks);
+    int64_t comp_total = 0;
+    for (int i = 0; i < nchunks; i++) {
+        if (nbytes[i] < 0 || destsize[i] < 0) return e->fail(ERR_INVALID_PARAM, "negative size");
+        d_comp_off[(size_t)i] = comp_total;
+        comp_total += ((int64_t)destsize[i] + 63) & ~63ll;
+    }
+    int rc;
+    if ((rc = e->reserve(e->stage_comp, (size_t)comp_total + 64))) return rc;
+    rc = compress_launch(e, p, nchunks, d_raw, raw_off, nbytes, e->stage_comp.p, d_comp_off.data(), destsize, e->dflight_open);
+    const int frc = rc ? 0 : compress_finish(e, nchunks, cbytes);
+    if (rc || frc) return rc ? rc : frc;
+    e->fetch_off = std::move(d_comp_off);
+    e->fetch_len.assign(cbytes, cbytes + nchunks);
+    return 0;
+}
+
+int cimg_compress_batch_device_packed_fetch(cimg_engine* e, int32_t nchunks, void* d_dst, const int64_t* dst_off)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    if (nchunks <= 0) return 0;
+    if (!d_dst || !dst_off) return e->fail(ERR_INVALID_PARAM, "null argument");
+    if ((size_t)nchunks != e->fetch_off.size()) return e->fail(ERR_INVALID_PARAM, "no compressed batch of %d chunks is waiting to be fetched", nchunks);
+    (void)hipSetDevice(e->device);
+    std::vector<const void*> src((size_t)nchunks);
+    std::vector<int32_t> len((size_t)nchunks);
+    for (int i = 0; i < nchunks; i++) {
+        src[(size_t)i] = (const uint8_t*)e->stage_comp.p + e->fetch_off[(size_t)i];
+        len[(size_t)i] = e->fetch_len[(size_t)i] > 0 ? e->fetch_len[(size_t)i] : 0;       // (a chunk that did not fit has nothing to move)
+    }
+    e->fetch_off.clear();
+    e->begin_batch(0);
+    const int rc = pack_launch(e, nchunks, src.data(), len.data(), d_dst, dst_off);
+    const int src_rc = cimg_engine_synchronize(e);
+    return rc ? rc : src_rc;
+}
+
+int cimg_interleave_device(cimg_engine* e, const void* d_planar, int64_t plane_stride, int32_t nch, int32_t ts, int64_t npixels, void* d_interleaved)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    (void)hipSetDevice(e->device);
+    if (!d_interleaved || !d_planar) return e->fail(ERR_INVALID_PARAM, "null argument");
+    if (nch < 1 || nch > 4096 || (ts != 1 && ts != 2 && ts != 4 && ts != 8)) return e->fail(ERR_INVALID_PARAM, "interleave: %d channels of %d-byte elements are not supported", nch, ts);
+    if (npixels < 0 || (plane_stride & 15) || plane_stride < npixels * ts) return e->fail(ERR_INVALID_PARAM, "interleave: the plane stride must be a multiple of 16 and hold a plane");
+    if ((((uintptr_t)d_interleaved) | ((uintptr_t)d_planar)) & 15) return e->fail(ERR_INVALID_PARAM, "interleave: buffers must be 16-byte aligned");
+    if (nch * ts * 16 > 16384) return e->fail(ERR_INVALID_PARAM, "interleave: %d channels of %d bytes do not fit a tile", nch, ts);
+    if (npixels == 0) return 0;
+    const int tile = deinterleave_tile_pixels(nch, ts);
+    const int64_t tiles = (npixels + tile - 1) / tile;
+    if (tiles > 0x7fffffff) return e->fail(ERR_INVALID_PARAM, "interleave: too many pixels for one call");
+    const int lds = interleave_lds_bytes(nch, ts);
+    e->begin_batch(0);
+    InterleaveArgs a{(const uint8_t*)d_planar, (uint8_t*)d_interleaved, plane_stride, npixels, nch, ts, tile, lds};
+    const int rc = e->launch(CIMG_K_INTERLEAVE, cimg_interleave, a, (int)tiles, 64, lds);
+    const int src = cimg_engine_synchronize(e);
+    return rc ? rc : src;
+}
+
+int cimg_engine_wait_stream(cimg_engine* e, void* stream)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    (void)hipSetDevice(e->device);
+    int rc;
+    if (!e->ev_wait && (rc = e->hip(hipEventCreateWithFlags(&e->ev_wait, hipEventDisableTiming), "hipEventCreate"))) return rc;
+    if ((rc = e->hip(hipEventRecord(e->ev_wait, (hipStream_t)stream), "hipEventRecord(caller's stream)"))) return rc;
+    return e->hip(hipStreamWaitEvent(e->stream, e->ev_wait, 0), "hipStreamWaitEvent");
+}
+
+int cimg_device_range_check(cimg_engine* e, const void* p, size_t bytes)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    if (!p) return e->fail(ERR_INVALID_PARAM, "null address where device memory is expected");
+    (void)hipSetDevice(e->device);
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();                          // (an address HIP has never seen: ordinary host memory)
+        return e->fail(ERR_INVALID_PARAM, "%p is not device memory", p);
+    }
+    if (attr.type != hipMemoryTypeDevice) return e->fail(ERR_INVALID_PARAM, "%p is not device memory (memory type %d)", p, (int)attr.type);
+    if (attr.device != e->device) return e->fail(ERR_INVALID_PARAM, "%p is memory of device %d, the engine runs on device %d", p, attr.device, e->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return e->fail(ERR_INVALID_PARAM, "%p: the extent of its allocation is unknown", p);
+    }
+    const uintptr_t a = (uintptr_t)p, lo = (uintptr_t)base, hi = lo + size;
+    if (a < lo || a > hi || bytes > hi - a)
+        return e->fail(ERR_INVALID_PARAM, "%zu bytes at %p run past their allocation (%zu bytes at %p)", bytes, p, size, (void*)base);
+    return 0;
 }
 
 }  // extern "C"

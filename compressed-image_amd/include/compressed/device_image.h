@@ -1,0 +1,254 @@
+// device_image.h -- compressed::device_image<T>: equally sized channels kept COMPRESSED IN DEVICE MEMORY, in ONE store.
+//
+// The counterpart of image<T> (image.h) for pixels that live on the GPU.  All channels are compressed in one engine batch into one
+// allocation (device_channel.h: the store), so a region of every channel is ONE windows call over one base address, and, if the
+// consumer wants pixels (h, w, C) instead of planes (C, h, w), one more launch interleaves them on the device.
+// add_channel / remove_channel are not offered: the store is one packed allocation.
+#pragma once
+#include <optional>
+#include <string>
+#include <string_view>
+
+#include "device_channel.h"
+#include "image.h"
+
+namespace NAMESPACE_COMPRESSED_IMAGE
+{
+	template <typename T>
+	struct device_image
+	{
+		device_image() = default;
+		device_image(device_image&&) noexcept = default;
+		device_image& operator=(device_image&&) noexcept = default;
+		device_image(const device_image&) = delete;
+		device_image& operator=(const device_image&) = delete;
+
+		/// Compress planar channels (each width * height elements in device memory), all in one engine batch.
+		device_image(const std::vector<const T*>& d_channels, size_t width, size_t height, std::vector<std::string> channel_names = {},
+			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+		{
+			init(compression_codec, compression_level, block_size, chunk_size, width, height, d_channels.size(), channel_names);
+			if (d_channels.empty()) return;
+			cimg_engine* e = blosc2::batch::engine();
+			const size_t total = width * height * sizeof(T);
+			const std::byte* base = reinterpret_cast<const std::byte*>(d_channels[0]);
+			for (const T* c : d_channels)
+			{
+				detail::device_range(e, c, total, "device_image");
+				base = std::min(base, reinterpret_cast<const std::byte*>(c));
+			}
+			std::vector<int64_t> raw_off;
+			std::vector<int32_t> nbytes;
+			for (const T* c : d_channels)
+				for (size_t off = 0; off < total; off += m_ChunkSize)
+				{
+					raw_off.push_back(static_cast<int64_t>(reinterpret_cast<const std::byte*>(c) - base) + static_cast<int64_t>(off));
+					nbytes.push_back(static_cast<int32_t>(std::min(m_ChunkSize, total - off)));
+				}
+			m_Store = detail::compress_to_store(prototype().cparams(), base, raw_off, nbytes, m_ChunkSize);
+		}
+
+		/// Channels that arrive INTERLEAVED in device memory (R G B A R G B A ...): split into planes on the device, then as above.
+		static device_image from_interleaved(const T* d_interleaved, size_t width, size_t height, size_t nchannels, std::vector<std::string> channel_names = {},
+			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+		{
+			if (nchannels == 0) throw std::runtime_error("Invalid interleaved data passed. Expected at least one channel");
+			cimg_engine* e = blosc2::batch::engine();
+			const size_t npixels = width * height;
+			detail::device_range(e, d_interleaved, npixels * nchannels * sizeof(T), "from_interleaved");
+			if (reinterpret_cast<uintptr_t>(d_interleaved) & 15) throw std::invalid_argument("from_interleaved: the pixels must be 16-byte aligned");
+			const size_t stride = blosc2::batch::planar_stride(npixels, sizeof(T));
+			detail::device_store planes;
+			planes.allocate(e, stride * nchannels + 64);
+			detail::engine_call(e, cimg_deinterleave_device(e, d_interleaved, static_cast<int32_t>(nchannels), static_cast<int32_t>(sizeof(T)),
+				static_cast<int64_t>(npixels), planes.base, static_cast<int64_t>(stride)), "Splitting the interleaved pixels");
+			std::vector<const T*> ch(nchannels);
+			for (size_t c = 0; c < nchannels; ++c) ch[c] = reinterpret_cast<const T*>(planes.base + c * stride);
+			// (the batch is enqueued on the engine's stream behind the split, and returns after the stream has been synchronised)
+			return device_image(ch, width, height, std::move(channel_names), compression_codec, compression_level, block_size, chunk_size);
+		}
+
+		/// The compressed chunks of a host image, moved over PCIe as they are.  Its channels must share codec, level, block and chunk size.
+		static device_image from_image(const image<T>& host)
+		{
+			device_image out;
+			const auto& chans = host.channels();
+			if (chans.empty()) { out.m_Width = host.width(); out.m_Height = host.height(); return out; }
+			out.init(chans[0].compression(), chans[0].compression_level(), chans[0].block_size(), chans[0].chunk_size(), host.width(), host.height(),
+				chans.size(), host.channelnames());
+			out.m_ChunkSize = chans[0].chunk_size();
+			std::vector<std::vector<std::byte>> chunks;
+			for (const auto& c : chans)
+			{
+				if (c.compression() != out.m_Codec || c.compression_level() != out.m_CompressionLevel || c.block_size() != out.m_BlockSize || c.chunk_size() != out.m_ChunkSize)
+					throw std::invalid_argument("from_image: the channels of the image differ in codec, level, block size or chunk size");
+				detail::host_chunks(c, chunks);
+			}
+			if (chunks.size() != out.m_NumChannels * out.chunks_per_channel()) throw std::runtime_error("from_image: unexpected chunk count");
+			auto store = detail::upload_store(chunks);
+			out.m_Store = std::move(store);
+			return out;
+		}
+		image<T> to_image() const
+		{
+			std::vector<compressed::channel<T>> chans;
+			for (size_t c = 0; c < m_NumChannels; ++c) chans.push_back(channel(c).to_channel());
+			return image<T>(std::move(chans), m_Width, m_Height, m_ChannelNames);
+		}
+
+		static void wait_stream(void* stream) { device_channel<T>::wait_stream(stream); }
+
+		/// A handle on channel `index` that shares this image's store and is read-only (edits go through set_region of the image).
+		/// It keeps the store it was taken from: a later set_region of the image does not change what the handle decodes.
+		device_channel<T> channel(size_t index) const
+		{
+			if (index >= m_NumChannels)
+				throw std::out_of_range(detail::text("Channel index ", index, " is out of range for an image with ", m_NumChannels, " channels"));
+			device_channel<T> c = prototype();
+			c.m_Store = m_Store;
+			c.m_First = index * chunks_per_channel();
+			c.m_Count = chunks_per_channel();
+			c.m_ReadOnly = true;
+			return c;
+		}
+		device_channel<T> channel(const std::string_view name) const { return channel(get_channel_offset(name)); }
+		size_t get_channel_offset(const std::string_view channelname) const
+		{
+			for (size_t i = 0; i < m_ChannelNames.size(); ++i) if (m_ChannelNames[i] == channelname) return i;
+			throw std::invalid_argument(detail::text("Unknown channelname '", channelname, "' encountered"));
+		}
+
+		/// All channels into device memory (num_channels * height * width elements, channel-major): one engine call.
+		void decompress_into(T* d_out) const
+		{
+			if (m_NumChannels == 0) return;
+			cimg_engine* e = m_Store->engine;
+			detail::device_range(e, d_out, m_NumChannels * m_Width * m_Height * sizeof(T), "decompress_into");
+			const size_t n = m_Store->num_chunks();
+			std::vector<int64_t> raw_off(n);
+			int64_t at = 0;
+			for (size_t i = 0; i < n; ++i) { raw_off[i] = at; at += m_Store->nbytes[i]; }
+			std::vector<int32_t> status(n, 0);
+			detail::engine_call(e, cimg_decompress_batch_device_sized(e, static_cast<int32_t>(n), m_Store->base, m_Store->off.data(), m_Store->cbytes.data(),
+				m_Store->nbytes.data(), m_Store->blocksize.data(), d_out, raw_off.data(), status.data()), "Decompressing the image");
+		}
+		/// The rectangle of every channel in ONE windows call: planes (C, height, width) or, with `interleaved`, pixels
+		/// (height, width, C) -- then the planes are decoded into scratch and one more launch interleaves them.
+		void get_region(T* d_out, size_t x, size_t y, size_t width, size_t height, bool interleaved = false) const
+		{
+			prototype().check_region(x, y, width, height);
+			if (m_NumChannels == 0 || width == 0 || height == 0) return;
+			cimg_engine* e = m_Store->engine;
+			const size_t plane = width * height * sizeof(T);
+			detail::device_range(e, d_out, plane * m_NumChannels, "get_region");
+			const bool il = interleaved && m_NumChannels > 1;                  // (one channel: planes and pixels are the same bytes)
+			if (il && (reinterpret_cast<uintptr_t>(d_out) & 15)) throw std::invalid_argument("get_region: an interleaved result must be 16-byte aligned");
+			const size_t stride = il ? blosc2::batch::planar_stride(width * height, sizeof(T)) : plane;
+			detail::device_store scratch;
+			if (il) scratch.allocate(e, stride * m_NumChannels + 64);
+			std::vector<cimg_window> w;
+			for (size_t c = 0; c < m_NumChannels; ++c) w.push_back(channel_window(c, x, y, width, height, c * stride));
+			std::vector<int32_t> status(m_Store->num_chunks(), 0);
+			detail::engine_lock lock(e);
+			detail::engine_call(e, cimg_decompress_windows_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base, m_Store->off.data(),
+				m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)), static_cast<int32_t>(w.size()),
+				w.data(), il ? static_cast<void*>(scratch.base) : static_cast<void*>(d_out), status.data()), "Decoding the region");
+			if (il)
+				detail::engine_call(e, cimg_interleave_device(e, scratch.base, static_cast<int64_t>(stride), static_cast<int32_t>(m_NumChannels),
+					static_cast<int32_t>(sizeof(T)), static_cast<int64_t>(width * height), d_out), "Interleaving the region");
+		}
+		/// Write planes (num_channels x height x width elements in device memory, channel-major) over the rectangle of every channel:
+		/// one update call, one repack of the store.  Nothing changes unless the whole call succeeds.
+		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)
+		{
+			prototype().check_region(x, y, width, height);
+			if (m_NumChannels == 0 || width == 0 || height == 0) return;
+			const size_t plane = width * height * sizeof(T);
+			detail::device_range(m_Store->engine, d_src, plane * m_NumChannels, "set_region");
+			std::vector<cimg_window> w;
+			for (size_t c = 0; c < m_NumChannels; ++c) w.push_back(channel_window(c, x, y, width, height, c * plane));
+			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
+		}
+
+		size_t width() const noexcept { return m_Width; }
+		size_t height() const noexcept { return m_Height; }
+		size_t num_channels() const noexcept { return m_NumChannels; }
+		std::vector<std::string> channelnames() const noexcept { return m_ChannelNames; }
+		void channelnames(std::vector<std::string> names)
+		{
+			if (names.size() != m_NumChannels)
+				throw std::invalid_argument(detail::text("Invalid number of arguments received for setting channelnames. Expected vector size to be exactly ",
+					m_NumChannels, " but instead got ", names.size()));
+			m_ChannelNames = std::move(names);
+		}
+		enums::codec compression() const noexcept { return m_Codec; }
+		uint8_t compression_level() const noexcept { return m_CompressionLevel; }
+		size_t chunk_size() const
+		{
+			if (m_NumChannels == 0) throw std::runtime_error("Unable to get chunk size from image without channels");
+			return m_ChunkSize;
+		}
+		size_t block_size() const
+		{
+			if (m_NumChannels == 0) throw std::runtime_error("Unable to get block size from image without channels");
+			return m_BlockSize;
+		}
+		size_t compressed_bytes() const
+		{
+			size_t n = 0;
+			if (m_Store) for (int32_t c : m_Store->cbytes) n += static_cast<size_t>(c);
+			return n;
+		}
+		size_t uncompressed_size() const noexcept { return m_NumChannels * m_Width * m_Height; }
+		size_t num_chunks() const noexcept { return m_Store ? m_Store->num_chunks() : 0; }
+		size_t device_bytes() const noexcept { return m_Store ? m_Store->bytes : 0; }
+		double compression_ratio() const noexcept
+		{
+			return static_cast<double>(1 + uncompressed_size() * sizeof(T)) / static_cast<double>(1 + compressed_bytes());
+		}
+
+	private:
+		std::shared_ptr<detail::device_store> m_Store;
+		std::vector<std::string> m_ChannelNames{};
+		size_t m_NumChannels = 0;
+		enums::codec m_Codec = enums::codec::lz4;
+		uint8_t m_CompressionLevel = 9;
+		size_t m_BlockSize = s_default_blocksize;
+		size_t m_ChunkSize = s_default_chunksize;
+		size_t m_Width = 1;
+		size_t m_Height = 1;
+
+		void init(enums::codec codec, size_t level, size_t block_size, size_t chunk_size, size_t width, size_t height, size_t nchannels,
+			const std::vector<std::string>& names)
+		{
+			m_Codec = codec;
+			m_CompressionLevel = util::ensure_compression_level(level);
+			m_BlockSize = block_size;
+			m_Width = width; m_Height = height;
+			m_NumChannels = nchannels;
+			m_ChunkSize = util::align_chunk_to_scanlines_bytes<T>(width, chunk_size);
+			util::validate_chunk_size<T>(m_ChunkSize, "device_image");
+			if (names.size() != nchannels && !names.empty())
+				std::cout << "Invalid number of channel names received, expected " << nchannels << " but instead got " << names.size()
+					<< ". Ignoring channel names" << std::endl;
+			else
+				m_ChannelNames = names;
+		}
+		size_t chunks_per_channel() const noexcept
+		{
+			const size_t total = m_Width * m_Height * sizeof(T);
+			return (total + m_ChunkSize - 1) / m_ChunkSize;
+		}
+		/// a store-less channel with this image's geometry and codec (region checks, windows, cparams)
+		device_channel<T> prototype() const { return device_channel<T>(m_Codec, m_CompressionLevel, m_BlockSize, m_ChunkSize, m_Width, m_Height); }
+		cimg_window channel_window(size_t c, size_t x, size_t y, size_t width, size_t height, size_t out_off) const
+		{
+			device_channel<T> p = prototype();
+			p.m_First = c * chunks_per_channel();
+			p.m_Count = chunks_per_channel();
+			return p.region_window(x, y, width, height, out_off);
+		}
+	};
+}

@@ -3,6 +3,8 @@
 // bind_channel.h:17-255, bind_image.h:34-480, bind_enums.h:15-24) on top of the host mirror in
 // ../include/compressed.  dtype -> T dispatch over the same nine element types as the reference's
 // variant_t.h:92-103.  Out of scope here: Image.read / dtype(s)_from_file (OpenImageIO is absent).
+// DeviceChannel / DeviceImage / DeviceArray (not in the reference): the same surface over compressed/device_channel.h and
+// device_image.h, taking and filling GPU arrays through __cuda_array_interface__ -- neither torch nor HIP is linked here.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -17,6 +19,7 @@
 #include "compressed/channel.h"
 #include "compressed/half.h"
 #include "compressed/image.h"
+#include "compressed/device_image.h"
 
 namespace py = pybind11;
 using compressed::enums::codec;
@@ -220,6 +223,7 @@ namespace
 
 		template <typename F> auto visit(F&& f) const { return std::visit([&](auto& p) { return f(p); }, impl); }
 
+		explicit Image(any_image adopted) : impl(std::move(adopted)) {}          // (DeviceImage.to_image)
 		Image(const py::object& dtype, const std::vector<py::array>& channels, size_t width, size_t height, std::vector<std::string> names,
 			codec c, size_t level, size_t block, size_t chunk)
 		{
@@ -328,6 +332,283 @@ namespace
 			});
 		}
 	};
+
+	// ---- device-resident objects ----------------------------------------------------------------------------
+	// Inputs and out= arguments are any object with __cuda_array_interface__ (torch ROCm tensors have it): dtype from `typestr`,
+	// C-contiguous only.  Everything about an argument is checked before the engine is touched; the address itself is checked by
+	// the C++ layer (cimg_device_range_check) before a kernel sees it.
+	struct device_view
+	{
+		void* ptr = nullptr;
+		std::vector<py::ssize_t> shape;
+		py::dtype dt;
+		bool readonly = false;
+		size_t count() const { size_t n = 1; for (auto d : shape) n *= static_cast<size_t>(d); return n; }
+	};
+	device_view view_of(const py::object& o, const char* what)
+	{
+		if (py::isinstance<py::array>(o))
+			throw py::type_error(std::string(what) + ": a numpy array is host memory; pass an object with __cuda_array_interface__ (a torch tensor on the GPU)");
+		if (!py::hasattr(o, "__cuda_array_interface__"))
+			throw py::type_error(std::string(what) + ": expected an object with __cuda_array_interface__");
+		py::dict d = o.attr("__cuda_array_interface__");
+		device_view v;
+		for (auto n : d["shape"].cast<py::tuple>()) v.shape.push_back(n.cast<py::ssize_t>());
+		v.dt = py::dtype::from_args(d["typestr"]);
+		py::tuple data = d["data"];
+		v.ptr = reinterpret_cast<void*>(data[0].cast<uintptr_t>());
+		v.readonly = data[1].cast<bool>();
+		if (d.contains("strides") && !d["strides"].is_none())
+		{
+			py::ssize_t dense = v.dt.itemsize();
+			py::tuple st = d["strides"];
+			if (st.size() != v.shape.size()) throw py::value_error(std::string(what) + ": strides and shape disagree");
+			for (size_t k = v.shape.size(); k-- > 0;)
+			{
+				if (v.shape[k] != 1 && st[k].cast<py::ssize_t>() != dense) throw py::value_error(std::string(what) + ": the array is not C-contiguous");
+				dense *= v.shape[k];
+			}
+		}
+		if (v.count() > 0 && !v.ptr) throw py::value_error(std::string(what) + ": null device address");
+		return v;
+	}
+	void wait_for(const std::optional<uintptr_t>& stream)
+	{
+		if (stream) compressed::device_channel<uint8_t>::wait_stream(reinterpret_cast<void*>(*stream));
+	}
+
+	// Results with out=None: device memory from cimg_device_malloc, exposed through __cuda_array_interface__ (version 2), so that
+	// torch.as_tensor(r, device="cuda") wraps it without a copy (the tensor keeps this object alive).
+	struct DeviceArray
+	{
+		std::shared_ptr<void> mem;
+		std::vector<py::ssize_t> shape;
+		py::dtype dt;
+		size_t nbytes = 0;
+
+		DeviceArray(std::vector<py::ssize_t> shape_, py::dtype dt_) : shape(std::move(shape_)), dt(std::move(dt_))
+		{
+			nbytes = static_cast<size_t>(dt.itemsize());
+			for (auto d : shape) nbytes *= static_cast<size_t>(d);
+			cimg_engine* e = compressed::blosc2::batch::engine();
+			void* p = cimg_device_malloc(e, nbytes);
+			if (!p) throw std::runtime_error(std::string("Unable to allocate device memory: ") + cimg_last_error(e));
+			mem = std::shared_ptr<void>(p, [e](void* q) { cimg_device_free(e, q); });
+		}
+		py::dict interface() const
+		{
+			py::dict d;
+			d["version"] = 2;
+			d["shape"] = py::tuple(py::cast(shape));
+			d["typestr"] = dt.attr("str");
+			d["data"] = py::make_tuple(reinterpret_cast<uintptr_t>(mem.get()), false);
+			d["strides"] = py::none();
+			return d;
+		}
+		py::array copy_to_host() const
+		{
+			py::array out(dt, shape);
+			cimg_engine* e = compressed::blosc2::batch::engine();
+			if (nbytes && cimg_memcpy_d2h(e, out.mutable_data(), mem.get(), nbytes) < 0) throw std::runtime_error(cimg_last_error(e));
+			return out;
+		}
+	};
+
+	// where a result goes: the caller's `out` (checked: dtype, shape, writable, contiguous) or a new DeviceArray
+	template <typename T> std::pair<T*, py::object> result_target(const py::object& out, const std::vector<py::ssize_t>& shape, const char* what)
+	{
+		if (out.is_none())
+		{
+			DeviceArray a(shape, np_dtype<T>());
+			T* p = static_cast<T*>(a.mem.get());
+			return { p, py::cast(std::move(a)) };
+		}
+		const device_view v = view_of(out, what);
+		if (!v.dt.is(np_dtype<T>())) throw py::type_error(std::string(what) + ": out has dtype " + std::string(py::str(v.dt)) + ", expected " + dtype_code<T>());
+		if (v.shape != shape) throw py::value_error(std::string(what) + ": out has the wrong shape");
+		if (v.readonly) throw py::value_error(std::string(what) + ": out is read-only");
+		return { static_cast<T*>(v.ptr), out };
+	}
+	inline void check_region_args(py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h)
+	{
+		if (x < 0 || y < 0 || w < 0 || h < 0) throw py::value_error("region coordinates and sizes must be >= 0");
+	}
+
+	template <typename T> using dchan_ptr = std::shared_ptr<compressed::device_channel<T>>;
+	using any_dchannel = std::variant<dchan_ptr<compressed::half>, dchan_ptr<float>, dchan_ptr<double>, dchan_ptr<uint8_t>, dchan_ptr<int8_t>,
+		dchan_ptr<uint16_t>, dchan_ptr<int16_t>, dchan_ptr<uint32_t>, dchan_ptr<int32_t>>;
+
+	struct DeviceChannel
+	{
+		any_dchannel impl;
+		template <typename F> auto visit(F&& f) const { return std::visit([&](auto& p) { return f(*p); }, impl); }
+
+		static DeviceChannel from_array(const py::object& data, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk,
+			std::optional<uintptr_t> stream)
+		{
+			const device_view v = view_of(data, "DeviceChannel");
+			return dispatch(v.dt, [&]<typename T>() {
+				if (v.count() != width * height)
+					throw py::value_error("Channel data has " + std::to_string(v.count()) + " elements, expected width * height = " + std::to_string(width * height));
+				wait_for(stream);
+				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(static_cast<const T*>(v.ptr), width, height, c,
+					static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk) };
+			});
+		}
+		static DeviceChannel from_channel(const Channel& host)
+		{
+			return host.visit([]<typename T>(compressed::channel<T>& ch) {
+				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(compressed::device_channel<T>::from_channel(ch)) };
+			});
+		}
+		Channel to_channel() const
+		{
+			return visit([]<typename T>(compressed::device_channel<T>& ch) { return Channel{ std::make_shared<compressed::channel<T>>(ch.to_channel()) }; });
+		}
+		py::object get_decompressed(const py::object& out, std::optional<uintptr_t> stream) const
+		{
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				auto [p, ret] = result_target<T>(out, { static_cast<py::ssize_t>(ch.height()), static_cast<py::ssize_t>(ch.width()) }, "get_decompressed");
+				wait_for(stream);
+				ch.decompress_into(p);
+				return ret;
+			});
+		}
+		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, std::optional<uintptr_t> stream) const
+		{
+			check_region_args(x, y, width, height);
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				auto [p, ret] = result_target<T>(out, { height, width }, "get_region");
+				wait_for(stream);
+				ch.get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				return ret;
+			});
+		}
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream)
+		{
+			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			const device_view v = view_of(array, "set_region");
+			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				if (v.shape.size() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(v.shape.size()) + " dimensions");
+				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]));
+				wait_for(stream);
+				ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]));
+				return 0;
+			});
+		}
+	};
+
+	template <typename T> using dimg_ptr = std::shared_ptr<compressed::device_image<T>>;
+	using any_dimage = std::variant<dimg_ptr<compressed::half>, dimg_ptr<float>, dimg_ptr<double>, dimg_ptr<uint8_t>, dimg_ptr<int8_t>,
+		dimg_ptr<uint16_t>, dimg_ptr<int16_t>, dimg_ptr<uint32_t>, dimg_ptr<int32_t>>;
+
+	struct DeviceImage
+	{
+		any_dimage impl;
+		template <typename F> auto visit(F&& f) const { return std::visit([&](auto& p) { return f(p); }, impl); }
+
+		// channels: a list of (H, W) device arrays or one (C, H, W) device array
+		static DeviceImage from_arrays(const py::object& dtype, const py::object& channels, size_t width, size_t height, std::vector<std::string> names,
+			codec c, size_t level, size_t block, size_t chunk, std::optional<uintptr_t> stream)
+		{
+			const py::dtype dt = as_dtype(dtype);
+			std::vector<device_view> views;
+			if (py::isinstance<py::list>(channels) || py::isinstance<py::tuple>(channels))
+				for (auto o : channels) views.push_back(view_of(py::reinterpret_borrow<py::object>(o), "DeviceImage"));
+			else
+			{
+				device_view all = view_of(channels, "DeviceImage");
+				if (all.shape.size() != 3) throw py::value_error("DeviceImage: a single array must have the shape (channels, height, width)");
+				const size_t plane = static_cast<size_t>(all.shape[1] * all.shape[2]) * static_cast<size_t>(all.dt.itemsize());
+				for (py::ssize_t k = 0; k < all.shape[0]; ++k)
+				{
+					device_view v = all;
+					v.shape = { all.shape[1], all.shape[2] };
+					v.ptr = static_cast<char*>(all.ptr) + static_cast<size_t>(k) * plane;
+					views.push_back(v);
+				}
+			}
+			return DeviceImage{ dispatch(dt, [&]<typename T>() -> any_dimage {
+				std::vector<const T*> ptrs;
+				for (const auto& v : views)
+				{
+					if (!v.dt.is(np_dtype<T>())) throw py::value_error("channel dtype does not match the image dtype");
+					if (v.count() != width * height)
+						throw py::value_error("Invalid channel data passed. Expected its size to match up to width * height (" + std::to_string(width * height) + "), got " + std::to_string(v.count()));
+					ptrs.push_back(static_cast<const T*>(v.ptr));
+				}
+				wait_for(stream);
+				return std::make_shared<compressed::device_image<T>>(ptrs, width, height, std::move(names), c, level, block, chunk);
+			}) };
+		}
+		static DeviceImage from_interleaved(const py::object& array, std::vector<std::string> names, codec c, size_t level, size_t block, size_t chunk,
+			std::optional<uintptr_t> stream)
+		{
+			const device_view v = view_of(array, "from_interleaved");
+			if (v.shape.size() != 3) throw py::value_error("from_interleaved: expected an array of the shape (height, width, channels)");
+			return DeviceImage{ dispatch(v.dt, [&]<typename T>() -> any_dimage {
+				wait_for(stream);
+				return std::make_shared<compressed::device_image<T>>(compressed::device_image<T>::from_interleaved(static_cast<const T*>(v.ptr),
+					static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]), static_cast<size_t>(v.shape[2]), std::move(names), c, level, block, chunk));
+			}) };
+		}
+		static DeviceImage from_image(const Image& host)
+		{
+			return DeviceImage{ host.visit([]<typename T>(const img_ptr<T>& img) -> any_dimage {
+				return std::make_shared<compressed::device_image<T>>(compressed::device_image<T>::from_image(*img)); }) };
+		}
+		Image to_image() const
+		{
+			return visit([]<typename T>(const dimg_ptr<T>& img) { return Image(any_image(std::make_shared<compressed::image<T>>(img->to_image()))); });
+		}
+		DeviceChannel channel(const std::variant<std::string, size_t>& key) const
+		{
+			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(std::holds_alternative<size_t>(key) ? img->channel(std::get<size_t>(key))
+					: img->channel(std::string_view(std::get<std::string>(key)))) };
+			});
+		}
+		py::object get_decompressed(const py::object& out, std::optional<uintptr_t> stream) const
+		{
+			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+				auto [p, ret] = result_target<T>(out, { static_cast<py::ssize_t>(img->num_channels()), static_cast<py::ssize_t>(img->height()),
+					static_cast<py::ssize_t>(img->width()) }, "get_decompressed");
+				wait_for(stream);
+				img->decompress_into(p);
+				return ret;
+			});
+		}
+		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, bool interleaved,
+			std::optional<uintptr_t> stream) const
+		{
+			check_region_args(x, y, width, height);
+			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				const py::ssize_t C = static_cast<py::ssize_t>(img->num_channels());
+				auto [p, ret] = result_target<T>(out, interleaved ? std::vector<py::ssize_t>{ height, width, C } : std::vector<py::ssize_t>{ C, height, width }, "get_region");
+				wait_for(stream);
+				img->get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height), interleaved);
+				return ret;
+			});
+		}
+		// one (C, h, w) device array over the rectangle at (x, y) of every channel
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream)
+		{
+			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			const device_view v = view_of(array, "set_region");
+			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
+				if (v.shape.size() != 3 || static_cast<size_t>(v.shape[0]) != img->num_channels())
+					throw py::value_error("region arrays must have the shape (channels, height, width)");
+				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[2]), static_cast<size_t>(v.shape[1]));
+				wait_for(stream);
+				img->set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[2]), static_cast<size_t>(v.shape[1]));
+				return 0;
+			});
+		}
+	};
 }
 
 PYBIND11_MODULE(compressed_image, m)
@@ -406,4 +687,70 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("chunk_size", [](const Image& i) { return i.visit([](auto& img) { return img->chunk_size(); }); })
 		.def("set_metadata", [](Image& i, py::dict md) { i.metadata = std::move(md); }, py::arg("metadata"))
 		.def("get_metadata", [](const Image& i) { return i.metadata; });
+
+	py::class_<DeviceArray>(m, "DeviceArray", py::module_local())
+		.def_property_readonly("__cuda_array_interface__", &DeviceArray::interface)
+		.def_property_readonly("shape", [](const DeviceArray& a) { return py::tuple(py::cast(a.shape)); })
+		.def_property_readonly("dtype", [](const DeviceArray& a) { return a.dt; })
+		.def_property_readonly("nbytes", [](const DeviceArray& a) { return a.nbytes; })
+		.def("copy_to_host", &DeviceArray::copy_to_host);
+
+	py::class_<DeviceChannel>(m, "DeviceChannel", py::module_local())
+		.def(py::init(&DeviceChannel::from_array), py::arg("data"), py::arg("width"), py::arg("height"), py::arg("compression_codec") = codec::lz4,
+			py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt)
+		.def_static("from_channel", &DeviceChannel::from_channel, py::arg("channel"))
+		.def("to_channel", &DeviceChannel::to_channel)
+		.def_property_readonly("dtype", [](const DeviceChannel& c) { return c.visit([]<typename T>(compressed::device_channel<T>&) { return np_dtype<T>(); }); })
+		.def_property_readonly("shape", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return py::make_tuple(ch.height(), ch.width()); }); })
+		.def_property_readonly("width", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.width(); }); })
+		.def_property_readonly("height", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.height(); }); })
+		.def("block_size", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.block_size(); }); })
+		.def("chunk_size", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.chunk_size(); }); })
+		.def("chunk_size", [](const DeviceChannel& c, size_t i) { return c.visit([&](auto& ch) { return ch.chunk_size(i); }); }, py::arg("chunk_index"))
+		.def("chunk_elems", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.chunk_elems(); }); })
+		.def("chunk_elems", [](const DeviceChannel& c, size_t i) { return c.visit([&](auto& ch) { return ch.chunk_elems(i); }); }, py::arg("chunk_index"))
+		.def("compressed_bytes", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.compressed_bytes(); }); })
+		.def("compressed_bytes", [](const DeviceChannel& c, size_t i) { return c.visit([&](auto& ch) { return ch.compressed_bytes(i); }); }, py::arg("chunk_index"))
+		.def("uncompressed_size", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.uncompressed_size(); }); })
+		.def("num_chunks", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.num_chunks(); }); })
+		.def("compression", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.compression(); }); })
+		.def("compression_level", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return static_cast<size_t>(ch.compression_level()); }); })
+		.def("device_bytes", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.device_bytes(); }); })
+		.def("read_only", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.read_only(); }); })
+		.def("get_decompressed", &DeviceChannel::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
+		.def("get_region", &DeviceChannel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
+			py::arg("stream") = std::nullopt)
+		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt);
+
+	py::class_<DeviceImage>(m, "DeviceImage", py::module_local())
+		.def(py::init(&DeviceImage::from_arrays), py::arg("dtype"), py::arg("channels"), py::arg("width"), py::arg("height"),
+			py::arg("channel_names") = std::vector<std::string>{}, py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9,
+			py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt)
+		.def_static("from_interleaved", &DeviceImage::from_interleaved, py::arg("array"), py::arg("channel_names") = std::vector<std::string>{},
+			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk,
+			py::arg("stream") = std::nullopt)
+		.def_static("from_image", &DeviceImage::from_image, py::arg("image"))
+		.def("to_image", &DeviceImage::to_image)
+		.def("__getitem__", &DeviceImage::channel, py::arg("key"))
+		.def("__len__", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->num_channels(); }); })
+		.def("channel", &DeviceImage::channel, py::arg("key"))
+		.def("get_decompressed", &DeviceImage::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
+		.def("get_region", &DeviceImage::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
+			py::arg("interleaved") = false, py::arg("stream") = std::nullopt)
+		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt)
+		.def("get_channel_index", [](const DeviceImage& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
+		.def("get_channel_names", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->channelnames(); }); })
+		.def("set_channel_names", [](DeviceImage& i, std::vector<std::string> names) { i.visit([&](auto& img) { img->channelnames(std::move(names)); return 0; }); }, py::arg("channel_names"))
+		.def("compression_ratio", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->compression_ratio(); }); })
+		.def_property_readonly("dtype", [](const DeviceImage& i) { return i.visit([]<typename T>(const dimg_ptr<T>&) { return np_dtype<T>(); }); })
+		.def_property_readonly("shape", [](const DeviceImage& i) { return i.visit([](auto& img) { return py::make_tuple(img->num_channels(), img->height(), img->width()); }); })
+		.def_property_readonly("width", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->width(); }); })
+		.def_property_readonly("height", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->height(); }); })
+		.def_property_readonly("num_channels", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->num_channels(); }); })
+		.def("block_size", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->block_size(); }); })
+		.def("chunk_size", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->chunk_size(); }); })
+		.def("compressed_bytes", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->compressed_bytes(); }); })
+		.def("uncompressed_size", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->uncompressed_size(); }); })
+		.def("num_chunks", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->num_chunks(); }); })
+		.def("device_bytes", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->device_bytes(); }); });
 }

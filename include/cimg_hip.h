@@ -232,6 +232,40 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole,
                               int64_t* bytes_uploaded);
 
+/* ---- packed device storage: what an object that keeps an image compressed in device memory is made of ----------------
+ * cimg_compress_batch_device gives chunk i room for destsize[i], so a plane that compresses 2 : 1 still occupies its full size.
+ * The pair below is shaped like cimg_compress_batch_host_begin / _fetch with pixels AND destination on the device: _begin
+ * compresses into the engine's device staging area and reports cbytes[]; the caller allocates exactly what it needs and _fetch
+ * moves chunk i (cbytes[i] bytes; nothing for a chunk that did not fit) to d_dst + dst_off[i] with one launch of the pack kernel.
+ * The chunk bytes are those cimg_compress_batch_device writes for the same input and parameters.  _fetch refers to the most recent
+ * _begin (of this kind or of the host kind: both leave their chunks in the same staging area); any other batch call that reuses the
+ * staging area (the host-resident calls) voids it, and _fetch then fails with BLOSC2_ERROR_INVALID_PARAM.  Both return after the
+ * engine's stream has been synchronised. */
+int cimg_compress_batch_device_packed_begin(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
+                                            const void* d_raw, const int64_t* raw_off, const int32_t* nbytes, const int32_t* destsize,
+                                            int32_t* cbytes);
+int cimg_compress_batch_device_packed_fetch(cimg_engine* e, int32_t nchunks, void* d_dst, const int64_t* dst_off);
+/* The pack kernel on its own: a batched gather copy.  Piece i is bytes[i] bytes at the device address d_src[i] (d_src[] is a HOST
+ * array of device addresses) and goes to d_dst + dst_off[i]; any alignment of either; bytes[i] == 0 pieces are skipped.  One launch
+ * whatever the sizes: the work is cut into 16 KiB tiles, so the time follows the total bytes.  No destination range may overlap a
+ * source range or another destination range of the call (checked on the host: BLOSC2_ERROR_INVALID_PARAM, nothing runs).  Returns
+ * after the engine's stream has been synchronised. */
+int cimg_pack_chunks_device(cimg_engine* e, int32_t nchunks, const void* const* d_src, const int32_t* bytes,
+                            void* d_dst, const int64_t* dst_off);
+/* Planes -> interleaved pixels: the inverse of cimg_deinterleave_device, same argument meaning and constraints (typesize 1, 2, 4
+ * or 8; both buffers 16-byte aligned; plane_stride in bytes, a multiple of 16, at least npixels * typesize).  Returns after the
+ * engine's stream has been synchronised. */
+int cimg_interleave_device(cimg_engine* e, const void* d_planar, int64_t plane_stride, int32_t nchannels,
+                           int32_t typesize, int64_t npixels, void* d_interleaved);
+/* Records an event on `stream` (a hipStream_t; NULL: the null stream) and makes the engine's stream wait for it: pixels produced
+ * on the caller's stream before this call are seen by the next batch.  (Results need no counterpart: the device calls of this
+ * section, the window calls and the plain batch calls return after the engine's stream has been synchronised.) */
+int cimg_engine_wait_stream(cimg_engine* e, void* stream);
+/* 0 only if [p, p + bytes) is device memory of the engine's device and lies inside one allocation (a sub-range of a larger
+ * allocation is fine); else BLOSC2_ERROR_INVALID_PARAM and a message.  Nothing is launched.  For layers that take addresses from
+ * their callers: a host pointer handed to a kernel is a GPU fault, so they ask here first. */
+int cimg_device_range_check(cimg_engine* e, const void* p, size_t bytes);
+
 /* ---- glue between the blosc2 shim and the batched calls ----------------------------------------------
  * The single-chunk blosc2_*_ctx calls run on one process-wide engine (device $CIMG_DEVICE, else the
  * current HIP device); cimg_shared_engine() hands it out so that host code holding blosc2 contexts
@@ -266,7 +300,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* the window launch of cimg_decompress_windows_device / _host */
        CIMG_K_DECODE_WINDOW = 16,
        /* window writes: stage-and-patch, splice layout, splice copy */
-       CIMG_K_UPDATE_PATCH = 17, CIMG_K_UPDATE_LAYOUT = 18, CIMG_K_UPDATE_EMIT = 19, CIMG_K_COUNT = 20 };
+       CIMG_K_UPDATE_PATCH = 17, CIMG_K_UPDATE_LAYOUT = 18, CIMG_K_UPDATE_EMIT = 19,
+       /* packed device storage: the batched gather copy, planes -> interleaved pixels */
+       CIMG_K_PACK = 20, CIMG_K_INTERLEAVE = 21, CIMG_K_COUNT = 22 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);
