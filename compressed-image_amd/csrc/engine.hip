@@ -1239,16 +1239,9 @@ static int decompress_launch_wide(cimg_engine* e, const WideDecodePlan& wp, int3
     (void)nchunks;
     int rc = 0;
     if (!wp.normal.empty()) {
-        const size_t nn = wp.normal.size();
-        std::vector<int64_t> co(nn), ro(nn);
-        std::vector<int32_t> nb(nn), bs(nn), cs(comp_size ? nn : 0);
-        for (size_t k = 0; k < nn; k++) {
-            const int i = wp.normal[k];
-            co[k] = comp_off[i]; ro[k] = raw_off[i]; nb[k] = nbytes[i]; bs[k] = blocksize[i];
-            if (comp_size) cs[k] = comp_size[i];
-        }
-        if ((rc = decompress_launch(e, (int32_t)nn, d_comp, co.data(), nb.data(), bs.data(), d_raw, ro.data(),
-                                    comp_size ? cs.data() : nullptr, inputs_behind_stream))) return rc;
+        const SubBatch sub(wp.normal, comp_off, comp_size, nbytes, blocksize, raw_off);
+        if ((rc = decompress_launch(e, (int32_t)wp.normal.size(), d_comp, sub.co.data(), sub.nb.data(), sub.bs.data(), d_raw, sub.ro.data(),
+                                    comp_size ? sub.cs.data() : nullptr, inputs_behind_stream))) return rc;
     }
     const int nw = (int)wp.wide.size();
     const DecodePlan& plan = wp.plan;
@@ -2023,37 +2016,32 @@ static_assert(sizeof(cimg_window) == sizeof(WindowSpec) && offsetof(cimg_window,
 
 namespace {
 
-// run_windows' device side: chunks decoded whole go through the batch path into win_whole, the window launch runs on the stream
-struct EngineWindowEnv {
+// the batch a window call runs on, and the step run_windows and run_update share: chunks decoded whole go through the batch path
+// into win_whole
+struct EngineChunks {
     cimg_engine* e;
     const uint8_t* d_comp;
     const int64_t* comp_off;
     const int32_t* comp_size;          // may be null
     const int32_t* nbytes;
     const int32_t* blocksize;
-    uint8_t* d_out;
-    int32_t typesize;                  // 0: the host checked every header's typesize already
 
     int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
     {
         int rc;
         if ((rc = e->reserve(e->win_whole, (size_t)total + 64))) return rc;
-        const size_t n = list.size();
-        std::vector<int64_t> co(n);
-        std::vector<int32_t> cs(n), nb(n), bs(n);
-        for (size_t k = 0; k < n; k++) {
-            const int i = list[k];
-            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
-        }
-        rc = cimg_decompress_batch_device_sized(e, (int32_t)n, d_comp, co.data(), cs.data(), nb.data(), bs.data(), e->win_whole.p,
-                                                dst_off.data(), st);
-        if (rc < 0) {                  // refused before any chunk had a status of its own: it is every listed chunk's
-            bool any = false;
-            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
-            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
-        }
+        const SubBatch sub(list, comp_off, comp_size, nbytes, blocksize);
+        rc = cimg_decompress_batch_device_sized(e, (int32_t)list.size(), d_comp, sub.co.data(), sub.cs.data(), sub.nb.data(), sub.bs.data(),
+                                                e->win_whole.p, dst_off.data(), st);
+        spread_refusal(rc, list.size(), st);
         return 0;
     }
+};
+
+// run_windows' device side: the window launch runs on the stream
+struct EngineWindowEnv : EngineChunks {
+    uint8_t* d_out;
+    int32_t typesize;                  // 0: the host checked every header's typesize already
 
     int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
     {
@@ -2093,16 +2081,41 @@ struct EngineWindowEnv {
     }
 };
 
+int invalid_window(cimg_engine* e)
+{
+    return e->fail(ERR_INVALID_PARAM, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
+                                      "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
+}
+
+// the text of a call refused at its opening (open_window_call, open_update_call) or by read_named_headers
+int open_fail(cimg_engine* e, int32_t nchunks, int32_t nwindows)
+{
+    return e->fail(ERR_INVALID_PARAM, nchunks < 0 || nwindows < 0 ? "negative chunk or window count" : "a window needs chunks");
+}
+int named_fail(cimg_engine* e, int rc, const HostCallPlan& hp, int32_t nchunks, const cimg_window* w, const int32_t* comp_size)
+{
+    const int k = hp.bad_window, i = hp.short_chunk;
+    if (k >= 0) return e->fail(rc, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
+    return e->fail(rc, "chunk %d: %d bytes cannot hold a header", i, comp_size[i]);
+}
+
+// a window's rows between its packed form on the device and the caller's pitch: one copy where the two pitches agree
+int copy_rows(cimg_engine* e, void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch, int64_t row, int32_t height, hipMemcpyKind kind,
+              const char* what)
+{
+    if (dst_pitch == src_pitch || height == 1) return e->hip(hipMemcpyAsync(dst, src, (size_t)(row * height), kind, e->stream), what);
+    return e->hip(hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)row, (size_t)height, kind, e->stream), what);
+}
+
 int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
                 const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int32_t check_ts, const std::vector<uint8_t>& hint,
-                int32_t nwindows, const cimg_window* w, void* d_out, int32_t* status)
+                int32_t nwindows, const WindowSpec* w, void* d_out, int32_t* status)
 {
-    EngineWindowEnv env{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize, (uint8_t*)d_out, check_ts};
+    EngineWindowEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, (uint8_t*)d_out, check_ts};
     WindowStats st;
-    const int rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, reinterpret_cast<const WindowSpec*>(w), hint, status, &st);
+    const int rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
     e->win_stats = st;
-    if (rc == ERR_INVALID_PARAM) return e->fail(rc, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
-                                                    "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
+    if (rc == ERR_INVALID_PARAM) return invalid_window(e);
     if (rc < 0) {
         for (int i = 0; i < nchunks; i++) if (status[i] == rc) return e->fail(rc, "chunk %d failed to decode (code %d)", i, rc);
     }
@@ -2119,15 +2132,15 @@ int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* 
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->win_stats = WindowStats{};
-    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
-    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (nwindows == 0 || nchunks == 0) return nwindows == 0 ? 0 : e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    int rc = open_window_call(nchunks, nwindows, status);
+    if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
     if (!w || !comp_off || !nbytes || !blocksize || !status || !d_comp || !d_out) return e->fail(ERR_INVALID_PARAM, "null argument");
     if (typesize <= 0 || typesize > 255) return e->fail(ERR_INVALID_PARAM, "typesize %d", typesize);
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     std::vector<int32_t> ts((size_t)nchunks, typesize);
-    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows, w, d_out, status);
+    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows,
+                       reinterpret_cast<const WindowSpec*>(w), d_out, status);
 }
 
 int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
@@ -2135,89 +2148,39 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->win_stats = WindowStats{};
-    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
-    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (nwindows == 0 || nchunks == 0) return nwindows == 0 ? 0 : e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    int rc = open_window_call(nchunks, nwindows, status);
+    if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
     if (!w || !comp_off || !status || !h_comp || !h_out) return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
     const uint8_t* hc = (const uint8_t*)h_comp;
-    // the headers of the chunks the windows name (the geometry of their planes); the others are not looked at
-    std::vector<uint8_t> named((size_t)nchunks, 0), hint((size_t)nchunks, 0);
-    for (int k = 0; k < nwindows; k++) {
-        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count)
-            return e->fail(ERR_INVALID_PARAM, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
-        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
+    WindowHostPlan hp;
+    if ((rc = plan_windows_host(nchunks, hc, comp_off, comp_size, nwindows, reinterpret_cast<const WindowSpec*>(w), status, &hp)) < 0) {
+        if (hp.bad_window >= 0 || hp.short_chunk >= 0) return named_fail(e, rc, hp, nchunks, w, comp_size);
+        if (hp.bad_chunk >= 0) return e->fail(rc, "chunk %d: invalid header (code %d)", hp.bad_chunk, rc);
+        return rc == ERR_INVALID_PARAM ? invalid_window(e) : e->fail(rc, "invalid chunk header among the windows' chunks");
     }
-    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), ts((size_t)nchunks, 0), cb((size_t)nchunks, 0);
-    std::vector<int> flags((size_t)nchunks, 0), version((size_t)nchunks, 0);
-    for (int i = 0; i < nchunks; i++) {
-        if (!named[(size_t)i]) continue;
-        if (comp_size && comp_size[i] < HEADER_LEN) return e->fail(ERR_READ_BUFFER, "chunk %d: %d bytes cannot hold a header", i, comp_size[i]);
-        const uint8_t* c = hc + comp_off[i];
-        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
-        ts[(size_t)i] = c[OFF_TYPESIZE];
-        flags[(size_t)i] = c[OFF_FLAGS];
-        version[(size_t)i] = c[0];
-        hint[(size_t)i] = (flags[(size_t)i] >> 5) == 4 && !(flags[(size_t)i] & FLAG_MEMCPYED);   // zstd: decoded whole
-    }
-    WindowPlan plan;
-    int rc = plan_windows(nchunks, nb.data(), bs.data(), ts.data(), nwindows, reinterpret_cast<const WindowSpec*>(w), hint.data(), &plan);
-    if (rc == ERR_INVALID_PARAM) return e->fail(rc, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
-                                                    "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
-    if (rc < 0) return e->fail(rc, "invalid chunk header among the windows' chunks");
-    // the chunks some window row meets: full header checks, then only they go over PCIe
-    std::vector<int64_t> d_comp_off((size_t)nchunks, 0);
-    std::vector<int32_t> up((size_t)nchunks, 0);
-    int64_t comp_total = 0;
-    for (int i = 0; i < nchunks; i++) {
-        if (!plan.touched[(size_t)i]) continue;
-        int code = 0;
-        if (version[(size_t)i] > 5) code = ERR_VERSION_SUPPORT;
-        else if (cb[(size_t)i] < HEADER_LEN) code = ERR_INVALID_HEADER;
-        else if (comp_size && cb[(size_t)i] > comp_size[i]) code = ERR_READ_BUFFER;
-        if (code) { status[i] = code; return e->fail(code, "chunk %d: invalid header (code %d)", i, code); }
-        d_comp_off[(size_t)i] = comp_total;
-        up[(size_t)i] = cb[(size_t)i];
-        comp_total += ((int64_t)cb[(size_t)i] + 63) & ~63ll;
-    }
-    // the windows come back packed (row after row), and go to h_out at the callers' pitches
-    std::vector<cimg_window> dw(w, w + nwindows);
-    std::vector<int64_t> wbytes((size_t)nwindows, 0);
-    int64_t out_total = 0;
-    for (int k = 0; k < nwindows; k++) {
-        if (w[k].width == 0 || w[k].height == 0) continue;
-        const int64_t row = (int64_t)w[k].width * ts[(size_t)w[k].chunk_first];
-        dw[(size_t)k].out_off = out_total;
-        dw[(size_t)k].out_pitch = row;
-        wbytes[(size_t)k] = row * w[k].height;
-        out_total += (wbytes[(size_t)k] + 255) & ~255ll;
-    }
-    if ((rc = e->reserve(e->stage_comp, (size_t)comp_total + 64))) return rc;
-    if ((rc = e->reserve(e->win_out, (size_t)out_total + 64))) return rc;
+    // only the chunks some window row meets go over PCIe; the windows come back packed, and go to h_out at the callers' pitches
+    if ((rc = e->reserve(e->stage_comp, (size_t)hp.comp_total + 64))) return rc;
+    if ((rc = e->reserve(e->win_out, (size_t)hp.rows_total + 64))) return rc;
     uint8_t* sc = (uint8_t*)e->stage_comp.p;
     uint8_t* so = (uint8_t*)e->win_out.p;
     {
-        HostPin pin_in(e, h_comp, comp_off, up.data(), nchunks, false);
-        if ((rc = copy_in(e, e->stream, sc, d_comp_off.data(), hc, comp_off, up.data(), 0, nchunks, "chunk H2D"))) return rc;
-        if ((rc = e->hip(hipMemsetAsync(so, 0, (size_t)out_total, e->stream), "window memset"))) return rc;
-        rc = windows_run(e, nchunks, sc, d_comp_off.data(), cb.data(), nb.data(), bs.data(), ts.data(), 0, hint, nwindows, dw.data(), so, status);
+        HostPin pin_in(e, h_comp, comp_off, hp.up.data(), nchunks, false);
+        if ((rc = copy_in(e, e->stream, sc, hp.d_comp_off.data(), hc, comp_off, hp.up.data(), 0, nchunks, "chunk H2D"))) return rc;
+        if ((rc = e->hip(hipMemsetAsync(so, 0, (size_t)hp.rows_total, e->stream), "window memset"))) return rc;
+        rc = windows_run(e, nchunks, sc, hp.d_comp_off.data(), hp.cbytes.data(), hp.nbytes.data(), hp.blocksize.data(), hp.typesize.data(), 0,
+                         hp.hint, nwindows, hp.dw.data(), so, status);
     }
-    e->win_stats.comp_bytes_uploaded = 0;
-    for (int i = 0; i < nchunks; i++) e->win_stats.comp_bytes_uploaded += up[(size_t)i];
+    e->win_stats.comp_bytes_uploaded = hp.comp_bytes_uploaded;
     if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return rc;
     const std::string chunk_error = e->err;
     uint8_t* ho = (uint8_t*)h_out;
     for (int k = 0; k < nwindows; k++) {
-        if (!wbytes[(size_t)k]) continue;
-        const int64_t row = dw[(size_t)k].out_pitch;
-        int crc;
-        if (w[k].out_pitch == row || w[k].height == 1)
-            crc = e->hip(hipMemcpyAsync(ho + w[k].out_off, so + dw[(size_t)k].out_off, (size_t)wbytes[(size_t)k], hipMemcpyDeviceToHost, e->stream), "window D2H");
-        else
-            crc = e->hip(hipMemcpy2DAsync(ho + w[k].out_off, (size_t)w[k].out_pitch, so + dw[(size_t)k].out_off, (size_t)row, (size_t)row,
-                                          (size_t)w[k].height, hipMemcpyDeviceToHost, e->stream), "window D2H");
+        const WindowSpec& d = hp.dw[(size_t)k];
+        if (!hp.wbytes[(size_t)k]) continue;
+        const int crc = copy_rows(e, ho + w[k].out_off, w[k].out_pitch, so + d.out_off, d.out_pitch, d.out_pitch, w[k].height, hipMemcpyDeviceToHost, "window D2H");
         if (crc) { (void)cimg_engine_synchronize(e); return crc; }
     }
     int src;
@@ -2240,14 +2203,8 @@ void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* 
 namespace {
 
 // run_update's device side.  Every step ends in a stream synchronize: the planner reads its results on the host.
-struct EngineUpdateEnv {
-    cimg_engine* e;
+struct EngineUpdateEnv : EngineChunks {
     const cimg_cparams* p;
-    const uint8_t* d_comp;
-    const int64_t* comp_off;
-    const int32_t* comp_size;          // may be null
-    const int32_t* nbytes;
-    const int32_t* blocksize;
     const uint8_t* d_src;
     uint8_t* d_new;
     const uint8_t* h_comp;             // host call: the headers are read here, at h_off
@@ -2277,27 +2234,6 @@ struct EngineUpdateEnv {
                              "header D2H"))) { (void)cimg_engine_synchronize(e); return rc; }
         if ((rc = e->hip(hipStreamSynchronize(e->stream), "header D2H"))) return rc;
         memcpy(out, h, bytes);
-        return 0;
-    }
-
-    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
-    {
-        int rc;
-        if ((rc = e->reserve(e->win_whole, (size_t)total + 64))) return rc;
-        const size_t n = list.size();
-        std::vector<int64_t> co(n);
-        std::vector<int32_t> cs(n), nb(n), bs(n);
-        for (size_t k = 0; k < n; k++) {
-            const int i = list[k];
-            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
-        }
-        rc = cimg_decompress_batch_device_sized(e, (int32_t)n, d_comp, co.data(), cs.data(), nb.data(), bs.data(), e->win_whole.p,
-                                                dst_off.data(), st);
-        if (rc < 0) {
-            bool any = false;
-            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
-            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
-        }
         return 0;
     }
 
@@ -2386,19 +2322,17 @@ int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nc
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
-    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
-    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (new_cbytes) for (int i = 0; i < nchunks; i++) new_cbytes[i] = 0;
-    if (nwindows == 0) return 0;
+    int rc = open_update_call(nchunks, nwindows, status, new_cbytes, nullptr);
+    if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
     if (!p || !w || !comp_off || !nbytes || !blocksize || !destsize || !status || !new_cbytes || !new_off || !d_comp || !d_src || !d_new)
         return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     e->cflight_chunks = -1;
-    EngineUpdateEnv env{e, p, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr};
+    EngineUpdateEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, p, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr};
     UpdateStats st;
-    const int rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
-                              reinterpret_cast<const WindowSpec*>(w), new_off, new_cbytes, status, &st);
+    rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
+                    reinterpret_cast<const WindowSpec*>(w), new_off, new_cbytes, status, &st);
     e->upd_stats = st;
     return update_result(e, rc, nchunks, status);
 }
@@ -2409,91 +2343,42 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
-    if (nchunks < 0 || nwindows < 0) return e->fail(ERR_INVALID_PARAM, "negative chunk or window count");
-    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (new_cbytes) for (int i = 0; i < nchunks; i++) new_cbytes[i] = 0;
-    if (new_chunks) for (int i = 0; i < nchunks; i++) new_chunks[i] = nullptr;
-    if (nwindows == 0) return 0;
+    int rc = open_update_call(nchunks, nwindows, status, new_cbytes, new_chunks);
+    if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
     if (!p || !w || !comp_off || !destsize || !status || !new_cbytes || !new_chunks || !h_comp || !h_src || !alloc)
         return e->fail(ERR_INVALID_PARAM, "null argument");
-    if (nchunks == 0) return e->fail(ERR_INVALID_PARAM, "a window needs chunks");
+    if (nchunks == 0) return open_fail(e, nchunks, nwindows);
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     e->cflight_chunks = -1;
     e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
     const uint8_t* hc = (const uint8_t*)h_comp;
-    // the headers of the chunks the windows name (the geometry of their planes); the others are not looked at
-    std::vector<uint8_t> named((size_t)nchunks, 0);
-    for (int k = 0; k < nwindows; k++) {
-        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count)
-            return e->fail(ERR_INVALID_PARAM, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
-        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
-    }
-    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), cb((size_t)nchunks, 0);
-    for (int i = 0; i < nchunks; i++) {
-        if (!named[(size_t)i]) continue;
-        if (comp_size && comp_size[i] < HEADER_LEN) { status[i] = ERR_READ_BUFFER; return e->fail(ERR_READ_BUFFER, "chunk %d: %d bytes cannot hold a header", i, comp_size[i]); }
-        const uint8_t* c = hc + comp_off[i];
-        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
-    }
-    const int ts = p->typesize > 255 ? 1 : (p->typesize > 0 ? p->typesize : 1);
-    const std::vector<int32_t> tsv((size_t)nchunks, ts);
-    WindowPlan plan;
-    if (p->typesize <= 0 || plan_windows(nchunks, nb.data(), bs.data(), tsv.data(), nwindows, reinterpret_cast<const WindowSpec*>(w), nullptr, &plan) < 0)
-        return update_result(e, ERR_INVALID_PARAM, nchunks, status);
-    // only the touched chunks go up (a header that claims more than the buffer holds is the chunk's error, found by run_update)
-    std::vector<int64_t> d_comp_off((size_t)nchunks, 0), new_off((size_t)nchunks, 0);
-    std::vector<int32_t> up((size_t)nchunks, 0), held((size_t)nchunks, 0);
-    int64_t comp_total = 0, new_total = 0;
-    for (int i = 0; i < nchunks; i++) {
-        held[(size_t)i] = comp_size ? comp_size[i] : cb[(size_t)i];
-        if (!plan.touched[(size_t)i]) continue;
-        d_comp_off[(size_t)i] = comp_total;
-        up[(size_t)i] = std::max((int32_t)HEADER_LEN, std::min(cb[(size_t)i], held[(size_t)i]));
-        comp_total += ((int64_t)up[(size_t)i] + 63) & ~63ll;
-        new_off[(size_t)i] = new_total;
-        new_total += ((int64_t)std::max(destsize[i], 0) + 63) & ~63ll;
-    }
-    // the windows' rows go up packed (row after row)
-    std::vector<cimg_window> dw(w, w + nwindows);
-    std::vector<int64_t> wbytes((size_t)nwindows, 0);
-    int64_t src_total = 0;
-    for (int k = 0; k < nwindows; k++) {
-        if (w[k].width <= 0 || w[k].height <= 0) continue;
-        const int64_t row = (int64_t)w[k].width * ts;
-        dw[(size_t)k].out_off = src_total;
-        dw[(size_t)k].out_pitch = row;
-        wbytes[(size_t)k] = row * w[k].height;
-        src_total += (wbytes[(size_t)k] + 255) & ~255ll;
-    }
-    int rc;
-    if ((rc = e->reserve(e->stage_comp, (size_t)comp_total + 64))) return rc;
-    if ((rc = e->reserve(e->upd_src, (size_t)src_total + 64))) return rc;
-    if ((rc = e->reserve(e->upd_new, (size_t)new_total + 64))) return rc;
+    UpdateHostPlan hp;
+    if ((rc = plan_update_host(p->typesize, nchunks, hc, comp_off, comp_size, destsize, nwindows, reinterpret_cast<const WindowSpec*>(w), status, &hp)) < 0)
+        return hp.bad_window >= 0 || hp.short_chunk >= 0 ? named_fail(e, rc, hp, nchunks, w, comp_size) : update_result(e, rc, nchunks, status);
+    // only the touched chunks go up, and the windows' rows go up packed
+    if ((rc = e->reserve(e->stage_comp, (size_t)hp.comp_total + 64))) return rc;
+    if ((rc = e->reserve(e->upd_src, (size_t)hp.rows_total + 64))) return rc;
+    if ((rc = e->reserve(e->upd_new, (size_t)hp.new_total + 64))) return rc;
     uint8_t* sc = (uint8_t*)e->stage_comp.p;
     uint8_t* ss = (uint8_t*)e->upd_src.p;
     const uint8_t* hs = (const uint8_t*)h_src;
     {
-        HostPin pin_in(e, h_comp, comp_off, up.data(), nchunks, false);
-        if ((rc = copy_in(e, e->stream, sc, d_comp_off.data(), hc, comp_off, up.data(), 0, nchunks, "chunk H2D"))) return rc;
+        HostPin pin_in(e, h_comp, comp_off, hp.up.data(), nchunks, false);
+        if ((rc = copy_in(e, e->stream, sc, hp.d_comp_off.data(), hc, comp_off, hp.up.data(), 0, nchunks, "chunk H2D"))) return rc;
         for (int k = 0; k < nwindows; k++) {
-            if (!wbytes[(size_t)k]) continue;
-            const int64_t row = dw[(size_t)k].out_pitch;
-            if (w[k].out_pitch == row || w[k].height == 1)
-                rc = e->hip(hipMemcpyAsync(ss + dw[(size_t)k].out_off, hs + w[k].out_off, (size_t)wbytes[(size_t)k], hipMemcpyHostToDevice, e->stream), "window H2D");
-            else
-                rc = e->hip(hipMemcpy2DAsync(ss + dw[(size_t)k].out_off, (size_t)row, hs + w[k].out_off, (size_t)w[k].out_pitch, (size_t)row,
-                                             (size_t)w[k].height, hipMemcpyHostToDevice, e->stream), "window H2D");
+            const WindowSpec& d = hp.dw[(size_t)k];
+            if (!hp.wbytes[(size_t)k]) continue;
+            rc = copy_rows(e, ss + d.out_off, d.out_pitch, hs + w[k].out_off, w[k].out_pitch, d.out_pitch, w[k].height, hipMemcpyHostToDevice, "window H2D");
             if (rc) { (void)cimg_engine_synchronize(e); return rc; }
         }
-        EngineUpdateEnv env{e, p, sc, d_comp_off.data(), held.data(), nb.data(), bs.data(), ss, (uint8_t*)e->upd_new.p, hc, comp_off};
+        EngineUpdateEnv env{{e, sc, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data()}, p, ss, (uint8_t*)e->upd_new.p, hc, comp_off};
         UpdateStats st;
-        rc = run_update(env, to_host(p), nchunks, d_comp_off.data(), held.data(), nb.data(), bs.data(), destsize, nwindows,
-                        reinterpret_cast<const WindowSpec*>(dw.data()), new_off.data(), new_cbytes, status, &st);
+        rc = run_update(env, to_host(p), nchunks, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data(), destsize, nwindows,
+                        hp.dw.data(), hp.new_off.data(), new_cbytes, status, &st);
         e->upd_stats = st;
     }
-    for (int i = 0; i < nchunks; i++) e->upd_stats.bytes_uploaded += up[(size_t)i];
-    for (int k = 0; k < nwindows; k++) e->upd_stats.bytes_uploaded += wbytes[(size_t)k];
+    e->upd_stats.bytes_uploaded += hp.bytes_uploaded;
     if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return update_result(e, rc, nchunks, status);
     const std::string chunk_error = e->err;
     // the new chunks come back into memory from `alloc`
@@ -2502,7 +2387,7 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
         void* m = alloc(user, (size_t)new_cbytes[i]);
         if (!m) { (void)cimg_engine_synchronize(e); return e->fail(-4, "alloc returned NULL for %d bytes", new_cbytes[i]); }
         new_chunks[i] = m;
-        int crc = e->hip(hipMemcpyAsync(m, (uint8_t*)e->upd_new.p + new_off[(size_t)i], (size_t)new_cbytes[i], hipMemcpyDeviceToHost, e->stream), "chunk D2H");
+        int crc = e->hip(hipMemcpyAsync(m, (uint8_t*)e->upd_new.p + hp.new_off[(size_t)i], (size_t)new_cbytes[i], hipMemcpyDeviceToHost, e->stream), "chunk D2H");
         if (crc) { (void)cimg_engine_synchronize(e); return crc; }
     }
     int src;

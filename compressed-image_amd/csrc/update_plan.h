@@ -8,6 +8,9 @@
 //           assembly behind it), and spliced with the old streams of the untouched blocks (cimg_update_layout + cimg_update_emit).
 //   whole   everything else (zstd, wide blocks, memcpyed or special-zero chunks, a chunk whose new form clipped at an old coded stream
 //           or fell back to memcpyed): decoded whole through the batch path, patched in place, compressed through the batch path.
+//
+// The host-buffer call (cimg_update_windows_host) is planned here for the engine and the emulator alike: open_update_call (the opening
+// of both write calls) and plan_update_host, over window_plan.h's read_named_headers, stage_chunk and pack_rows.
 #pragma once
 #include "plan.h"
 #include "window_plan.h"
@@ -263,6 +266,55 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
         }
     }
     for (int i = 0; i < nchunks; i++) if (status[i] != 0) return status[i];
+    return 0;
+}
+
+// ---- the host-buffer call: what is decided before anything is staged -------------------------------------------------------------
+
+// The opening of a write call (new_chunks: the host call's): < 0 refused, CALL_DONE nothing to do, 0 go on.  Chunks are asked for
+// later: by the host call once its pointers are known to be good, by run_update for the device call.
+inline int open_update_call(int nchunks, int nwindows, int32_t* status, int32_t* new_cbytes, void** new_chunks)
+{
+    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (new_cbytes) for (int i = 0; i < nchunks; i++) new_cbytes[i] = 0;
+    if (new_chunks) for (int i = 0; i < nchunks; i++) new_chunks[i] = nullptr;
+    return nwindows == 0 ? CALL_DONE : 0;
+}
+
+struct UpdateHostPlan : HostCallPlan {
+    std::vector<int32_t> held;          // the bytes the caller holds of each chunk: comp_size, or what the header says
+    std::vector<int64_t> new_off;       // the touched chunks' new forms, in 64-byte slots of destsize each
+    int64_t new_total = 0, new_used = 0, bytes_uploaded = 0;
+};
+
+// cimg_update_windows_host: only the touched chunks go up, and a header that claims more than the buffer holds is the chunk's
+// own error, found by run_update (hence `up`: what is there to copy, a header at least).  ERR_INVALID_PARAM with bad_window < 0:
+// the typesize or a window was refused.
+inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size,
+                            const int32_t* destsize, int nwindows, const WindowSpec* w, int32_t* status, UpdateHostPlan* hp)
+{
+    const int rc = read_named_headers(nchunks, comp, comp_off, comp_size, nwindows, w, hp);
+    if (hp->short_chunk >= 0) status[hp->short_chunk] = rc;
+    if (rc < 0) return rc;
+    if (typesize <= 0) return ERR_INVALID_PARAM;
+    const std::vector<int32_t> tsv((size_t)nchunks, typesize > 255 ? 1 : typesize);
+    WindowPlan plan;
+    if (plan_windows(nchunks, hp->nbytes.data(), hp->blocksize.data(), tsv.data(), nwindows, w, nullptr, &plan) < 0) return ERR_INVALID_PARAM;
+    hp->held.assign((size_t)nchunks, 0);
+    hp->new_off.assign((size_t)nchunks, 0);
+    for (int i = 0; i < nchunks; i++) {
+        const int32_t cb = hp->cbytes[(size_t)i];
+        hp->held[(size_t)i] = comp_size ? comp_size[i] : cb;
+        if (!plan.touched[(size_t)i]) continue;
+        stage_chunk(hp, i, std::max((int32_t)HEADER_LEN, std::min(cb, hp->held[(size_t)i])));
+        hp->new_off[(size_t)i] = hp->new_total;
+        hp->new_used = hp->new_total + std::max(destsize[i], 0);
+        hp->new_total += ((int64_t)std::max(destsize[i], 0) + 63) & ~63ll;
+    }
+    pack_rows(nwindows, w, tsv.data(), hp);
+    hp->bytes_uploaded = hp->comp_bytes_uploaded;
+    for (const int64_t b : hp->wbytes) hp->bytes_uploaded += b;
     return 0;
 }
 

@@ -61,6 +61,29 @@ struct WideDecodePlan {
 
 inline bool decode_is_wide(int blocksize) { return decode_lds_bound(blocksize) > MAX_LDS_BYTES; }
 
+// The batch arrays of the listed chunks, in the order of the list: what a sub-batch is handed to the batch path with.  Without
+// comp_size every cs says 0x7fffffff (the caller chooses between that and a null pointer); without raw_off ro stays empty.
+struct SubBatch {
+    std::vector<int64_t> co, ro;
+    std::vector<int32_t> cs, nb, bs;
+    SubBatch(const std::vector<int>& list, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize,
+             const int64_t* raw_off = nullptr)
+    {
+        for (const int i : list) {
+            co.push_back(comp_off[i]); cs.push_back(comp_size ? comp_size[i] : 0x7fffffff); nb.push_back(nbytes[i]); bs.push_back(blocksize[i]);
+            if (raw_off) ro.push_back(raw_off[i]);
+        }
+    }
+};
+
+// a sub-batch refused before any of its chunks had a status of its own: the refusal is every listed chunk's
+inline void spread_refusal(int rc, size_t n, int32_t* st)
+{
+    if (rc >= 0) return;
+    for (size_t k = 0; k < n; k++) if (st[k] != 0) return;
+    for (size_t k = 0; k < n; k++) st[k] = rc;
+}
+
 inline int plan_decode_wide(int nchunks, const int64_t* comp_off, const int32_t* nbytes, const int32_t* blocksize,
                             const int64_t* raw_off, WideDecodePlan* wp, const int32_t* comp_size = nullptr)
 {
@@ -73,25 +96,19 @@ inline int plan_decode_wide(int nchunks, const int64_t* comp_off, const int32_t*
     }
     if (wp->wide.empty()) return ERR_CODEC_SUPPORT;           // nothing here is wide: the normal planner's refusal stands
     const int nw = (int)wp->wide.size();
-    std::vector<int64_t> co((size_t)nw), ro((size_t)nw);
-    std::vector<int32_t> nb((size_t)nw), bs((size_t)nw), cs((size_t)nw);
-    for (int k = 0; k < nw; k++) {
-        const int i = wp->wide[(size_t)k];
-        co[(size_t)k] = comp_off[i]; ro[(size_t)k] = raw_off[i]; nb[(size_t)k] = nbytes[i]; bs[(size_t)k] = blocksize[i];
-        cs[(size_t)k] = comp_size ? comp_size[i] : 0x7fffffff;
-    }
     DecodePlan& plan = wp->plan;
     plan.descs.resize((size_t)nw);
     int32_t blk = 0, slot = 0;
     for (int k = 0; k < nw; k++) {
+        const int i = wp->wide[(size_t)k];
         ChunkDesc& d = plan.descs[(size_t)k];
         d = ChunkDesc{};
-        d.raw_off = ro[(size_t)k];
-        d.comp_off = co[(size_t)k];
-        d.nbytes = nb[(size_t)k];
-        d.destsize = cs[(size_t)k];
+        d.raw_off = raw_off[i];
+        d.comp_off = comp_off[i];
+        d.nbytes = nbytes[i];
+        d.destsize = comp_size ? comp_size[i] : 0x7fffffff;
         if (d.destsize < HEADER_LEN) return ERR_READ_BUFFER;
-        d.blocksize = bs[(size_t)k];
+        d.blocksize = blocksize[i];
         d.nblocks = d.nbytes / d.blocksize;
         d.leftover = d.nbytes % d.blocksize;
         if (d.leftover) d.nblocks++;

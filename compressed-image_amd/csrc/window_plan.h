@@ -7,9 +7,14 @@
 // out_off + r * out_pitch.  The planner validates every window before anything runs, then lists the blocks that meet some window
 // row -- each once per window -- as work items.  Chunks whose blocks the window kernel cannot stage (zstd, blocks beyond LDS)
 // are decoded whole through the batch path first and cut from there (copy-mode items).
+//
+// The host-buffer call (cimg_decompress_windows_host) is planned here too, for the engine and the emulator alike: open_window_call
+// (the opening of both read calls), read_named_headers, stage_chunk and pack_rows (shared with update_plan.h) and plan_windows_host,
+// which decides everything between "the arguments are good" and "reserve the staging buffers".
 #pragma once
 #include "wide_plan.h"
 #include "window_kernel.h"
+#include <cstring>
 #include <vector>
 
 namespace cimg {
@@ -192,6 +197,115 @@ int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blo
         if ((rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.data(), &plan)) < 0) return rc;
     }
     for (int i = 0; i < nchunks; i++) if (status[i] != 0) return status[i];
+    return 0;
+}
+
+// ---- the host-buffer calls: what is decided before anything is staged -----------------------------------------------------------
+
+// The opening of a read call: < 0 refused, CALL_DONE nothing to do (the call returns 0), 0 go on.
+enum : int { CALL_DONE = 1 };
+inline int open_window_call(int nchunks, int nwindows, int32_t* status)
+{
+    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
+    if (status) for (int i = 0; i < nchunks; i++) status[i] = 0;
+    if (nwindows == 0) return CALL_DONE;
+    return nchunks == 0 ? ERR_INVALID_PARAM : 0;
+}
+
+// What both host calls plan.  Per-chunk arrays cover the whole batch; a chunk no window names keeps the defaults and is never
+// dereferenced, a chunk no window row meets is not staged (up 0).
+struct HostCallPlan {
+    std::vector<uint8_t> named, flags, version;                 // named: some window's [chunk_first, +chunk_count) holds the chunk
+    std::vector<int32_t> nbytes, blocksize, cbytes, typesize;   // from the named chunks' headers
+    int bad_window = -1;                // ERR_INVALID_PARAM: this window's chunks leave the batch
+    int short_chunk = -1;               // ERR_READ_BUFFER: this named chunk's buffer cannot hold a header
+    int bad_chunk = -1;                 // a touched chunk's header was refused (its status word says why)
+    // the touched chunks in the staging buffer, in 64-byte slots: `up` bytes of chunk i at d_comp_off[i]
+    std::vector<int64_t> d_comp_off;
+    std::vector<int32_t> up;
+    int64_t comp_total = 0, comp_used = 0, comp_bytes_uploaded = 0;     // (_used: the last byte a slot holds; _total rounds it up)
+    // the windows with their rows packed one after the other, each window at a multiple of 256
+    std::vector<WindowSpec> dw;
+    std::vector<int64_t> wbytes;
+    int64_t rows_total = 0, rows_used = 0;
+};
+
+// The headers of the chunks the windows name (the geometry of their planes); the others are not looked at.
+inline int read_named_headers(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, int nwindows,
+                              const WindowSpec* w, HostCallPlan* hp)
+{
+    const size_t n = (size_t)nchunks;
+    hp->named.assign(n, 0); hp->flags.assign(n, 0); hp->version.assign(n, 0);
+    hp->nbytes.assign(n, 0); hp->blocksize.assign(n, 1); hp->cbytes.assign(n, 0); hp->typesize.assign(n, 0);
+    hp->d_comp_off.assign(n, 0); hp->up.assign(n, 0);
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count) { hp->bad_window = k; return ERR_INVALID_PARAM; }
+        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) hp->named[(size_t)i] = 1;
+    }
+    for (int i = 0; i < nchunks; i++) {
+        if (!hp->named[(size_t)i]) continue;
+        if (comp_size && comp_size[i] < HEADER_LEN) { hp->short_chunk = i; return ERR_READ_BUFFER; }
+        const uint8_t* c = comp + comp_off[i];
+        memcpy(&hp->nbytes[(size_t)i], c + OFF_NBYTES, 4); memcpy(&hp->blocksize[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&hp->cbytes[(size_t)i], c + OFF_CBYTES, 4);
+        hp->typesize[(size_t)i] = c[OFF_TYPESIZE];
+        hp->flags[(size_t)i] = c[OFF_FLAGS];
+        hp->version[(size_t)i] = c[0];
+    }
+    return 0;
+}
+
+// the next slot of the staging buffer: `bytes` of chunk i
+inline void stage_chunk(HostCallPlan* hp, int i, int32_t bytes)
+{
+    hp->d_comp_off[(size_t)i] = hp->comp_total;
+    hp->up[(size_t)i] = bytes;
+    hp->comp_used = hp->comp_total + bytes;
+    hp->comp_total += ((int64_t)bytes + 63) & ~63ll;
+    hp->comp_bytes_uploaded += bytes;
+}
+
+// the windows as the device sees them: rows packed (out_pitch = width * typesize); the caller's out_off / out_pitch stay in w
+inline void pack_rows(int nwindows, const WindowSpec* w, const int32_t* typesize, HostCallPlan* hp)
+{
+    hp->dw.assign(w, w + nwindows);
+    hp->wbytes.assign((size_t)nwindows, 0);
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].width <= 0 || w[k].height <= 0) continue;
+        const int64_t row = (int64_t)w[k].width * typesize[w[k].chunk_first];
+        hp->dw[(size_t)k].out_off = hp->rows_total;
+        hp->dw[(size_t)k].out_pitch = row;
+        hp->wbytes[(size_t)k] = row * w[k].height;
+        hp->rows_used = hp->rows_total + hp->wbytes[(size_t)k];
+        hp->rows_total += (hp->wbytes[(size_t)k] + 255) & ~255ll;
+    }
+}
+
+struct WindowHostPlan : HostCallPlan {
+    std::vector<uint8_t> hint;          // 1: a zstd chunk, decoded whole
+};
+
+// cimg_decompress_windows_host: the chunks some window row meets get their full header checks (a refusal is that chunk's status
+// word and the call's code), then only they are staged.  ERR_INVALID_PARAM with bad_window < 0: plan_windows refused a window.
+inline int plan_windows_host(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, int nwindows,
+                             const WindowSpec* w, int32_t* status, WindowHostPlan* hp)
+{
+    int rc = read_named_headers(nchunks, comp, comp_off, comp_size, nwindows, w, hp);
+    if (rc < 0) return rc;
+    hp->hint.assign((size_t)nchunks, 0);
+    for (int i = 0; i < nchunks; i++) hp->hint[(size_t)i] = (hp->flags[(size_t)i] >> 5) == 4 && !(hp->flags[(size_t)i] & FLAG_MEMCPYED);
+    WindowPlan plan;
+    if ((rc = plan_windows(nchunks, hp->nbytes.data(), hp->blocksize.data(), hp->typesize.data(), nwindows, w, hp->hint.data(), &plan)) < 0) return rc;
+    for (int i = 0; i < nchunks; i++) {
+        if (!plan.touched[(size_t)i]) continue;
+        const int32_t cb = hp->cbytes[(size_t)i];
+        int code = 0;
+        if (hp->version[(size_t)i] > 5) code = ERR_VERSION_SUPPORT;
+        else if (cb < HEADER_LEN) code = ERR_INVALID_HEADER;
+        else if (comp_size && cb > comp_size[i]) code = ERR_READ_BUFFER;
+        if (code) { status[i] = code; hp->bad_chunk = i; return code; }
+        stage_chunk(hp, i, cb);
+    }
+    pack_rows(nwindows, w, hp->typesize.data(), hp);
     return 0;
 }
 

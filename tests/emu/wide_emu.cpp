@@ -85,10 +85,9 @@ int wemu_decompress_batch(int nchunks, const uint8_t* comp, const int64_t* comp_
     memset(status, 0, sizeof(int32_t) * (size_t)nchunks);
     if (!wp.normal.empty()) {
         const size_t nn = wp.normal.size();
-        std::vector<int64_t> co(nn), ro(nn);
-        std::vector<int32_t> nb(nn), bs(nn), st(nn, 0);
-        for (size_t k = 0; k < nn; k++) { const int i = wp.normal[k]; co[k] = comp_off[i]; ro[k] = raw_off[i]; nb[k] = nbytes[i]; bs[k] = blocksize[i]; }
-        if ((rc = emu_decompress_batch((int)nn, comp, co.data(), nb.data(), bs.data(), raw, ro.data(), st.data())) < 0) return rc;
+        const SubBatch sub(wp.normal, comp_off, nullptr, nbytes, blocksize, raw_off);
+        std::vector<int32_t> st(nn, 0);
+        if ((rc = emu_decompress_batch((int)nn, comp, sub.co.data(), sub.nb.data(), sub.bs.data(), raw, sub.ro.data(), st.data())) < 0) return rc;
         for (size_t k = 0; k < nn; k++) status[wp.normal[k]] = st[k];
     }
     if (wp.wide.empty()) return 0;

@@ -6,8 +6,6 @@
 #define CIMG_EMULATE 1
 #endif
 #include "window_plan.h"
-#include <cstring>
-#include <vector>
 
 #ifndef EMU_LDS_SLACK
 #define EMU_LDS_SLACK 64
@@ -19,35 +17,36 @@ namespace cimg {
 typedef int (*EmuWholeFn)(int n, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
                           const int32_t* blocksize, uint8_t* raw, const int64_t* raw_off, int32_t* status);
 
-struct EmuWindowEnv {
+// the batch a window call runs on, and the step run_windows and run_update share (engine.hip: EngineChunks)
+struct EmuChunks {
     EmuWholeFn whole_fn;
     const uint8_t* comp;
     const int64_t* comp_off;
     const int32_t* comp_size;
     const int32_t* nbytes;
     const int32_t* blocksize;
-    uint8_t* out;
-    int32_t typesize;
-    std::vector<uint8_t> scratch;
+    std::vector<uint8_t> whole;
 
     int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
     {
-        scratch.assign((size_t)total + 64, 0xEE);
-        const size_t n = list.size();
-        std::vector<int64_t> co(n);
-        std::vector<int32_t> cs(n), nb(n), bs(n);
-        for (size_t k = 0; k < n; k++) {
-            const int i = list[k];
-            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
-        }
-        const int rc = whole_fn((int)n, comp, co.data(), comp_size ? cs.data() : nullptr, nb.data(), bs.data(), scratch.data(), dst_off.data(), st);
-        if (rc < 0) {
-            bool any = false;
-            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
-            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
-        }
+        whole.assign((size_t)total + 64, 0xEE);
+        const SubBatch sub(list, comp_off, comp_size, nbytes, blocksize);
+        const int rc = whole_fn((int)list.size(), comp, sub.co.data(), comp_size ? sub.cs.data() : nullptr, sub.nb.data(), sub.bs.data(), whole.data(),
+                                dst_off.data(), st);
+        spread_refusal(rc, list.size(), st);
         return 0;
     }
+};
+
+// rows of `row` bytes from one pitch to another: what the engine's host calls do with (2-D) copies over PCIe
+inline void copy_rows(uint8_t* dst, int64_t dst_pitch, const uint8_t* src, int64_t src_pitch, int64_t row, int height)
+{
+    for (int r = 0; r < height; r++) memcpy(dst + r * dst_pitch, src + r * src_pitch, (size_t)row);
+}
+
+struct EmuWindowEnv : EmuChunks {
+    uint8_t* out;
+    int32_t typesize;
 
     int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
     {
@@ -61,7 +60,7 @@ struct EmuWindowEnv {
         WindowArgs wa{};
         wa.d = DecodeArgs{descs.data(), nchunks, comp, out, st.data(), plan.lds_bytes, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0};
         wa.items = items.data();
-        wa.whole = scratch.data();
+        wa.whole = whole.data();
         wa.out = out;
         wa.typesize = typesize;
         wa.nitems = (int32_t)items.size();
@@ -85,56 +84,34 @@ inline int emu_windows_device(EmuWholeFn fn, int nchunks, const uint8_t* comp, c
                               uint8_t* out, int32_t* status, WindowStats* stats)
 {
     *stats = WindowStats{};
-    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
-    for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (nwindows == 0) return 0;
-    if (nchunks == 0 || typesize <= 0 || typesize > 255) return ERR_INVALID_PARAM;
+    const int rc = open_window_call(nchunks, nwindows, status);
+    if (rc) return rc > 0 ? 0 : rc;
+    if (typesize <= 0 || typesize > 255) return ERR_INVALID_PARAM;
     std::vector<int32_t> ts((size_t)nchunks, typesize);
-    EmuWindowEnv env{fn, comp, comp_off, comp_size, nbytes, blocksize, out, typesize, {}};
+    EmuWindowEnv env{{fn, comp, comp_off, comp_size, nbytes, blocksize, {}}, out, typesize};
     return run_windows(env, nchunks, nbytes, blocksize, ts.data(), nwindows, w, {}, status, stats);
 }
 
-// cimg_decompress_windows_host: the headers read on the host, zstd chunks known up front, the touched chunks' bytes counted
+// cimg_decompress_windows_host: planned as the engine plans it, staged with memcpy where the engine copies over PCIe -- into buffers
+// that end at their last used byte, for the sanitizers
 inline int emu_windows_host(EmuWholeFn fn, int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size,
                             int nwindows, const WindowSpec* w, uint8_t* out, int32_t* status, WindowStats* stats)
 {
     *stats = WindowStats{};
-    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
-    for (int i = 0; i < nchunks; i++) status[i] = 0;
-    if (nwindows == 0) return 0;
-    if (nchunks == 0) return ERR_INVALID_PARAM;
-    std::vector<uint8_t> named((size_t)nchunks, 0), hint((size_t)nchunks, 0);
+    int rc = open_window_call(nchunks, nwindows, status);
+    if (rc) return rc > 0 ? 0 : rc;
+    WindowHostPlan hp;
+    if ((rc = plan_windows_host(nchunks, comp, comp_off, comp_size, nwindows, w, status, &hp)) < 0) return rc;
+    std::vector<uint8_t> sc((size_t)hp.comp_used), so((size_t)hp.rows_used, 0);
+    for (int i = 0; i < nchunks; i++) if (hp.up[(size_t)i]) memcpy(sc.data() + hp.d_comp_off[(size_t)i], comp + comp_off[i], (size_t)hp.up[(size_t)i]);
+    EmuWindowEnv env{{fn, sc.data(), hp.d_comp_off.data(), hp.cbytes.data(), hp.nbytes.data(), hp.blocksize.data(), {}}, so.data(), 0};
+    rc = run_windows(env, nchunks, hp.nbytes.data(), hp.blocksize.data(), hp.typesize.data(), nwindows, hp.dw.data(), hp.hint, status, stats);
+    stats->comp_bytes_uploaded = hp.comp_bytes_uploaded;
+    if (rc == ERR_INVALID_PARAM) return rc;
     for (int k = 0; k < nwindows; k++) {
-        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count) return ERR_INVALID_PARAM;
-        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
+        const WindowSpec& d = hp.dw[(size_t)k];
+        if (hp.wbytes[(size_t)k]) copy_rows(out + w[k].out_off, w[k].out_pitch, so.data() + d.out_off, d.out_pitch, d.out_pitch, w[k].height);
     }
-    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), ts((size_t)nchunks, 0), cb((size_t)nchunks, 0);
-    std::vector<int> version((size_t)nchunks, 0);
-    for (int i = 0; i < nchunks; i++) {
-        if (!named[(size_t)i]) continue;
-        if (comp_size && comp_size[i] < HEADER_LEN) return ERR_READ_BUFFER;
-        const uint8_t* c = comp + comp_off[i];
-        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
-        ts[(size_t)i] = c[OFF_TYPESIZE];
-        version[(size_t)i] = c[0];
-        hint[(size_t)i] = (c[OFF_FLAGS] >> 5) == 4 && !(c[OFF_FLAGS] & FLAG_MEMCPYED);
-    }
-    WindowPlan plan;
-    int rc = plan_windows(nchunks, nb.data(), bs.data(), ts.data(), nwindows, w, hint.data(), &plan);
-    if (rc < 0) return rc;
-    int64_t uploaded = 0;
-    for (int i = 0; i < nchunks; i++) {
-        if (!plan.touched[(size_t)i]) continue;
-        int code = 0;
-        if (version[(size_t)i] > 5) code = ERR_VERSION_SUPPORT;
-        else if (cb[(size_t)i] < HEADER_LEN) code = ERR_INVALID_HEADER;
-        else if (comp_size && cb[(size_t)i] > comp_size[i]) code = ERR_READ_BUFFER;
-        if (code) { status[i] = code; return code; }
-        uploaded += cb[(size_t)i];
-    }
-    EmuWindowEnv env{fn, comp, comp_off, cb.data(), nb.data(), bs.data(), out, 0, {}};
-    rc = run_windows(env, nchunks, nb.data(), bs.data(), ts.data(), nwindows, w, hint, status, stats);
-    stats->comp_bytes_uploaded = uploaded;
     return rc;
 }
 

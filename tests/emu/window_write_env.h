@@ -7,56 +7,24 @@
 #define CIMG_EMULATE 1
 #endif
 #include "update_plan.h"
-#include <cstring>
-#include <vector>
-
-#ifndef EMU_LDS_SLACK
-#define EMU_LDS_SLACK 64
-#endif
+#include "window_env.h"
 
 namespace cimg {
 
-typedef int (*EmuWholeFn)(int n, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
-                          const int32_t* blocksize, uint8_t* raw, const int64_t* raw_off, int32_t* status);
 // the batch compress (cparams laid out as cimg_cparams / HostCParams)
 typedef int (*EmuCompressFn)(const void* p, int n, const uint8_t* raw, const int64_t* raw_off, const int32_t* nbytes, uint8_t* comp,
                              const int64_t* comp_off, const int32_t* destsize, int32_t* cbytes);
 
-struct EmuUpdateEnv {
-    EmuWholeFn whole_fn;
+struct EmuUpdateEnv : EmuChunks {
     EmuCompressFn compress_fn;
-    const uint8_t* comp;
-    const int64_t* comp_off;
-    const int32_t* comp_size;
-    const int32_t* nbytes;
-    const int32_t* blocksize;
     const uint8_t* src;
     uint8_t* newbuf;
-    std::vector<uint8_t> whole, patchbuf, scratch;
+    std::vector<uint8_t> patchbuf, scratch;
     std::vector<StreamRec> recs;
 
     int headers(const std::vector<int>& list, uint8_t* out)
     {
         for (size_t k = 0; k < list.size(); k++) memcpy(out + k * HEADER_LEN, comp + comp_off[list[k]], HEADER_LEN);
-        return 0;
-    }
-
-    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
-    {
-        whole.assign((size_t)total + 64, 0xEE);
-        const size_t n = list.size();
-        std::vector<int64_t> co(n);
-        std::vector<int32_t> cs(n), nb(n), bs(n);
-        for (size_t k = 0; k < n; k++) {
-            const int i = list[k];
-            co[k] = comp_off[i]; cs[k] = comp_size ? comp_size[i] : 0x7fffffff; nb[k] = nbytes[i]; bs[k] = blocksize[i];
-        }
-        const int rc = whole_fn((int)n, comp, co.data(), comp_size ? cs.data() : nullptr, nb.data(), bs.data(), whole.data(), dst_off.data(), st);
-        if (rc < 0) {
-            bool any = false;
-            for (size_t k = 0; k < n; k++) any |= st[k] != 0;
-            if (!any) for (size_t k = 0; k < n; k++) st[k] = rc;
-        }
         return 0;
     }
 
@@ -144,50 +112,38 @@ inline int emu_update_device(EmuWholeFn wf, EmuCompressFn cf, const HostCParams&
                              const WindowSpec* w, const uint8_t* src, uint8_t* newbuf, const int64_t* new_off, int32_t* new_cbytes,
                              int32_t* status, UpdateStats* stats)
 {
-    EmuUpdateEnv env{wf, cf, comp, comp_off, comp_size, nbytes, blocksize, src, newbuf, {}, {}, {}, {}};
+    EmuUpdateEnv env{{wf, comp, comp_off, comp_size, nbytes, blocksize, {}}, cf, src, newbuf, {}, {}, {}};
     return run_update(env, p, nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, w, new_off, new_cbytes, status, stats);
 }
 
-// = cimg_update_windows_host: the headers read on the host; every touched chunk's new form in memory from `alloc`
+// = cimg_update_windows_host: planned as the engine plans it, staged with memcpy where the engine copies over PCIe -- into buffers that
+// end at their last used byte, for the sanitizers; every touched chunk's new form in memory from `alloc`
 inline int emu_update_host(EmuWholeFn wf, EmuCompressFn cf, const HostCParams& p, int nchunks, const uint8_t* comp, const int64_t* comp_off,
                            const int32_t* comp_size, const int32_t* destsize, int nwindows, const WindowSpec* w, const uint8_t* src,
                            void* (*alloc)(void*, size_t), void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status,
                            UpdateStats* stats)
 {
     *stats = UpdateStats{};
-    if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
-    for (int i = 0; i < nchunks; i++) { status[i] = 0; new_cbytes[i] = 0; new_chunks[i] = nullptr; }
-    if (nwindows == 0) return 0;
+    int rc = open_update_call(nchunks, nwindows, status, new_cbytes, new_chunks);
+    if (rc) return rc > 0 ? 0 : rc;
     if (nchunks == 0 || !alloc) return ERR_INVALID_PARAM;
-    std::vector<uint8_t> named((size_t)nchunks, 0);
+    UpdateHostPlan hp;
+    if ((rc = plan_update_host(p.typesize, nchunks, comp, comp_off, comp_size, destsize, nwindows, w, status, &hp)) < 0) return rc;
+    std::vector<uint8_t> sc((size_t)hp.comp_used), ss((size_t)hp.rows_used), newbuf((size_t)hp.new_used, 0);
+    for (int i = 0; i < nchunks; i++) if (hp.up[(size_t)i]) memcpy(sc.data() + hp.d_comp_off[(size_t)i], comp + comp_off[i], (size_t)hp.up[(size_t)i]);
     for (int k = 0; k < nwindows; k++) {
-        if (w[k].chunk_first < 0 || w[k].chunk_count < 1 || w[k].chunk_first > nchunks - w[k].chunk_count) return ERR_INVALID_PARAM;
-        for (int i = w[k].chunk_first; i < w[k].chunk_first + w[k].chunk_count; i++) named[(size_t)i] = 1;
+        const WindowSpec& d = hp.dw[(size_t)k];
+        if (hp.wbytes[(size_t)k]) copy_rows(ss.data() + d.out_off, d.out_pitch, src + w[k].out_off, w[k].out_pitch, d.out_pitch, w[k].height);
     }
-    std::vector<int32_t> nb((size_t)nchunks, 0), bs((size_t)nchunks, 1), cb((size_t)nchunks, 0);
-    for (int i = 0; i < nchunks; i++) {
-        if (!named[(size_t)i]) continue;
-        if (comp_size && comp_size[i] < HEADER_LEN) { status[i] = ERR_READ_BUFFER; return ERR_READ_BUFFER; }
-        const uint8_t* c = comp + comp_off[i];
-        memcpy(&nb[(size_t)i], c + OFF_NBYTES, 4); memcpy(&bs[(size_t)i], c + OFF_BLOCKSIZE, 4); memcpy(&cb[(size_t)i], c + OFF_CBYTES, 4);
-    }
-    std::vector<int64_t> new_off((size_t)nchunks, 0);
-    int64_t total = 0;
-    for (int i = 0; i < nchunks; i++) { new_off[(size_t)i] = total; if (named[(size_t)i] && destsize[i] > 0) total += ((int64_t)destsize[i] + 63) & ~63ll; }
-    std::vector<uint8_t> newbuf((size_t)total + 64, 0);
-    const int rc = emu_update_device(wf, cf, p, nchunks, comp, comp_off, comp_size, nb.data(), bs.data(), destsize, nwindows, w, src,
-                                     newbuf.data(), new_off.data(), new_cbytes, status, stats);
+    rc = emu_update_device(wf, cf, p, nchunks, sc.data(), hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data(), destsize,
+                           nwindows, hp.dw.data(), ss.data(), newbuf.data(), hp.new_off.data(), new_cbytes, status, stats);
+    stats->bytes_uploaded += hp.bytes_uploaded;
     if (rc == ERR_INVALID_PARAM) return rc;
-    WindowPlan plan;
-    const std::vector<int32_t> tsv((size_t)nchunks, p.typesize > 255 ? 1 : p.typesize);
-    if (plan_windows(nchunks, nb.data(), bs.data(), tsv.data(), nwindows, w, nullptr, &plan) == 0)
-        for (int i = 0; i < nchunks; i++) if (plan.touched[(size_t)i]) stats->bytes_uploaded += cb[(size_t)i];
-    for (int k = 0; k < nwindows; k++) stats->bytes_uploaded += (int64_t)w[k].width * w[k].height * tsv[0];
     for (int i = 0; i < nchunks; i++) {
         if (new_cbytes[i] <= 0) continue;
         void* m = alloc(user, (size_t)new_cbytes[i]);
         if (!m) return -4;
-        memcpy(m, newbuf.data() + new_off[(size_t)i], (size_t)new_cbytes[i]);
+        memcpy(m, newbuf.data() + hp.new_off[(size_t)i], (size_t)new_cbytes[i]);
         new_chunks[i] = m;
     }
     return rc;
