@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "plan.h"
@@ -231,6 +232,17 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_window(WindowArgs 
     wb.phase_w(wave);
 }
 
+// Strided windows: the same staging, then only the sampled elements of each window row are written (StridedWindowBlock).
+extern "C" __global__ __launch_bounds__(256) void cimg_decode_window_strided(StridedWindowArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    StridedWindowBlock wb(a, lds, (int)blockIdx.x);
+    wb.phase_a(wave);
+    __syncthreads();
+    wb.phase_w(wave);
+}
+
 // zstd blocks beyond the normal kernels' LDS.  Encode: cimg_encode_wide's waves with zstd_wide_encode (hash table and FSE tables in
 // LDS, sequences in a device-memory area per wave).  Decode, behind cimg_zstd_walk: the replay with its planes in a device-memory
 // slot per single-wave workgroup, which walks blocks blk_first + k, k + G, ... of the group.
@@ -379,7 +391,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13)
+    int max_dyn_lds[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -577,6 +589,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_ZSTD_SEQ: return "cimg_zstd_seq";
     case CIMG_K_ZSTD_LIT: return "cimg_zstd_lit";
     case CIMG_K_DECODE_WINDOW: return "cimg_decode_window";
+    case CIMG_K_DECODE_WINDOW_STRIDED: return "cimg_decode_window_strided";
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
@@ -2013,6 +2026,8 @@ int cimg_decompress_batch_host_sized(cimg_engine* e, int32_t nchunks, const void
 
 // ---- windows (window_plan.h, window_kernel.h) --------------------------------------------------------
 static_assert(sizeof(cimg_window) == sizeof(WindowSpec) && offsetof(cimg_window, out_pitch) == offsetof(WindowSpec, out_pitch), "cimg_window != WindowSpec");
+static_assert(sizeof(cimg_window_strided) == sizeof(StridedWindowSpec) && offsetof(cimg_window_strided, col_pitch) == offsetof(StridedWindowSpec, col_pitch) &&
+              offsetof(cimg_window_strided, out_pitch) == offsetof(StridedWindowSpec, out_pitch), "cimg_window_strided != StridedWindowSpec");
 
 namespace {
 
@@ -2043,11 +2058,16 @@ struct EngineWindowEnv : EngineChunks {
     uint8_t* d_out;
     int32_t typesize;                  // 0: the host checked every header's typesize already
 
-    int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
+    int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status) { return run(plan, items, status); }
+    int run_items(const StridedWindowPlan& plan, const std::vector<StridedWindowItem>& items, int32_t* status) { return run(plan, items, status); }
+
+    // the launch over a table of items: cimg_decode_window, or its strided form over StridedWindowItem
+    template <class Item>
+    int run(const WindowPlanT<Item>& plan, const std::vector<Item>& items, int32_t* status)
     {
         int rc;
         const int nchunks = (int)plan.descs.size();
-        const size_t ib = items.size() * sizeof(WindowItem), db = plan.descs.size() * sizeof(ChunkDesc), sb = (size_t)nchunks * 4;
+        const size_t ib = items.size() * sizeof(Item), db = plan.descs.size() * sizeof(ChunkDesc), sb = (size_t)nchunks * 4;
         if ((rc = e->reserve(e->h_win_items, ib)) || (rc = e->reserve(e->win_items, ib))) return rc;
         if ((rc = e->reserve(e->h_win_descs, db)) || (rc = e->reserve(e->win_descs, db))) return rc;
         if ((rc = e->reserve(e->h_win_st, sb))) return rc;
@@ -2065,14 +2085,21 @@ struct EngineWindowEnv : EngineChunks {
         if ((rc = e->hip(hipMemcpyAsync(e->win_descs.p, e->h_win_descs.p, db, hipMemcpyHostToDevice, e->stream), "window descs H2D"))) return rc;
         WindowArgs wa{};
         wa.d = DecodeArgs{(const ChunkDesc*)e->win_descs.p, nchunks, d_comp, d_out, d_st, plan.lds_bytes, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0};
-        wa.items = (const WindowItem*)e->win_items.p;
         wa.whole = (const uint8_t*)e->win_whole.p;
         wa.out = d_out;
         wa.typesize = typesize;
         wa.nitems = (int32_t)items.size();
-        if ((rc = e->allow_lds(cimg_decode_window, 12, plan.lds_bytes))) return rc;
-        e->begin_batch(1);
-        rc = e->launch(CIMG_K_DECODE_WINDOW, cimg_decode_window, wa, (int)items.size(), 256, plan.lds_bytes);
+        if constexpr (std::is_same_v<Item, StridedWindowItem>) {
+            const StridedWindowArgs sa{wa, (const StridedWindowItem*)e->win_items.p};
+            if ((rc = e->allow_lds(cimg_decode_window_strided, 14, plan.lds_bytes))) return rc;
+            e->begin_batch(1);
+            rc = e->launch(CIMG_K_DECODE_WINDOW_STRIDED, cimg_decode_window_strided, sa, (int)items.size(), 256, plan.lds_bytes);
+        } else {
+            wa.items = (const WindowItem*)e->win_items.p;
+            if ((rc = e->allow_lds(cimg_decode_window, 12, plan.lds_bytes))) return rc;
+            e->begin_batch(1);
+            rc = e->launch(CIMG_K_DECODE_WINDOW, cimg_decode_window, wa, (int)items.size(), 256, plan.lds_bytes);
+        }
         const int src = cimg_engine_synchronize(e);
         if (rc || src) return rc ? rc : src;
         const int32_t* hs = (const int32_t*)e->h_win_st.p;
@@ -2086,13 +2113,21 @@ int invalid_window(cimg_engine* e)
     return e->fail(ERR_INVALID_PARAM, "invalid window: every window must lie inside its plane of chunks, with width and height >= 0, "
                                       "row_pitch >= width (height > 1), out_pitch >= width * typesize and one typesize per plane");
 }
+int invalid_window(cimg_engine* e, const StridedWindowSpec*)
+{
+    return e->fail(ERR_INVALID_PARAM, "invalid strided window: every sampled element must lie inside the window's plane of chunks, with width "
+                                      "and height >= 0, col_pitch >= 1, row_pitch >= (width - 1) * col_pitch + 1 (height > 1), "
+                                      "out_pitch >= width * typesize and one typesize per plane");
+}
+int invalid_window(cimg_engine* e, const WindowSpec*) { return invalid_window(e); }
 
 // the text of a call refused at its opening (open_window_call, open_update_call) or by read_named_headers
 int open_fail(cimg_engine* e, int32_t nchunks, int32_t nwindows)
 {
     return e->fail(ERR_INVALID_PARAM, nchunks < 0 || nwindows < 0 ? "negative chunk or window count" : "a window needs chunks");
 }
-int named_fail(cimg_engine* e, int rc, const HostCallPlan& hp, int32_t nchunks, const cimg_window* w, const int32_t* comp_size)
+template <class Window>
+int named_fail(cimg_engine* e, int rc, const HostCallPlan& hp, int32_t nchunks, const Window* w, const int32_t* comp_size)
 {
     const int k = hp.bad_window, i = hp.short_chunk;
     if (k >= 0) return e->fail(rc, "window %d: chunks [%d, +%d) are not inside the batch of %d", k, w[k].chunk_first, w[k].chunk_count, nchunks);
@@ -2107,28 +2142,27 @@ int copy_rows(cimg_engine* e, void* dst, int64_t dst_pitch, const void* src, int
     return e->hip(hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)row, (size_t)height, kind, e->stream), what);
 }
 
+template <class Spec>
 int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
                 const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int32_t check_ts, const std::vector<uint8_t>& hint,
-                int32_t nwindows, const WindowSpec* w, void* d_out, int32_t* status)
+                int32_t nwindows, const Spec* w, void* d_out, int32_t* status)
 {
     EngineWindowEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, (uint8_t*)d_out, check_ts};
     WindowStats st;
     const int rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
     e->win_stats = st;
-    if (rc == ERR_INVALID_PARAM) return invalid_window(e);
+    if (rc == ERR_INVALID_PARAM) return invalid_window(e, w);
     if (rc < 0) {
         for (int i = 0; i < nchunks; i++) if (status[i] == rc) return e->fail(rc, "chunk %d failed to decode (code %d)", i, rc);
     }
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
-                                   const int32_t* nbytes, const int32_t* blocksize, int32_t typesize, int32_t nwindows, const cimg_window* w,
-                                   void* d_out, int32_t* status)
+// cimg_decompress_windows_device and its strided form
+template <class Spec>
+int windows_device_call(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
+                        const int32_t* nbytes, const int32_t* blocksize, int32_t typesize, int32_t nwindows, const Spec* w, void* d_out,
+                        int32_t* status)
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->win_stats = WindowStats{};
@@ -2139,12 +2173,13 @@ int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* 
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     std::vector<int32_t> ts((size_t)nchunks, typesize);
-    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows,
-                       reinterpret_cast<const WindowSpec*>(w), d_out, status);
+    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows, w, d_out, status);
 }
 
-int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
-                                 int32_t nwindows, const cimg_window* w, void* h_out, int32_t* status)
+// cimg_decompress_windows_host and its strided form
+template <class Spec>
+int windows_host_call(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
+                      int32_t nwindows, const Spec* w, void* h_out, int32_t* status)
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->win_stats = WindowStats{};
@@ -2156,10 +2191,11 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
     e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
     const uint8_t* hc = (const uint8_t*)h_comp;
     WindowHostPlan hp;
-    if ((rc = plan_windows_host(nchunks, hc, comp_off, comp_size, nwindows, reinterpret_cast<const WindowSpec*>(w), status, &hp)) < 0) {
+    std::vector<Spec> dw;                                  // the windows with their rows packed
+    if ((rc = plan_windows_host(nchunks, hc, comp_off, comp_size, nwindows, w, status, &hp, &dw)) < 0) {
         if (hp.bad_window >= 0 || hp.short_chunk >= 0) return named_fail(e, rc, hp, nchunks, w, comp_size);
         if (hp.bad_chunk >= 0) return e->fail(rc, "chunk %d: invalid header (code %d)", hp.bad_chunk, rc);
-        return rc == ERR_INVALID_PARAM ? invalid_window(e) : e->fail(rc, "invalid chunk header among the windows' chunks");
+        return rc == ERR_INVALID_PARAM ? invalid_window(e, w) : e->fail(rc, "invalid chunk header among the windows' chunks");
     }
     // only the chunks some window row meets go over PCIe; the windows come back packed, and go to h_out at the callers' pitches
     if ((rc = e->reserve(e->stage_comp, (size_t)hp.comp_total + 64))) return rc;
@@ -2171,14 +2207,14 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
         if ((rc = copy_in(e, e->stream, sc, hp.d_comp_off.data(), hc, comp_off, hp.up.data(), 0, nchunks, "chunk H2D"))) return rc;
         if ((rc = e->hip(hipMemsetAsync(so, 0, (size_t)hp.rows_total, e->stream), "window memset"))) return rc;
         rc = windows_run(e, nchunks, sc, hp.d_comp_off.data(), hp.cbytes.data(), hp.nbytes.data(), hp.blocksize.data(), hp.typesize.data(), 0,
-                         hp.hint, nwindows, hp.dw.data(), so, status);
+                         hp.hint, nwindows, dw.data(), so, status);
     }
     e->win_stats.comp_bytes_uploaded = hp.comp_bytes_uploaded;
     if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return rc;
     const std::string chunk_error = e->err;
     uint8_t* ho = (uint8_t*)h_out;
     for (int k = 0; k < nwindows; k++) {
-        const WindowSpec& d = hp.dw[(size_t)k];
+        const Spec& d = dw[(size_t)k];
         if (!hp.wbytes[(size_t)k]) continue;
         const int crc = copy_rows(e, ho + w[k].out_off, w[k].out_pitch, so + d.out_off, d.out_pitch, d.out_pitch, w[k].height, hipMemcpyDeviceToHost, "window D2H");
         if (crc) { (void)cimg_engine_synchronize(e); return crc; }
@@ -2187,6 +2223,39 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
     if ((src = cimg_engine_synchronize(e))) return src;
     if (rc) e->err = chunk_error;
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cimg_decompress_windows_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
+                                   const int32_t* nbytes, const int32_t* blocksize, int32_t typesize, int32_t nwindows, const cimg_window* w,
+                                   void* d_out, int32_t* status)
+{
+    return windows_device_call(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, typesize, nwindows,
+                               reinterpret_cast<const WindowSpec*>(w), d_out, status);
+}
+
+int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
+                                 int32_t nwindows, const cimg_window* w, void* h_out, int32_t* status)
+{
+    return windows_host_call(e, nchunks, h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const WindowSpec*>(w), h_out, status);
+}
+
+int cimg_decompress_windows_strided_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                           const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, int32_t typesize,
+                                           int32_t nwindows, const cimg_window_strided* w, void* d_out, int32_t* status)
+{
+    return windows_device_call(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, typesize, nwindows,
+                               reinterpret_cast<const StridedWindowSpec*>(w), d_out, status);
+}
+
+int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
+                                         int32_t* status)
+{
+    return windows_host_call(e, nchunks, h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const StridedWindowSpec*>(w), h_out, status);
 }
 
 void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded)

@@ -5,6 +5,7 @@
 // out + out_off + r * out_pitch + (column * typesize).  Nothing outside the window is written.  Memcpyed and special-zero
 // chunks are cut from the chunk (or from nothing) without staging; items of chunks that were decoded whole beforehand
 // (zstd, blocks beyond LDS: the batch path into engine scratch) are cut from that copy (`b < 0`).
+// cimg_decode_window_strided (below) stages the same way and writes only every col_pitch-th element of each window row.
 #pragma once
 #include "decode_kernel.h"
 
@@ -53,6 +54,9 @@ struct WindowBlock {
 
     CIMG_DEV WindowBlock(const WindowArgs& a_, uint8_t* lds_, int k)
         : a(a_), lds(lds_), it(uniform_item(a_.items + k)), blk(a_.d, lds_, it.b < 0 ? 0 : it.b) {}
+    // (the item handed in, already wave-uniform: the strided kernel keeps its items in a table of its own)
+    CIMG_DEV WindowBlock(const WindowArgs& a_, uint8_t* lds_, const WindowItem& t)
+        : a(a_), lds(lds_), it(t), blk(a_.d, lds_, it.b < 0 ? 0 : it.b) {}
 
     CIMG_DEV void fail(int code) { a.d.status[it.chunk] = code; mode = 3; }
 
@@ -147,6 +151,88 @@ struct WindowBlock {
                                 const int64_t q = q0 + i;
                                 if (q >= 0 && q < n) dst[q] = byte_at(k0 + q);
                             }
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// ---- strided windows: cimg_decode_window_strided -----------------------------------------------------------------------------
+// A window whose rows take every col_pitch-th element of the plane.  The block is staged exactly as above (WindowBlock::phase_a);
+// only the write phase differs: output byte q of a row is byte q % typesize of element q / typesize, which lies cpitch bytes after
+// its neighbour in the plane.  An element that straddles two blocks belongs, byte by byte, to both items.
+struct StridedWindowItem : WindowItem {     // wbytes: bytes of an OUTPUT row (width * typesize)
+    int64_t cpitch;       // plane bytes between consecutive elements of a window row (col_pitch * typesize)
+    int32_t ts;           // the plane's typesize (validated by the planner)
+    int32_t pad_;
+};
+
+struct StridedWindowArgs {
+    WindowArgs w;         // (w.items unused)
+    const StridedWindowItem* items;
+};
+
+struct StridedWindowBlock {
+    WindowBlock wb;
+    int64_t cpitch;
+    int ts;
+    int lg;               // log2(ts) when it is a power of two, else -1
+
+    CIMG_DEV StridedWindowBlock(const StridedWindowArgs& a, uint8_t* lds, int k)
+        : wb(a.w, lds, WindowBlock::uniform_item(a.items + k)), cpitch(uni64(a.items[k].cpitch)), ts(uni(a.items[k].ts))
+    {
+        lg = (ts & (ts - 1)) == 0 ? __builtin_ctz((unsigned)ts) : -1;
+    }
+
+    CIMG_DEV void phase_a(int wave) { wb.phase_a(wave); }
+
+    CIMG_DEV void phase_w(int wave)
+    {
+        if (wb.mode == 3) return;
+        const WindowItem& it = wb.it;
+        const int64_t blen = wb.blen, width = it.wbytes / ts;
+        const int tid0 = wave * 64;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the block
+            // elements c_lo .. c_hi of the row have a byte in [0, blen)
+            const int64_t lo = -rel - (ts - 1), hi = blen - 1 - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = lo <= 0 ? 0 : (lo + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            const int64_t base = rel + c_lo * cpitch;                          // block offset of element c_lo (>= -(ts - 1))
+            uint8_t* dst = wb.a.out + it.out_off + (int64_t)r * it.out_pitch + c_lo * ts;
+            const int64_t n = (c_hi + 1 - c_lo) * ts;                          // (< 2^32: at most blen / ts + 2 elements)
+            // 4-byte units aligned on the destination, as in WindowBlock::phase_w
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += 256) {
+                FOR_LANES(l) {
+                    const int64_t u = u0 + l;
+                    if (u < units) {
+                        const int64_t q0 = 4 * u - mis;
+                        int64_t k[4];
+                        bool all = true;
+                        for (int i = 0; i < 4; i++) {
+                            const int64_t q = q0 + i;
+                            k[i] = -1;
+                            if (q >= 0 && q < n) {
+                                const uint32_t e = lg >= 0 ? (uint32_t)q >> lg : (uint32_t)q / (uint32_t)ts;
+                                const int64_t at = base + (int64_t)e * cpitch + (int64_t)((uint32_t)q - e * (uint32_t)ts);
+                                if (at >= 0 && at < blen) k[i] = at;
+                            }
+                            all = all && k[i] >= 0;
+                        }
+                        if (all) {
+                            const uint32_t v = (uint32_t)wb.byte_at(k[0]) | ((uint32_t)wb.byte_at(k[1]) << 8) |
+                                               ((uint32_t)wb.byte_at(k[2]) << 16) | ((uint32_t)wb.byte_at(k[3]) << 24);
+                            *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                        } else {
+                            for (int i = 0; i < 4; i++)
+                                if (k[i] >= 0) dst[q0 + i] = wb.byte_at(k[i]);
                         }
                     }
                 }

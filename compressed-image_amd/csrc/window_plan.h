@@ -1,12 +1,14 @@
 // window_plan.h -- the planner of cimg_decode_window (window_kernel.h) and the order in which a window call runs.  Pure C++,
-// shared by the engine (engine.hip) and the emulator tests (tests/emu/window_emu.cpp, tests/emu/mock_window.cpp), like
+// shared by the engine (engine.hip) and the emulator tests (tests/emu/window_emu.cpp, tests/emu/mock_window.cpp and the _strided files that include them), like
 // wide_plan.h.
 //
 // A window is a strided 2-D view over the element space of one PLANE: chunks chunk_first .. chunk_first + chunk_count - 1 of the
 // batch, read back to back.  Its row r covers elements [origin + r * row_pitch, + width) of the plane and goes to the output at
 // out_off + r * out_pitch.  The planner validates every window before anything runs, then lists the blocks that meet some window
 // row -- each once per window -- as work items.  Chunks whose blocks the window kernel cannot stage (zstd, blocks beyond LDS)
-// are decoded whole through the batch path first and cut from there (copy-mode items).
+// are decoded whole through the batch path first and cut from there (copy-mode items).  A strided window (StridedWindowSpec, for
+// cimg_decode_window_strided) takes every col_pitch-th element of its rows; its planner lists only the blocks that hold a byte of
+// a sampled element, and run_windows and plan_windows_host serve both kinds of window.
 //
 // The host-buffer call (cimg_decompress_windows_host) is planned here too, for the engine and the emulator alike: open_window_call
 // (the opening of both read calls), read_named_headers, stage_chunk and pack_rows (shared with update_plan.h) and plan_windows_host,
@@ -28,22 +30,35 @@ struct WindowSpec {
     int64_t out_off, out_pitch;
 };
 
-struct WindowPlan {
+// = cimg_window_strided (include/cimg_hip.h): element c of row r is plane element origin + r * row_pitch + c * col_pitch
+struct StridedWindowSpec {
+    int32_t chunk_first, chunk_count;
+    int64_t origin;
+    int64_t row_pitch;
+    int64_t col_pitch;
+    int32_t width, height;
+    int64_t out_off, out_pitch;
+};
+
+template <class Item>
+struct WindowPlanT {
     std::vector<ChunkDesc> descs;       // every chunk of the batch (raw_off 0; untouched chunks are never read)
     std::vector<int64_t> plane_start;   // plane byte offset of each chunk in its window's plane (the last window that names it)
     std::vector<uint8_t> touched;       // 1: some window row meets the chunk
     std::vector<uint8_t> whole;         // 1: decoded whole (copy-mode items)
-    std::vector<WindowItem> items;      // decode items (b >= 0) and copy items (b < 0, src_off filled in by the caller)
+    std::vector<Item> items;            // decode items (b >= 0) and copy items (b < 0, src_off filled in by the caller)
     int32_t lds_bytes = 0;              // LDS of the window launch (largest staging among the chunks it decodes block by block)
     int64_t blocks = 0;                 // decode items
 };
+using WindowPlan = WindowPlanT<WindowItem>;
+using StridedWindowPlan = WindowPlanT<StridedWindowItem>;
+template <class Spec> struct PlanOf { using type = WindowPlan; };
+template <> struct PlanOf<StridedWindowSpec> { using type = StridedWindowPlan; };
 
-// nbytes / blocksize / typesize: per chunk, from the chunk headers.  whole_hint[i] = 1: chunk i must be decoded whole (its codec says
-// so; wide blocks are found here).  Chunks outside every window's range are not looked at.
-inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
-                        const WindowSpec* w, const uint8_t* whole_hint, WindowPlan* plan)
+// the start of a plan: nothing listed, one descriptor per chunk of the batch
+template <class Item>
+inline void plan_descs(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const uint8_t* whole_hint, WindowPlanT<Item>* plan)
 {
-    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
     plan->descs.assign((size_t)nchunks, ChunkDesc{});
     plan->plane_start.assign((size_t)nchunks, 0);
     plan->touched.assign((size_t)nchunks, 0);
@@ -51,30 +66,6 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
     plan->items.clear();
     plan->lds_bytes = 0;
     plan->blocks = 0;
-    // validation first: nothing is listed unless every window is good
-    for (int k = 0; k < nwindows; k++) {
-        const WindowSpec& s = w[k];
-        if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
-        if (s.width < 0 || s.height < 0) return ERR_INVALID_PARAM;
-        const int ts = typesize[s.chunk_first];
-        if (ts <= 0) return ERR_INVALID_PARAM;
-        int64_t total = 0;
-        for (int i = s.chunk_first; i < s.chunk_first + s.chunk_count; i++) {
-            if (nbytes[i] < 0 || blocksize[i] <= 0 || (nbytes[i] > 0 && blocksize[i] > nbytes[i])) return ERR_INVALID_HEADER;
-            if (typesize[i] != ts) return ERR_INVALID_PARAM;
-            if (i + 1 < s.chunk_first + s.chunk_count && nbytes[i] % ts) return ERR_INVALID_PARAM;
-            total += nbytes[i];
-        }
-        if (s.width == 0 || s.height == 0) continue;
-        const int64_t elems = total / ts;
-        if (s.height > 1 && s.row_pitch < s.width) return ERR_INVALID_PARAM;
-        if (s.out_pitch < (int64_t)s.width * ts || s.out_off < 0) return ERR_INVALID_PARAM;
-        if (s.origin < 0 || s.origin > elems || s.width > elems) return ERR_INVALID_PARAM;
-        if (s.height > 1 && (s.row_pitch > elems || (int64_t)(s.height - 1) > elems / (s.row_pitch ? s.row_pitch : 1))) return ERR_INVALID_PARAM;
-        const int64_t last = s.origin + (int64_t)(s.height - 1) * (s.height > 1 ? s.row_pitch : 0) + s.width;
-        if (last > elems) return ERR_INVALID_PARAM;
-    }
-    // descriptors
     int32_t blk = 0;
     for (int i = 0; i < nchunks; i++) {
         ChunkDesc& d = plan->descs[(size_t)i];
@@ -86,6 +77,60 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
         d.blk0 = blk;
         blk += d.nblocks;
         plan->whole[(size_t)i] = (whole_hint && whole_hint[i]) || decode_is_wide(d.blocksize);
+    }
+}
+
+// the end of a plan: the launch's LDS and the count of decode items
+template <class Item>
+inline void plan_totals(WindowPlanT<Item>* plan)
+{
+    for (size_t i = 0; i < plan->descs.size(); i++)
+        if (plan->touched[i] && !plan->whole[i]) plan->lds_bytes = imax(plan->lds_bytes, decode_lds_bound(plan->descs[i].blocksize));
+    for (const Item& t : plan->items) if (t.b >= 0) plan->blocks++;
+}
+
+// the plane a window names: its typesize and its size in elements, or the refusal
+inline int plane_of_window(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int chunk_first,
+                           int chunk_count, int* ts_out, int64_t* elems)
+{
+    if (chunk_first < 0 || chunk_count < 1 || chunk_first > nchunks - chunk_count) return ERR_INVALID_PARAM;
+    const int ts = typesize[chunk_first];
+    if (ts <= 0) return ERR_INVALID_PARAM;
+    int64_t total = 0;
+    for (int i = chunk_first; i < chunk_first + chunk_count; i++) {
+        if (nbytes[i] < 0 || blocksize[i] <= 0 || (nbytes[i] > 0 && blocksize[i] > nbytes[i])) return ERR_INVALID_HEADER;
+        if (typesize[i] != ts) return ERR_INVALID_PARAM;
+        if (i + 1 < chunk_first + chunk_count && nbytes[i] % ts) return ERR_INVALID_PARAM;
+        total += nbytes[i];
+    }
+    *ts_out = ts;
+    *elems = total / ts;
+    return 0;
+}
+
+// nbytes / blocksize / typesize: per chunk, from the chunk headers.  whole_hint[i] = 1: chunk i must be decoded whole (its codec says
+// so; wide blocks are found here).  Chunks outside every window's range are not looked at.
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const WindowSpec* w, const uint8_t* whole_hint, WindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    // validation first: nothing is listed unless every window is good
+    for (int k = 0; k < nwindows; k++) {
+        const WindowSpec& s = w[k];
+        if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
+        if (s.width < 0 || s.height < 0) return ERR_INVALID_PARAM;
+        int ts = 0;
+        int64_t elems = 0;
+        const int prc = plane_of_window(nchunks, nbytes, blocksize, typesize, s.chunk_first, s.chunk_count, &ts, &elems);
+        if (prc < 0) return prc;
+        if (s.width == 0 || s.height == 0) continue;
+        if (s.height > 1 && s.row_pitch < s.width) return ERR_INVALID_PARAM;
+        if (s.out_pitch < (int64_t)s.width * ts || s.out_off < 0) return ERR_INVALID_PARAM;
+        if (s.origin < 0 || s.origin > elems || s.width > elems) return ERR_INVALID_PARAM;
+        if (s.height > 1 && (s.row_pitch > elems || (int64_t)(s.height - 1) > elems / (s.row_pitch ? s.row_pitch : 1))) return ERR_INVALID_PARAM;
+        const int64_t last = s.origin + (int64_t)(s.height - 1) * (s.height > 1 ? s.row_pitch : 0) + s.width;
+        if (last > elems) return ERR_INVALID_PARAM;
     }
     // items: rows run forward through the plane, so a block met again by the next row is the window's last item
     for (int k = 0; k < nwindows; k++) {
@@ -128,9 +173,87 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
             }
         }
     }
-    for (int i = 0; i < nchunks; i++)
-        if (plan->touched[(size_t)i] && !plan->whole[(size_t)i]) plan->lds_bytes = imax(plan->lds_bytes, decode_lds_bound(plan->descs[(size_t)i].blocksize));
-    for (const WindowItem& t : plan->items) if (t.b >= 0) plan->blocks++;
+    plan_totals(plan);
+    return 0;
+}
+
+// The strided form.  Validation adds: col_pitch >= 1; with span = (width - 1) * col_pitch + 1 the elements a row reaches over,
+// row_pitch >= span when height > 1 (rows run forward and do not interleave) and origin + (height - 1) * row_pitch + span inside the
+// plane -- every product is bounded by the plane before it is formed.  A block is listed only if it holds a byte of a sampled
+// element: each row walks sample to sample, and from a listed block straight to the first sample that reaches past its end, so
+// the work is min(blocks, samples) per row and the blocks (and chunks) between far-apart samples are never named.
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const StridedWindowSpec* w, const uint8_t* whole_hint, StridedWindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    for (int k = 0; k < nwindows; k++) {
+        const StridedWindowSpec& s = w[k];
+        if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
+        if (s.width < 0 || s.height < 0 || s.col_pitch < 1) return ERR_INVALID_PARAM;
+        int ts = 0;
+        int64_t elems = 0;
+        const int prc = plane_of_window(nchunks, nbytes, blocksize, typesize, s.chunk_first, s.chunk_count, &ts, &elems);
+        if (prc < 0) return prc;
+        if (s.width == 0 || s.height == 0) continue;
+        if (s.out_pitch < (int64_t)s.width * ts || s.out_off < 0) return ERR_INVALID_PARAM;
+        if (s.origin < 0 || s.origin >= elems || s.width > elems) return ERR_INVALID_PARAM;
+        if (s.width > 1 && s.col_pitch > (elems - 1) / (s.width - 1)) return ERR_INVALID_PARAM;       // span > elems
+        const int64_t span = (int64_t)(s.width - 1) * (s.width > 1 ? s.col_pitch : 0) + 1;
+        if (span > elems - s.origin) return ERR_INVALID_PARAM;
+        if (s.height > 1) {
+            if (s.row_pitch < span || s.row_pitch > elems || (int64_t)(s.height - 1) > elems / s.row_pitch) return ERR_INVALID_PARAM;
+            if ((int64_t)(s.height - 1) * s.row_pitch > elems - s.origin - span) return ERR_INVALID_PARAM;
+        }
+    }
+    for (int k = 0; k < nwindows; k++) {
+        const StridedWindowSpec& s = w[k];
+        if (s.width == 0 || s.height == 0) continue;
+        const int ts = typesize[s.chunk_first];
+        const int cf = s.chunk_first, cn = s.chunk_count;
+        std::vector<int64_t> start((size_t)cn + 1, 0);
+        for (int i = 0; i < cn; i++) start[(size_t)i + 1] = start[(size_t)i] + nbytes[cf + i];
+        for (int i = 0; i < cn; i++) plan->plane_start[(size_t)(cf + i)] = start[(size_t)i];
+        const size_t first_item = plan->items.size();
+        const int64_t rpitch = (int64_t)ts * (s.height > 1 ? s.row_pitch : 0), row0 = (int64_t)ts * s.origin;
+        const int64_t cpitch = (int64_t)ts * (s.width > 1 ? s.col_pitch : 1);
+        int ci = 0;
+        for (int r = 0; r < s.height; r++) {
+            const int64_t rs = row0 + (int64_t)r * rpitch;
+            int64_t c = 0;
+            while (c < s.width) {
+                const int64_t pos = rs + c * cpitch;                                 // the sample's bytes: [pos, pos + ts), inside one chunk
+                while (ci + 1 < cn && start[(size_t)ci + 1] <= pos) ci++;
+                const int chunk = cf + ci;
+                const ChunkDesc& d = plan->descs[(size_t)chunk];
+                const int64_t cs = start[(size_t)ci], ce = start[(size_t)ci + 1];
+                plan->touched[(size_t)chunk] = 1;
+                const bool whole = plan->whole[(size_t)chunk] != 0;
+                const int jf = whole ? -1 : (int)((pos - cs) / d.blocksize), jl = whole ? -1 : (int)((pos + ts - 1 - cs) / d.blocksize);
+                for (int j = jf; j <= jl; j++) {
+                    const int b = whole ? -1 : d.blk0 + j;
+                    if (plan->items.size() > first_item) {
+                        StridedWindowItem& last = plan->items.back();
+                        if (last.chunk == chunk && last.b == b) { last.r1 = r + 1; continue; }
+                    }
+                    StridedWindowItem t{};
+                    t.chunk = chunk; t.b = b; t.r0 = r; t.r1 = r + 1;
+                    t.p0 = whole ? cs : cs + (int64_t)j * d.blocksize;
+                    t.len = whole ? d.nbytes : 0;
+                    t.row0 = row0; t.rpitch = rpitch; t.wbytes = (int64_t)ts * s.width;
+                    t.out_off = s.out_off; t.out_pitch = s.out_pitch;
+                    t.cpitch = cpitch; t.ts = ts;
+                    plan->items.push_back(t);
+                }
+                // the first sample with a byte at or past the end of what was just listed
+                int64_t edge = whole ? ce : cs + (int64_t)(jl + 1) * d.blocksize;
+                if (edge > ce) edge = ce;
+                const int64_t next = (edge - ts - rs) / cpitch + 1;                  // (edge >= pos + ts: the numerator is >= 0)
+                c = next > c + 1 ? next : c + 1;
+            }
+        }
+    }
+    plan_totals(plan);
     return 0;
 }
 
@@ -143,14 +266,16 @@ struct WindowStats {
 //       -- the batch path over the listed chunks into its scratch (st: one status per listed chunk); < 0 only when the
 //          device itself failed;
 //   int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status)
-//       -- one window launch over `items`, waited for; a chunk's status word is set when one of its blocks fails.
+//       -- one window launch over `items`, waited for; a chunk's status word is set when one of its blocks fails
+//          (for strided windows: the same over StridedWindowPlan and StridedWindowItem).
 // A zstd chunk is recognised by its header: the host call knows it up front (whole_hint), the device call when its blocks come
 // back pending from the window launch -- those chunks then go the whole-chunk way in a second round.
-template <class Env>
+template <class Env, class Spec>
 int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
-                const WindowSpec* w, std::vector<uint8_t> hint, int32_t* status, WindowStats* stats)
+                const Spec* w, std::vector<uint8_t> hint, int32_t* status, WindowStats* stats)
 {
-    WindowPlan plan;
+    typename PlanOf<Spec>::type plan;
+    using Item = typename decltype(plan.items)::value_type;
     int rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.empty() ? nullptr : hint.data(), &plan);
     if (rc < 0) return rc;
     for (int i = 0; i < nchunks; i++) status[i] = 0;
@@ -172,11 +297,11 @@ int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blo
             for (size_t k = 0; k < list.size(); k++) { status[list[k]] = st[k]; done_whole[(size_t)list[k]] = 1; }
             stats->chunks_whole += (int64_t)list.size();
         }
-        std::vector<WindowItem> items;
-        for (const WindowItem& t : plan.items) {
+        std::vector<Item> items;
+        for (const Item& t : plan.items) {
             if (t.b < 0) {
                 if (at[(size_t)t.chunk] < 0 || status[t.chunk] != 0) continue;          // (a chunk that failed whole: nothing to cut)
-                WindowItem c = t;
+                Item c = t;
                 c.src_off = at[(size_t)t.chunk];
                 items.push_back(c);
             } else if (round == 0) {
@@ -189,7 +314,7 @@ int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blo
         for (int i = 0; i < nchunks; i++)
             if (status[i] == STATUS_ZSTD_PENDING || status[i] == STATUS_ZSTD_PENDING_SPLIT) { pending[(size_t)i] = 1; status[i] = 0; any = true; }
         if (round == 0)
-            for (const WindowItem& t : plan.items) if (t.b >= 0 && !pending[(size_t)t.chunk]) stats->blocks_decoded++;
+            for (const Item& t : plan.items) if (t.b >= 0 && !pending[(size_t)t.chunk]) stats->blocks_decoded++;
         if (!any || round == 1) break;
         // second round: the chunks found to be zstd, decoded whole and cut
         if (hint.empty()) hint.assign((size_t)nchunks, 0);
@@ -231,8 +356,9 @@ struct HostCallPlan {
 };
 
 // The headers of the chunks the windows name (the geometry of their planes); the others are not looked at.
+template <class Spec>
 inline int read_named_headers(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, int nwindows,
-                              const WindowSpec* w, HostCallPlan* hp)
+                              const Spec* w, HostCallPlan* hp)
 {
     const size_t n = (size_t)nchunks;
     hp->named.assign(n, 0); hp->flags.assign(n, 0); hp->version.assign(n, 0);
@@ -265,20 +391,23 @@ inline void stage_chunk(HostCallPlan* hp, int i, int32_t bytes)
 }
 
 // the windows as the device sees them: rows packed (out_pitch = width * typesize); the caller's out_off / out_pitch stay in w
-inline void pack_rows(int nwindows, const WindowSpec* w, const int32_t* typesize, HostCallPlan* hp)
+template <class Spec>
+inline void pack_rows(int nwindows, const Spec* w, const int32_t* typesize, HostCallPlan* hp, std::vector<Spec>* dw)
 {
-    hp->dw.assign(w, w + nwindows);
+    dw->assign(w, w + nwindows);
     hp->wbytes.assign((size_t)nwindows, 0);
     for (int k = 0; k < nwindows; k++) {
         if (w[k].width <= 0 || w[k].height <= 0) continue;
         const int64_t row = (int64_t)w[k].width * typesize[w[k].chunk_first];
-        hp->dw[(size_t)k].out_off = hp->rows_total;
-        hp->dw[(size_t)k].out_pitch = row;
+        (*dw)[(size_t)k].out_off = hp->rows_total;
+        (*dw)[(size_t)k].out_pitch = row;
         hp->wbytes[(size_t)k] = row * w[k].height;
         hp->rows_used = hp->rows_total + hp->wbytes[(size_t)k];
         hp->rows_total += (hp->wbytes[(size_t)k] + 255) & ~255ll;
     }
 }
+
+inline void pack_rows(int nwindows, const WindowSpec* w, const int32_t* typesize, HostCallPlan* hp) { pack_rows(nwindows, w, typesize, hp, &hp->dw); }
 
 struct WindowHostPlan : HostCallPlan {
     std::vector<uint8_t> hint;          // 1: a zstd chunk, decoded whole
@@ -286,14 +415,16 @@ struct WindowHostPlan : HostCallPlan {
 
 // cimg_decompress_windows_host: the chunks some window row meets get their full header checks (a refusal is that chunk's status
 // word and the call's code), then only they are staged.  ERR_INVALID_PARAM with bad_window < 0: plan_windows refused a window.
+// (dw: the packed windows -- hp->dw, or the strided call's list)
+template <class Spec>
 inline int plan_windows_host(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, int nwindows,
-                             const WindowSpec* w, int32_t* status, WindowHostPlan* hp)
+                             const Spec* w, int32_t* status, WindowHostPlan* hp, std::vector<Spec>* dw)
 {
     int rc = read_named_headers(nchunks, comp, comp_off, comp_size, nwindows, w, hp);
     if (rc < 0) return rc;
     hp->hint.assign((size_t)nchunks, 0);
     for (int i = 0; i < nchunks; i++) hp->hint[(size_t)i] = (hp->flags[(size_t)i] >> 5) == 4 && !(hp->flags[(size_t)i] & FLAG_MEMCPYED);
-    WindowPlan plan;
+    typename PlanOf<Spec>::type plan;
     if ((rc = plan_windows(nchunks, hp->nbytes.data(), hp->blocksize.data(), hp->typesize.data(), nwindows, w, hp->hint.data(), &plan)) < 0) return rc;
     for (int i = 0; i < nchunks; i++) {
         if (!plan.touched[(size_t)i]) continue;
@@ -305,8 +436,13 @@ inline int plan_windows_host(int nchunks, const uint8_t* comp, const int64_t* co
         if (code) { status[i] = code; hp->bad_chunk = i; return code; }
         stage_chunk(hp, i, cb);
     }
-    pack_rows(nwindows, w, hp->typesize.data(), hp);
+    pack_rows(nwindows, w, hp->typesize.data(), hp, dw);
     return 0;
+}
+inline int plan_windows_host(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size, int nwindows,
+                             const WindowSpec* w, int32_t* status, WindowHostPlan* hp)
+{
+    return plan_windows_host(nchunks, comp, comp_off, comp_size, nwindows, w, status, hp, &hp->dw);
 }
 
 }  // namespace cimg

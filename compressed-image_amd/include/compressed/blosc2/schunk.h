@@ -201,6 +201,73 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					}
 				}
 
+				/// The subsampled form: of the rectangle (x, y, w, h), every sy-th row and every sx-th element of those rows (sx, sy >= 1)
+				/// go to `out`, ceil(w / sx) elements a row, rows `out_pitch` elements apart.  Runs of chunks become windows as above,
+				/// with col_pitch = sx and row_pitch = sy * row_len; a partial row is cut at the first and last sample inside its run.
+				void plan_region(T* out, size_t out_pitch, size_t row_len, size_t x, size_t y, size_t w, size_t h, size_t sx, size_t sy,
+					batch::strided_window_job& job) const
+				{
+					if (w == 0 || h == 0) return;
+					const size_t ow = (w + sx - 1) / sx, oh = (h + sy - 1) / sy;
+					const size_t span = (ow - 1) * sx + 1, rp = sy * row_len;           // elements a sampled row reaches over; between rows
+					auto row_start = [&](size_t r) { return (y + r * sy) * row_len + x; };
+					size_t cs = 0;
+					for (size_t i = 0; i < m_Chunks.size();)
+					{
+						const bool lazy = m_Chunks[i].is_lazy();
+						size_t j = i, ce = cs;
+						while (j < m_Chunks.size() && m_Chunks[j].is_lazy() == lazy) { ce += m_Chunks[j].num_elements; ++j; if (lazy) break; }
+						// sampled rows [r0, r1) meet the run [cs, ce); of row r, the samples [ca, cb) lie inside it
+						const size_t r0 = row_start(0) + span > cs ? 0 : (cs - row_start(0) - span) / rp + 1;
+						size_t r1 = oh;
+						if (row_start(0) >= ce) r1 = 0;
+						else if (row_start(oh - 1) >= ce) r1 = (ce - row_start(0) + rp - 1) / rp;
+						auto samples = [&](size_t r, size_t& ca, size_t& cb) {
+							const size_t s = row_start(r);
+							ca = s >= cs ? 0 : (cs - s + sx - 1) / sx;
+							cb = s + span <= ce ? ow : (ce > s ? (ce - s + sx - 1) / sx : 0);
+						};
+						if (lazy)
+						{
+							const T v = std::get<T>(m_Chunks[i].value);
+							for (size_t r = r0; r < r1; ++r)
+							{
+								size_t ca, cb;
+								samples(r, ca, cb);
+								if (ca < cb) std::fill(out + r * out_pitch + ca, out + r * out_pitch + cb, v);
+							}
+						}
+						else if (r0 < r1)
+						{
+							const int32_t first = static_cast<int32_t>(job.chunks.size());
+							for (size_t k = i; k < j; ++k) { job.chunks.push_back(m_Chunks[k].bytes().data()); job.held.push_back(m_Chunks[k].bytes().size()); }
+							auto add = [&](size_t ra, size_t rb, bool partial) {
+								if (ra >= rb) return;
+								size_t ca = 0, cb = ow;
+								if (partial) samples(ra, ca, cb);
+								if (ca >= cb) return;                                       // (no sample of the partial row lies in this run)
+								cimg_window_strided win{};
+								win.chunk_first = first;
+								win.chunk_count = static_cast<int32_t>(j - i);
+								win.origin = static_cast<int64_t>(row_start(ra) + ca * sx - cs);
+								win.row_pitch = static_cast<int64_t>(rp);
+								win.col_pitch = static_cast<int64_t>(sx);
+								win.width = static_cast<int32_t>(cb - ca);
+								win.height = static_cast<int32_t>(rb - ra);
+								win.out_pitch = static_cast<int64_t>(out_pitch * sizeof(T));
+								job.windows.push_back(win);
+								job.outs.push_back(reinterpret_cast<std::byte*>(out + ra * out_pitch + ca));
+							};
+							size_t ra = r0, rb = r1;
+							if (row_start(ra) < cs) { add(ra, ra + 1, true); ++ra; }
+							if (rb > ra && row_start(rb - 1) + span > ce) { --rb; add(rb, rb + 1, true); }
+							add(ra, rb, false);
+						}
+						cs = ce;
+						i = j;
+					}
+				}
+
 				/// What set_region changes in a table: the compressed chunks it queued (job index -> chunk index) and the lazy chunks
 				/// the rectangle meets, filled and patched on the host.
 				struct region_write

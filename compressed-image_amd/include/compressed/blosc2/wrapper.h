@@ -334,15 +334,32 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			// Windows of several planes in one engine call (cimg_decompress_windows_host): only the blocks the windows meet are decoded
 			// and only the windows' bytes come back.  windows[i] names chunks by their index in `chunks`; its out_off is filled in
 			// here from outs[i], where its first element goes.
-			struct window_job
+			// (Window: cimg_window, or cimg_window_strided for subsampled regions -- cimg_decompress_windows_strided_host decodes only
+			// the blocks that hold a sampled element.)
+			template <typename Window>
+			struct window_job_of
 			{
 				std::vector<const std::byte*> chunks;
 				std::vector<size_t> held;               // bytes each chunk buffer holds
-				std::vector<cimg_window> windows;
+				std::vector<Window> windows;
 				std::vector<std::byte*> outs;
 			};
+			using window_job = window_job_of<cimg_window>;
+			using strided_window_job = window_job_of<cimg_window_strided>;
 
-			inline void decompress_windows(window_job& job)
+			inline int decompress_windows_call(int32_t n, const void* comp, const int64_t* comp_off, const int32_t* held, int32_t nwindows,
+				const cimg_window* w, void* out, int32_t* status)
+			{
+				return cimg_decompress_windows_host(engine(), n, comp, comp_off, held, nwindows, w, out, status);
+			}
+			inline int decompress_windows_call(int32_t n, const void* comp, const int64_t* comp_off, const int32_t* held, int32_t nwindows,
+				const cimg_window_strided* w, void* out, int32_t* status)
+			{
+				return cimg_decompress_windows_strided_host(engine(), n, comp, comp_off, held, nwindows, w, out, status);
+			}
+
+			template <typename Window>
+			inline void decompress_windows(window_job_of<Window>& job)
 			{
 				if (job.windows.empty()) return;
 				const std::byte* cbase = job.chunks.empty() ? nullptr : job.chunks[0];
@@ -360,7 +377,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					held[i] = static_cast<int32_t>(job.held[i]);
 				}
 				for (size_t k = 0; k < job.windows.size(); ++k) job.windows[k].out_off = job.outs[k] - obase;
-				const int rc = cimg_decompress_windows_host(engine(), static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+				const int rc = decompress_windows_call(static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
 					static_cast<int32_t>(job.windows.size()), job.windows.data(), obase, status.data());
 				if (rc < 0)
 					throw std::runtime_error(detail::text("Error code ", rc, " while decompressing a region of blosc2 chunks (", cimg_last_error(engine()), ")"));

@@ -154,6 +154,27 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			plan_region(out.data(), width, x, y, width, height, job);
 			blosc2::batch::decompress_windows(job);
 		}
+		/// The rectangle subsampled: every step_y-th row of it and every step_x-th element of those rows, ceil(height / step_y) rows
+		/// of ceil(width / step_x) elements -- what a[y:y+height:step_y, x:x+width:step_x] is.  Only the blocks that hold a sampled
+		/// element are decoded, and only the samples come back.
+		std::vector<T> get_region(size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y) const
+		{
+			check_steps(step_x, step_y);
+			std::vector<T> out(((width + step_x - 1) / step_x) * ((height + step_y - 1) / step_y));
+			get_region(std::span<T>(out), x, y, width, height, step_x, step_y);
+			return out;
+		}
+		void get_region(std::span<T> out, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y) const
+		{
+			check_region(x, y, width, height);
+			check_steps(step_x, step_y);
+			const size_t ow = (width + step_x - 1) / step_x, oh = (height + step_y - 1) / step_y;
+			if (out.size() < ow * oh)
+				throw std::invalid_argument(detail::text("get_region: buffer holds ", out.size(), " elements, the subsampled region has ", ow * oh));
+			blosc2::batch::strided_window_job job;
+			plan_region(out.data(), ow, x, y, width, height, step_x, step_y, job);
+			blosc2::batch::decompress_windows(job);
+		}
 		/// Write `data` (width * height elements, row-major) over the rectangle [x, x + width) x [y, y + height).  Only the blocks
 		/// the rectangle meets are decoded and re-encoded, on the device; the result is what compressing the edited pixels from
 		/// scratch gives.  Lazy chunks the rectangle meets become real.  Nothing changes unless the whole call succeeds.
@@ -188,6 +209,15 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		void plan_region(T* out, size_t out_pitch, size_t x, size_t y, size_t width, size_t height, blosc2::batch::window_job& job) const
 		{
 			visit([&](const auto& s) { s.plan_region(out, out_pitch, m_Width, x, y, width, height, job); return 0; });
+		}
+		void plan_region(T* out, size_t out_pitch, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y,
+			blosc2::batch::strided_window_job& job) const
+		{
+			visit([&](const auto& s) { s.plan_region(out, out_pitch, m_Width, x, y, width, height, step_x, step_y, job); return 0; });
+		}
+		static void check_steps(size_t step_x, size_t step_y)
+		{
+			if (step_x == 0 || step_y == 0) throw std::invalid_argument("get_region: step_x and step_y must be at least 1");
 		}
 		void check_region(size_t x, size_t y, size_t width, size_t height) const
 		{

@@ -297,6 +297,22 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)), 1, &w, d_out, status.data()),
 				"Decoding the region");
 		}
+		/// The rectangle subsampled into device memory: ceil(height / step_y) rows of ceil(width / step_x) elements, every step_y-th
+		/// row and every step_x-th element of it.  Only the blocks that hold a sampled element are decoded.
+		void get_region(T* d_out, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y) const
+		{
+			check_region(x, y, width, height);
+			check_steps(step_x, step_y);
+			require();
+			if (width == 0 || height == 0) return;
+			cimg_engine* e = m_Store->engine;
+			const cimg_window_strided w = region_window(x, y, width, height, step_x, step_y, 0);
+			detail::device_range(e, d_out, static_cast<size_t>(w.width) * static_cast<size_t>(w.height) * sizeof(T), "get_region");
+			std::vector<int32_t> status(m_Store->num_chunks(), 0);
+			detail::engine_call(e, cimg_decompress_windows_strided_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base,
+				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)), 1, &w,
+				d_out, status.data()), "Decoding the subsampled region");
+		}
 		/// Write `d_src` (width * height elements in device memory, row-major) over the rectangle.  Only the blocks it meets are decoded
 		/// and re-encoded; the store is then repacked into a new exact-size allocation (untouched chunks from the old one).
 		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)
@@ -315,6 +331,10 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			if (x > m_Width || y > m_Height || width > m_Width - x || height > m_Height - y)
 				throw std::out_of_range(detail::text("Region (x ", x, ", y ", y, ", width ", width, ", height ", height, ") is out of bounds for a channel of ",
 					m_Width, " x ", m_Height));
+		}
+		static void check_steps(size_t step_x, size_t step_y)
+		{
+			if (step_x == 0 || step_y == 0) throw std::invalid_argument("get_region: step_x and step_y must be at least 1");
 		}
 		/// The codec parameters the chunks were made with (what set_region hands the engine).
 		cimg_cparams cparams() const
@@ -337,6 +357,22 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			w.height = static_cast<int32_t>(height);
 			w.out_off = static_cast<int64_t>(out_off);
 			w.out_pitch = static_cast<int64_t>(width * sizeof(T));
+			return w;
+		}
+
+		/// The rectangle subsampled, as a strided window: ceil(height / step_y) rows of ceil(width / step_x) elements, dense in the output.
+		cimg_window_strided region_window(size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, size_t out_off) const
+		{
+			cimg_window_strided w{};
+			w.chunk_first = static_cast<int32_t>(m_First);
+			w.chunk_count = static_cast<int32_t>(m_Count);
+			w.origin = static_cast<int64_t>(y * m_Width + x);
+			w.row_pitch = static_cast<int64_t>(step_y * m_Width);
+			w.col_pitch = static_cast<int64_t>(step_x);
+			w.width = static_cast<int32_t>((width + step_x - 1) / step_x);
+			w.height = static_cast<int32_t>((height + step_y - 1) / step_y);
+			w.out_off = static_cast<int64_t>(out_off);
+			w.out_pitch = static_cast<int64_t>(static_cast<size_t>(w.width) * sizeof(T));
 			return w;
 		}
 

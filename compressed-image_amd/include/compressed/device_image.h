@@ -159,6 +159,40 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				detail::engine_call(e, cimg_interleave_device(e, scratch.base, static_cast<int64_t>(stride), static_cast<int32_t>(m_NumChannels),
 					static_cast<int32_t>(sizeof(T)), static_cast<int64_t>(width * height), d_out), "Interleaving the region");
 		}
+		/// The rectangle of every channel subsampled (every step_y-th row, every step_x-th element of it) in ONE strided windows call:
+		/// planes (C, oh, ow) with oh = ceil(height / step_y), ow = ceil(width / step_x), or with `interleaved` pixels (oh, ow, C).
+		void get_region(T* d_out, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, bool interleaved = false) const
+		{
+			prototype().check_region(x, y, width, height);
+			device_channel<T>::check_steps(step_x, step_y);
+			if (m_NumChannels == 0 || width == 0 || height == 0) return;
+			cimg_engine* e = m_Store->engine;
+			const size_t ow = (width + step_x - 1) / step_x, oh = (height + step_y - 1) / step_y;
+			const size_t plane = ow * oh * sizeof(T);
+			detail::device_range(e, d_out, plane * m_NumChannels, "get_region");
+			const bool il = interleaved && m_NumChannels > 1;                  // (one channel: planes and pixels are the same bytes)
+			if (il && (reinterpret_cast<uintptr_t>(d_out) & 15)) throw std::invalid_argument("get_region: an interleaved result must be 16-byte aligned");
+			const size_t stride = il ? blosc2::batch::planar_stride(ow * oh, sizeof(T)) : plane;
+			detail::device_store scratch;
+			if (il) scratch.allocate(e, stride * m_NumChannels + 64);
+			std::vector<cimg_window_strided> w;
+			for (size_t c = 0; c < m_NumChannels; ++c)
+			{
+				device_channel<T> p = prototype();
+				p.m_First = c * chunks_per_channel();
+				p.m_Count = chunks_per_channel();
+				w.push_back(p.region_window(x, y, width, height, step_x, step_y, c * stride));
+			}
+			std::vector<int32_t> status(m_Store->num_chunks(), 0);
+			detail::engine_lock lock(e);
+			detail::engine_call(e, cimg_decompress_windows_strided_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base,
+				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)),
+				static_cast<int32_t>(w.size()), w.data(), il ? static_cast<void*>(scratch.base) : static_cast<void*>(d_out), status.data()),
+				"Decoding the subsampled region");
+			if (il)
+				detail::engine_call(e, cimg_interleave_device(e, scratch.base, static_cast<int64_t>(stride), static_cast<int32_t>(m_NumChannels),
+					static_cast<int32_t>(sizeof(T)), static_cast<int64_t>(ow * oh), d_out), "Interleaving the region");
+		}
 		/// Write planes (num_channels x height x width elements in device memory, channel-major) over the rectangle of every channel:
 		/// one update call, one repack of the store.  Nothing changes unless the whole call succeeds.
 		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)

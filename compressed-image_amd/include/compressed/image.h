@@ -203,6 +203,24 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return out;
 		}
 
+		/// The rectangle of every channel subsampled (channel<T>::get_region with steps): one engine call that decodes only the
+		/// blocks that hold a sampled element.
+		std::vector<std::vector<T>> get_region(size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y) const
+		{
+			if (step_x == 0 || step_y == 0) throw std::invalid_argument("get_region: step_x and step_y must be at least 1");
+			const size_t ow = (width + step_x - 1) / step_x, oh = (height + step_y - 1) / step_y;
+			std::vector<std::vector<T>> out(m_Channels.size());
+			blosc2::batch::strided_window_job job;
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				m_Channels[ch].check_region(x, y, width, height);
+				out[ch].resize(ow * oh);
+				m_Channels[ch].plan_region(out[ch].data(), ow, x, y, width, height, step_x, step_y, job);
+			}
+			blosc2::batch::decompress_windows(job);
+			return out;
+		}
+
 		/// Write one span per channel (width * height elements each, row-major) over the rectangle of every channel: one engine call
 		/// for all channels that share their codec parameters.  Nothing changes unless the whole call succeeds.
 		void set_region(const std::vector<std::span<const T>>& data, size_t x, size_t y, size_t width, size_t height)

@@ -90,6 +90,58 @@ namespace
 		return py::array(np_dtype<T>(), std::move(shape), heap->data(), owner);
 	}
 
+	// ---- subsampled regions and numpy-style keys ----------------------------------------------------------
+	inline void check_steps(py::ssize_t step_x, py::ssize_t step_y)
+	{
+		if (step_x < 1 || step_y < 1) throw py::value_error("step_x and step_y must be >= 1");
+	}
+	inline py::ssize_t ceil_div(py::ssize_t a, py::ssize_t b) { return (a + b - 1) / b; }
+
+	// one axis of a key: `count` elements from `start`, `step` apart; an integer drops its axis
+	struct axis_pick { py::ssize_t start = 0, count = 0, step = 1; bool drop = false; };
+	inline axis_pick pick_axis(const py::handle& k, py::ssize_t len)
+	{
+		axis_pick a;
+		if (py::isinstance<py::slice>(k))
+		{
+			py::ssize_t start = 0, stop = 0, step = 1, n = 0;
+			if (!py::reinterpret_borrow<py::slice>(k).compute(len, &start, &stop, &step, &n)) throw py::error_already_set();
+			if (step < 1) throw py::value_error("negative slice steps are not supported");
+			a.start = n > 0 ? start : 0; a.count = n; a.step = n > 1 ? step : 1;
+			return a;
+		}
+		if (k.is_none()) throw py::type_error("None (numpy.newaxis) is not supported as an index");
+		if (k.ptr() == Py_Ellipsis) throw py::type_error("Ellipsis is not supported as an index");
+		if (py::isinstance<py::bool_>(k) || !PyIndex_Check(k.ptr()))
+			throw py::type_error("indices must be integers or slices (index arrays, masks and lists are not supported)");
+		const py::ssize_t i = PyNumber_AsSsize_t(k.ptr(), PyExc_IndexError);
+		if (i == -1 && PyErr_Occurred()) throw py::error_already_set();
+		if (i < -len || i >= len) throw py::index_error("index " + std::to_string(i) + " is out of bounds for an axis of size " + std::to_string(len));
+		a.start = i < 0 ? i + len : i; a.count = 1; a.drop = true;
+		return a;
+	}
+
+	// a[key] of a (height, width) channel as a strided region: the source rectangle, the steps and the result's shape
+	struct region_pick { py::ssize_t x = 0, y = 0, w = 0, h = 0, sx = 1, sy = 1; std::vector<py::ssize_t> shape; };
+	inline region_pick pick_region(const py::object& key, py::ssize_t height, py::ssize_t width)
+	{
+		py::object rk = key, ck = py::slice(py::none(), py::none(), py::none());
+		if (py::isinstance<py::tuple>(key))
+		{
+			const py::tuple t = key;
+			if (t.size() > 2) throw py::index_error("too many indices: a channel has 2 dimensions, " + std::to_string(t.size()) + " were indexed");
+			rk = t.size() > 0 ? py::object(t[0]) : ck;
+			if (t.size() > 1) ck = t[1];
+		}
+		const axis_pick r = pick_axis(rk, height), c = pick_axis(ck, width);
+		region_pick p;
+		p.y = r.start; p.sy = r.step; p.h = r.count > 0 ? (r.count - 1) * r.step + 1 : 0;
+		p.x = c.start; p.sx = c.step; p.w = c.count > 0 ? (c.count - 1) * c.step + 1 : 0;
+		if (!r.drop) p.shape.push_back(r.count);
+		if (!c.drop) p.shape.push_back(c.count);
+		return p;
+	}
+
 	// ---- Channel ------------------------------------------------------------------------------------------
 	template <typename T> using chan_ptr = std::shared_ptr<compressed::channel<T>>;
 	using any_channel = std::variant<chan_ptr<compressed::half>, chan_ptr<float>, chan_ptr<double>, chan_ptr<uint8_t>, chan_ptr<int8_t>,
@@ -100,6 +152,19 @@ namespace
 		any_channel impl;
 
 		template <typename F> auto visit(F&& f) const { return std::visit([&](auto& p) { return f(*p); }, impl); }
+
+		// a[key] for key = a row index or slice, or a 2-tuple of those, as numpy has it (positive steps only)
+		py::array getitem(const py::object& key) const
+		{
+			return visit([&]<typename T>(compressed::channel<T>& ch) {
+				const region_pick p = pick_region(key, static_cast<py::ssize_t>(ch.height()), static_cast<py::ssize_t>(ch.width()));
+				py::array out(np_dtype<T>(), p.shape);
+				if (out.size() == 0) return out;
+				ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(out.size())), static_cast<size_t>(p.x),
+					static_cast<size_t>(p.y), static_cast<size_t>(p.w), static_cast<size_t>(p.h), static_cast<size_t>(p.sx), static_cast<size_t>(p.sy));
+				return out;
+			});
+		}
 
 		static Channel from_array(const py::array& data, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk)
 		{
@@ -169,14 +234,24 @@ namespace
 		}
 
 		// the rectangle (x, y, width, height) as a (height, width) array: only the blocks it meets are decoded
-		py::array get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height) const
+		// (step_x, step_y > 1: every step_y-th row and every step_x-th element of it, a (ceil(height / step_y), ceil(width / step_x)) array;
+		// only the blocks that hold a sampled element are decoded)
+		py::array get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, py::ssize_t step_x, py::ssize_t step_y) const
 		{
 			if (x < 0 || y < 0 || width < 0 || height < 0) throw py::value_error("region coordinates and sizes must be >= 0");
+			check_steps(step_x, step_y);
 			return visit([&]<typename T>(compressed::channel<T>& ch) {
 				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
-				py::array out(np_dtype<T>(), std::vector<py::ssize_t>{ height, width });
-				ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(width * height)), static_cast<size_t>(x),
-					static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				if (step_x == 1 && step_y == 1)
+				{
+					py::array out(np_dtype<T>(), std::vector<py::ssize_t>{ height, width });
+					ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(width * height)), static_cast<size_t>(x),
+						static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+					return out;
+				}
+				py::array out(np_dtype<T>(), std::vector<py::ssize_t>{ ceil_div(height, step_y), ceil_div(width, step_x) });
+				ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(out.size())), static_cast<size_t>(x),
+					static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height), static_cast<size_t>(step_x), static_cast<size_t>(step_y));
 				return out;
 			});
 		}
@@ -278,9 +353,25 @@ namespace
 			return out;
 		}
 		// the rectangle of every channel, one engine call: a list of (height, width) arrays
-		py::list get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height) const
+		py::list get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, py::ssize_t step_x, py::ssize_t step_y) const
 		{
 			if (x < 0 || y < 0 || width < 0 || height < 0) throw py::value_error("region coordinates and sizes must be >= 0");
+			check_steps(step_x, step_y);
+			if (step_x > 1 || step_y > 1)
+				return visit([&]<typename T>(const img_ptr<T>& img) {
+					compressed::blosc2::batch::strided_window_job job;
+					py::list out;
+					for (const auto& ch : img->channels())
+					{
+						ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+						py::array a(np_dtype<T>(), std::vector<py::ssize_t>{ ceil_div(height, step_y), ceil_div(width, step_x) });
+						ch.plan_region(static_cast<T*>(a.mutable_data()), static_cast<size_t>(a.shape(1)), static_cast<size_t>(x), static_cast<size_t>(y),
+							static_cast<size_t>(width), static_cast<size_t>(height), static_cast<size_t>(step_x), static_cast<size_t>(step_y), job);
+						out.append(a);
+					}
+					compressed::blosc2::batch::decompress_windows(job);
+					return out;
+				});
 			return visit([&]<typename T>(const img_ptr<T>& img) {
 				compressed::blosc2::batch::window_job job;
 				std::vector<py::array> arrays;
@@ -391,7 +482,7 @@ namespace
 			nbytes = static_cast<size_t>(dt.itemsize());
 			for (auto d : shape) nbytes *= static_cast<size_t>(d);
 			cimg_engine* e = compressed::blosc2::batch::engine();
-			void* p = cimg_device_malloc(e, nbytes);
+			void* p = cimg_device_malloc(e, std::max<size_t>(nbytes, 1));        // (an empty selection still has an address)
 			if (!p) throw std::runtime_error(std::string("Unable to allocate device memory: ") + cimg_last_error(e));
 			mem = std::shared_ptr<void>(p, [e](void* q) { cimg_device_free(e, q); });
 		}
@@ -474,14 +565,32 @@ namespace
 				return ret;
 			});
 		}
-		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, std::optional<uintptr_t> stream) const
+		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, std::optional<uintptr_t> stream,
+			py::ssize_t step_x, py::ssize_t step_y) const
 		{
 			check_region_args(x, y, width, height);
+			check_steps(step_x, step_y);
 			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
 				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
-				auto [p, ret] = result_target<T>(out, { height, width }, "get_region");
+				auto [p, ret] = result_target<T>(out, { ceil_div(height, step_y), ceil_div(width, step_x) }, "get_region");
 				wait_for(stream);
-				ch.get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				if (step_x == 1 && step_y == 1)
+					ch.get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				else
+					ch.get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height),
+						static_cast<size_t>(step_x), static_cast<size_t>(step_y));
+				return ret;
+			});
+		}
+		// a[key] as Channel.__getitem__ has it, into a new DeviceArray
+		py::object getitem(const py::object& key) const
+		{
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				const region_pick p = pick_region(key, static_cast<py::ssize_t>(ch.height()), static_cast<py::ssize_t>(ch.width()));
+				auto [d, ret] = result_target<T>(py::none(), p.shape, "__getitem__");
+				if (p.w > 0 && p.h > 0)
+					ch.get_region(d, static_cast<size_t>(p.x), static_cast<size_t>(p.y), static_cast<size_t>(p.w), static_cast<size_t>(p.h),
+						static_cast<size_t>(p.sx), static_cast<size_t>(p.sy));
 				return ret;
 			});
 		}
@@ -581,15 +690,20 @@ namespace
 			});
 		}
 		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, bool interleaved,
-			std::optional<uintptr_t> stream) const
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y) const
 		{
 			check_region_args(x, y, width, height);
+			check_steps(step_x, step_y);
 			return visit([&]<typename T>(const dimg_ptr<T>& img) {
 				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
-				const py::ssize_t C = static_cast<py::ssize_t>(img->num_channels());
-				auto [p, ret] = result_target<T>(out, interleaved ? std::vector<py::ssize_t>{ height, width, C } : std::vector<py::ssize_t>{ C, height, width }, "get_region");
+				const py::ssize_t C = static_cast<py::ssize_t>(img->num_channels()), oh = ceil_div(height, step_y), ow = ceil_div(width, step_x);
+				auto [p, ret] = result_target<T>(out, interleaved ? std::vector<py::ssize_t>{ oh, ow, C } : std::vector<py::ssize_t>{ C, oh, ow }, "get_region");
 				wait_for(stream);
-				img->get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height), interleaved);
+				if (step_x == 1 && step_y == 1)
+					img->get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height), interleaved);
+				else
+					img->get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height),
+						static_cast<size_t>(step_x), static_cast<size_t>(step_y), interleaved);
 				return ret;
 			});
 		}
@@ -655,7 +769,9 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_chunk", &Channel::get_chunk_into, py::arg("chunk_index"), py::arg("array"))
 		.def("set_chunk", &Channel::set_chunk, py::arg("chunk_index"), py::arg("array"))
 		.def("get_decompressed", &Channel::get_decompressed)
-		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"))
+		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1,
+			py::arg("step_y") = 1)
+		.def("__getitem__", &Channel::getitem, py::arg("key"))
 		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"));
 
 	py::class_<Image>(m, "Image", py::module_local())
@@ -670,7 +786,8 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("channel", &Image::channel, py::arg("key"))
 		.def("channels", &Image::channels)
 		.def("get_decompressed", &Image::get_decompressed)
-		.def("get_region", &Image::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"))
+		.def("get_region", &Image::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1,
+			py::arg("step_y") = 1)
 		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("print_statistics", [](const Image& i) { i.visit([](auto& img) { img->print_statistics(); return 0; }); })
@@ -719,7 +836,8 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("read_only", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.read_only(); }); })
 		.def("get_decompressed", &DeviceChannel::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceChannel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
-			py::arg("stream") = std::nullopt)
+			py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
 		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt);
 
 	py::class_<DeviceImage>(m, "DeviceImage", py::module_local())
@@ -736,7 +854,7 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("channel", &DeviceImage::channel, py::arg("key"))
 		.def("get_decompressed", &DeviceImage::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceImage::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
-			py::arg("interleaved") = false, py::arg("stream") = std::nullopt)
+			py::arg("interleaved") = false, py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
 		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt)
 		.def("get_channel_index", [](const DeviceImage& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("get_channel_names", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->channelnames(); }); })

@@ -202,6 +202,32 @@ int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_
  * call only).  Any pointer may be NULL. */
 void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded);
 
+/* Strided windows: a window whose rows take every col_pitch-th element -- a subsampled region, a[y0:y1:sy, x0:x1:sx] of a W-wide
+ * channel being origin = y0 * W + x0, row_pitch = sy * W, col_pitch = sx.  Element c of row r is plane element
+ * origin + r * row_pitch + c * col_pitch and goes to out + out_off + r * out_pitch + c * typesize: output rows are dense.  Only the
+ * blocks that hold a byte of a sampled element are decoded (with col_pitch * typesize >= blocksize, most blocks between a row's
+ * first and last sample are not), and only chunks that hold such a block are read or, by the host call, uploaded.  The rules of
+ * cimg_window hold, with these in place of "row_pitch < width": col_pitch < 1 is BLOSC2_ERROR_INVALID_PARAM; with
+ * span = (width - 1) * col_pitch + 1, a window of height > 1 needs row_pitch >= span (rows run forward and do not interleave), and
+ * origin + (height - 1) * row_pitch + span must lie inside the plane.  A window with col_pitch 1 gives the bytes, status and stats
+ * of the same cimg_window.  Locking, the voiding of pending _begin calls, status and return values are those of the two calls
+ * above, and cimg_engine_window_stats reports on these calls too. */
+typedef struct cimg_window_strided {
+    int32_t chunk_first, chunk_count;
+    int64_t origin;
+    int64_t row_pitch;
+    int64_t col_pitch;                  /* elements between consecutive elements of a window row in the plane; >= 1 */
+    int32_t width, height;              /* elements per OUTPUT row, rows */
+    int64_t out_off, out_pitch;
+} cimg_window_strided;
+int cimg_decompress_windows_strided_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                           const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize,
+                                           int32_t typesize, int32_t nwindows, const cimg_window_strided* w, void* d_out,
+                                           int32_t* status);
+int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
+                                         int32_t* status);
+
 /* ---- window writes: edit compressed planes in place of get_chunk + set_chunk ------------------------
  * The windows are cimg_window, with out_off / out_pitch describing the SOURCE: row r of a window is taken from
  * src + out_off + r * out_pitch.  Windows apply in call order (a later window wins where two overlap).  Every touched chunk's new
@@ -302,7 +328,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* window writes: stage-and-patch, splice layout, splice copy */
        CIMG_K_UPDATE_PATCH = 17, CIMG_K_UPDATE_LAYOUT = 18, CIMG_K_UPDATE_EMIT = 19,
        /* packed device storage: the batched gather copy, planes -> interleaved pixels */
-       CIMG_K_PACK = 20, CIMG_K_INTERLEAVE = 21, CIMG_K_COUNT = 22 };
+       CIMG_K_PACK = 20, CIMG_K_INTERLEAVE = 21,
+       /* the window launch of cimg_decompress_windows_strided_device / _host */
+       CIMG_K_DECODE_WINDOW_STRIDED = 22, CIMG_K_COUNT = 23 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

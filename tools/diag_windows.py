@@ -10,13 +10,25 @@ Write legs, each against what it replaces, the chunk roun
       wall time; the stats of the update (blocks staged / re-encoded);
   (4) the Python module: Channel.set_region of a 64^2 and a 512^2 window at (1024, 1024) into a 4096^2 float16 channel against
       get_chunk(2) + numpy edit + set_chunk(2), wall time; and the bytes the host call uploads (cimg_update_windows_host).
+Strided leg (second table), against the route it replaces:
+  (5) the 16 x 16 subsample of the device-resident plane of (1) (cimg_decompress_windows_strided_device: 1024 rows of 1024 elements,
+      2048 blocks) against cimg_decompress_batch_device_sized of the whole plane plus a device strided copy of the same subsample
+      (torch: full[::16, ::16].contiguous()) -- kernel time (HIP events of the engine, torch events for the copy) and wall time.
+      It runs in a child process (`--strided-leg`) that imports torch first, so that torch and the engine share one HIP runtime;
+      and the Python module: Channel.get_region(0, 0, 4096, 4096, step_x=8, step_y=8) on the 4096^2 float16 channel of (2) against
+      get_decompressed()[::8, ::8], wall time.
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
 import os
+import subprocess
 import sys
 import sysconfig
 import time
+
+STRIDED_LEG = "--strided-leg" in sys.argv
+if STRIDED_LEG:
+    import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "compressed-image_amd"), os.path.join(ROOT, "tests")]
@@ -57,6 +69,45 @@ def timed(fn, kernels):
     eng.enable_timing(0)
     return float(np.median(kus)), float(np.median(walls))
 
+
+def strided_leg():
+    """(5), in the child process: the plane decoded into a torch tensor and subsampled there, against the strided window call"""
+    step = 16
+    sw = n // step
+    full = torch.empty(n * n, dtype=torch.float32, device="cuda")
+    d_sub = eng.alloc(sw * sw * 4)
+    sspec = dict(chunk_first=0, chunk_count=nch, origin=0, row_pitch=step * n, col_pitch=step, width=sw, height=sw, out_off=0, out_pitch=sw * 4)
+    str_k, str_w = timed(lambda: eng.decompress_windows_device(d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, 4, [sspec], d_sub.ptr,
+                                                               comp_size=cb, strided=True), (hip.K_DECODE_WINDOW_STRIDED,))
+    stats = eng.window_stats()
+    assert np.array_equal(d_sub.download().view(np.float32).reshape(sw, sw), img[::step, ::step])
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    copy_us, kept = [], []
+
+    def parent_route():
+        eng.decompress_device(d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, full.data_ptr(), raw_off, comp_size=cb)
+        a.record()
+        sub = full.view(n, n)[::step, ::step].contiguous()
+        b.record()
+        torch.cuda.synchronize()
+        copy_us.append(a.elapsed_time(b) * 1e3)
+        kept[:] = [sub]
+
+    dec_k, par_w = timed(parent_route, (hip.K_DECODE, hip.K_DECODE_ZSTD))
+    assert np.array_equal(kept[0].cpu().numpy(), img[::step, ::step])
+    par_k = dec_k + float(np.median(copy_us[1:]))
+    d_sub.free()
+    return dict(strided_kernel_us=round(str_k, 1), strided_wall_us=round(str_w, 1), strided_blocks=stats["blocks_decoded"],
+                strided_chunks_whole=stats["chunks_whole"], parent_decode_kernel_us=round(dec_k, 1),
+                parent_copy_kernel_us=round(float(np.median(copy_us[1:])), 1), parent_kernel_us=round(par_k, 1), parent_wall_us=round(par_w, 1),
+                strided_kernel_ratio=round(par_k / str_k, 2), strided_wall_ratio=round(par_w / str_w, 2))
+
+
+if STRIDED_LEG:
+    print("STRIDED " + json.dumps(strided_leg()))
+    d_raw.free(); d_comp.free(); d_win.free()
+    eng.close()
+    sys.exit(0)
 
 full_k, full_w = timed(lambda: eng.decompress_device(d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, d_raw.ptr, raw_off, comp_size=cb),
                        (hip.K_DECODE, hip.K_DECODE_ZSTD))
@@ -119,6 +170,11 @@ reg_us, a = wall(lambda: ch.get_region(1024, 1024, 512, 512))
 dec_us, b = wall(lambda: ch.get_decompressed()[1024:1536, 1024:1536].copy())
 assert np.array_equal(a, b) and np.array_equal(a, arr[1024:1536, 1024:1536])
 res.update(region_wall_us=round(reg_us, 1), decompressed_slice_wall_us=round(dec_us, 1), region_speedup=round(dec_us / reg_us, 2))
+# (5), host class: every 8th pixel of every 8th row
+sub_us, a = wall(lambda: ch.get_region(0, 0, 4096, 4096, step_x=8, step_y=8))
+dsub_us, b = wall(lambda: ch.get_decompressed()[::8, ::8].copy())
+assert np.array_equal(a, b) and np.array_equal(a, arr[::8, ::8])
+res.update(region_step8_wall_us=round(sub_us, 1), decompressed_step8_wall_us=round(dsub_us, 1), region_step8_speedup=round(dsub_us / sub_us, 2))
 
 # (4) write through the module: set_region against get_chunk + edit + set_chunk of the chunk it lies in (chunk 2: rows 1024 .. 1535)
 for side in (64, 512):
@@ -147,6 +203,11 @@ hst = eng.update_stats()
 res.update(host_64_bytes_up=hst["bytes_uploaded"], host_64_bytes_down=sum(len(c) for c in new16 if c is not None),
            host_64_blocks_decoded=hst["blocks_decoded"], chunk_trip_bytes_each_way=chunk + len(chunks16[2]))
 eng.close()
+# (5), device: in a process of its own
+child = subprocess.run([sys.executable, os.path.abspath(__file__), "--strided-leg"], capture_output=True, text=True, timeout=900)
+got = [ln for ln in child.stdout.splitlines() if ln.startswith("STRIDED ")]
+assert child.returncode == 0 and got, child.stdout[-2000:] + child.stderr[-4000:]
+res.update(json.loads(got[0][len("STRIDED "):]))
 line = json.dumps(res)
 print(line)
 if len(sys.argv) > 2 and sys.argv[1] == "--out":
