@@ -17,6 +17,14 @@
 
 namespace cimg {
 
+#ifdef CIMG_EMULATE
+// test-side statistics only: streams the encoder left as REC_RAW_SRC, streams placed from the source
+inline long g_emu_src_left = 0, g_emu_src_placed = 0;
+#define CIMG_EMU_COUNT(x) (++(x))
+#else
+#define CIMG_EMU_COUNT(x) ((void)0)
+#endif
+
 struct AssembleArgs {
     const ChunkDesc* descs;
     int32_t nchunks;
@@ -195,6 +203,78 @@ struct LayoutChunk {
     }
 };
 
+// Can a stored stream of a split block be taken from the block's source bytes (REC_RAW_SRC)?  Byte plane of a 2- or 4-byte type
+// under the byte shuffle, or a slice of an unfiltered block.
+CIMG_HD bool plane_from_source_ok(int typesize, int filter)
+{
+    return (filter == FILTER_SHUFFLE && (typesize == 2 || typesize == 4)) || (filter == FILTER_NONE && typesize > 1);
+}
+
+// Stream s of a split block, as the encoder's phase A selects it (encode_kernel.h: load_plane), written at dst (any alignment) by one
+// wave: registers only, no LDS.  `src` is the block's first byte in the launch's input, which nobody writes during the launch.
+CIMG_DEV void wave_plane_from_source(const uint8_t* src, int bsize, int ts, int s, int neblock, bool shuf, uint8_t* dst)
+{
+    if (!shuf) { wave_copy_g2g<16>(src + (int64_t)s * neblock, dst, neblock, 0, 1); return; }
+    const int units = bsize >> 4;                    // 16 source bytes = 16 / ts plane bytes
+    constexpr int DEPTH = 16;                        // loads in flight per lane (load_plane)
+    if (ts == 2) {
+        const uint32_t sel = s ? 0x07050301u : 0x06040200u;
+        int u0 = 0;
+        for (; u0 + 64 * DEPTH <= units; u0 += 64 * DEPTH) {
+            LV<u128> x[DEPTH];
+            CIMG_UNROLL
+            for (int k = 0; k < DEPTH; k++) { FOR_LANES(l) { x[k][l] = ld128u(src + 16 * (u0 + 64 * k + l)); } }
+            CIMG_UNROLL
+            for (int k = 0; k < DEPTH; k++) {
+                FOR_LANES(l) {
+                    const uint64_t q = (uint64_t)byte_perm(x[k][l].y, x[k][l].x, sel) | ((uint64_t)byte_perm(x[k][l].w, x[k][l].z, sel) << 32);
+                    memcpy(dst + 8 * (u0 + 64 * k + l), &q, 8);
+                }
+            }
+        }
+        for (; u0 < units; u0 += 64) {
+            FOR_LANES(l) {
+                const int u = u0 + l;
+                if (u < units) {
+                    const u128 x = ld128u(src + 16 * u);
+                    const uint64_t q = (uint64_t)byte_perm(x.y, x.x, sel) | ((uint64_t)byte_perm(x.w, x.z, sel) << 32);
+                    memcpy(dst + 8 * u, &q, 8);
+                }
+            }
+        }
+    } else {                                         // ts == 4 (plane_from_source_ok)
+        const uint32_t s1 = (s & 2) ? 0x07030602u : 0x05010400u;      // bytes {0,1}/{2,3} of two elements
+        const uint32_t s2 = (s & 1) ? 0x07060302u : 0x05040100u;      // then byte s of four elements
+        int u0 = 0;
+        for (; u0 + 64 * DEPTH <= units; u0 += 64 * DEPTH) {
+            LV<u128> x[DEPTH];
+            CIMG_UNROLL
+            for (int k = 0; k < DEPTH; k++) { FOR_LANES(l) { x[k][l] = ld128u(src + 16 * (u0 + 64 * k + l)); } }
+            CIMG_UNROLL
+            for (int k = 0; k < DEPTH; k++) {
+                FOR_LANES(l) {
+                    const uint32_t t = byte_perm(x[k][l].y, x[k][l].x, s1), q = byte_perm(x[k][l].w, x[k][l].z, s1);
+                    st32(dst + 4 * (u0 + 64 * k + l), (int32_t)byte_perm(q, t, s2));
+                }
+            }
+        }
+        for (; u0 < units; u0 += 64) {
+            FOR_LANES(l) {
+                const int u = u0 + l;
+                if (u < units) {
+                    const u128 x = ld128u(src + 16 * u);
+                    const uint32_t t = byte_perm(x.y, x.x, s1), q = byte_perm(x.w, x.z, s1);
+                    st32(dst + 4 * u, (int32_t)byte_perm(q, t, s2));
+                }
+            }
+        }
+    }
+    // elements of the block past the last whole 16-byte unit
+    for (int e0 = (units << 4) / ts; e0 < neblock; e0 += 64) {
+        FOR_LANES(l) { if (e0 + l < neblock) dst[e0 + l] = src[(int64_t)(e0 + l) * ts + s]; }
+    }
+}
+
 struct EmitBlock {
     const AssembleArgs& a;
     int b;
@@ -207,7 +287,7 @@ struct EmitBlock {
     // memory (the writers wrote it through / wrote it back); the payload is this wave's own and comes out of its own L2.  No
     // acquire fence: an L2 invalidate per wave and chunk, a thousand waves at once, cost the launch more than the copies.
     CIMG_DEV void run_streams(int s_begin, int s_end) { copy(0, 1, s_begin, s_end, true); }
-
+    // (A REC_RAW_SRC stream has nothing in the scratch slot: its bytes are selected from the launch's input, which nobody writes.)
     CIMG_DEV void copy(int wave, int nwaves, int s_begin, int s_end, bool coherent = false)
     {
         const int chunk = find_chunk(a.descs, a.nchunks, b, a.uniform_nblocks);
@@ -266,7 +346,14 @@ struct EmitBlock {
                 }
             }
             pos += 4;
-            if (r.kind != REC_RUN && mine) { if (nwaves == 1) wave_copy_g2g<16>(slot + (int64_t)s * neblock, c + pos, r.csize, 0, 1); else wave_copy_g2g(slot + (int64_t)s * neblock, c + pos, r.csize, wave, nwaves); }
+            if (r.kind == REC_RAW_SRC) {
+                // (the stand-alone kernel never meets one: the kind exists only in chunks assembled inside the encode launch, by one wave)
+                if (mine) {
+                    CIMG_EMU_COUNT(g_emu_src_placed);
+                    wave_plane_from_source(a.raw + d.raw_off + (int64_t)j * d.blocksize, bsize, a.p.typesize, s, neblock, a.p.filter == FILTER_SHUFFLE, c + pos);
+                }
+            }
+            else if (r.kind != REC_RUN && mine) { if (nwaves == 1) wave_copy_g2g<16>(slot + (int64_t)s * neblock, c + pos, r.csize, 0, 1); else wave_copy_g2g(slot + (int64_t)s * neblock, c + pos, r.csize, wave, nwaves); }
             pos += rec_payload(r);
         }
     }

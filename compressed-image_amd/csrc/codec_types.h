@@ -20,6 +20,8 @@ enum : int {
     MAX_STREAMS = 16, MIN_BUFFERSIZE = 32,
     // stream record kinds written by the encode kernel
     REC_RUN = 0, REC_LZ4 = 1, REC_RAW = 2,
+    REC_RAW_SRC = 3,   // stored like REC_RAW, but nothing was written to the scratch slot: the bytes are a byte-select of the launch's input
+                       // (chunks assembled inside the encode launch only; sized and laid out exactly like REC_RAW)
     // error codes (c-blosc2 values) surfaced per chunk
     ERR_FAILURE = -1, ERR_DATA = -3, ERR_READ_BUFFER = -5, ERR_WRITE_BUFFER = -6, ERR_CODEC_SUPPORT = -7,
     ERR_CODEC_PARAM = -8, ERR_VERSION_SUPPORT = -10, ERR_INVALID_HEADER = -11, ERR_INVALID_PARAM = -12,
@@ -64,7 +66,7 @@ struct CodecParams {
 struct StreamRec {
     int32_t kind;     // REC_*
     int32_t value;    // run byte (REC_RUN)
-    int32_t csize;    // payload bytes in the scratch slot (REC_LZ4 / REC_RAW)
+    int32_t csize;    // payload bytes in the scratch slot (REC_LZ4 / REC_RAW) or to take from the source (REC_RAW_SRC)
     int32_t need;     // smallest LZ4 budget under which the stream still compresses (REC_LZ4)
 };
 

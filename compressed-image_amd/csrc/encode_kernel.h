@@ -67,10 +67,12 @@ struct EncodeArgs {
     // ---- chunks assembled INSIDE the launch (assemble != 0; round 3) ---------------------------------------------------------
     // A wave remembers the items it encoded (a linked list through next_item[]); the wave that finishes the last stream of a
     // chunk lays the chunk out (LayoutChunk: bstarts, header, the running-destsize rule) and raises ready[chunk]; when the work
-    // queue is empty every wave copies ITS OWN streams from the scratch slots into place -- out of its own XCD's L2, in the time
+    // queue is empty every wave copies ITS OWN coded streams from the scratch slots into place -- out of its own XCD's L2, in the time
     // the launch's tail leaves most waves idle anyway (4096 coded planes on 1280 chains: a fifth of the chains work through a
-    // fourth plane while the rest are done).  Only chunks whose descriptor says so (ChunkDesc::assemble: every stream of the chunk
-    // belongs to ONE launch) take part; cimg_layout_chunks / cimg_emit_blocks run behind the launch for the others.
+    // fourth plane while the rest are done).  STORED planes of split blocks never go through scratch (REC_RAW_SRC): they are a
+    // byte-select of `raw`, which nobody writes during the launch, and the wave that places them takes them from there.  Only chunks
+    // whose descriptor says so (ChunkDesc::assemble: every stream of the chunk belongs to ONE launch) take part; cimg_layout_chunks /
+    // cimg_emit_blocks run behind the launch for the others.
     int32_t assemble;
     uint8_t* comp;            // chunks are written at comp + desc.comp_off
     ChunkLayout* layout;      // per chunk (device)
@@ -1036,6 +1038,13 @@ CIMG_DEV void encode_item_place(kernarg_ptr<EncodeArgs> a, int item, int& b, int
     }
 }
 
+// does a stored plane of this chunk stay out of the scratch slot (REC_RAW_SRC)?  Split blocks of a chunk this launch assembles itself,
+// where the plane can be selected from the input again (round 6)
+CIMG_DEV bool encode_stored_from_source(kernarg_ptr<EncodeArgs> a, const ChunkDesc& d)
+{
+    return a->assemble && a->want_split && d.assemble && !d.memcpyed && d.split && plane_from_source_ok(a->p.typesize, a->p.filter);
+}
+
 // `finished` streams of `chunk` are done: their payloads sit in the scratch slots (plain stores: only this wave reads them again),
 // their records were written through to memory (agent-scope stores).  Counts them; the wave whose streams complete the chunk lays
 // it out and raises ready[chunk].  Returns the new head of the wave's item list (the item is only remembered when its chunk is
@@ -1081,9 +1090,10 @@ CIMG_DEV_OUTLINE int encode_account(kernarg_ptr<EncodeArgs> ap_in, int item_in, 
     return item;
 }
 
-// The wave found the work queue empty: it copies the streams IT encoded into place, chunk by chunk as they become ready.  A chunk
-// that is not laid out yet is waited for (s_sleep + one atomic load per try; every chain that still encodes keeps its own SIMD
-// slot, so waiting waves hold nobody up) -- with a hard bound, after which the batch FAILS.
+// The wave found the work queue empty: it copies the streams IT encoded into place, chunk by chunk as they become ready -- coded ones
+// from the scratch slots, stored planes of split blocks from the source (REC_RAW_SRC).  A chunk that is not laid out yet is waited for
+// (s_sleep + one atomic load per try; every chain that still encodes keeps its own SIMD slot, so waiting waves hold nobody up) --
+// with a hard bound, after which the batch FAILS.
 CIMG_DEV_OUTLINE void encode_emit_own(kernarg_ptr<EncodeArgs> ap_in, int last_in)
 {
     const kernarg_ptr<EncodeArgs> ap = CIMG_OWN_KERNARGS(EncodeArgs, ap_in);
@@ -1472,7 +1482,17 @@ struct EncodeStream {
                 r.kind = REC_LZ4; r.csize = cb; r.need = need;
             } else {
                 if (cb < 0) r.value = cb;                 // a loop guard tripped: stored raw, flagged for diagnosis
-                wave_copy_l2g(lds, 0, out, neblock);
+                // A stored plane of a split block in a chunk this launch assembles is not copied to the scratch slot: this wave, when it
+                // places it, selects it from the launch's input again (REC_RAW_SRC).  (Decided here, from the arguments, and not by run_item:
+                // a flag carried across the codec loop cost the kernel ten more spilled SGPRs.)
+                bool from_source = false;
+                if (cb >= 0) {
+                    const auto a = fresh(ap);
+                    const int b = rec_index / a->p.streams_per_block;
+                    from_source = encode_stored_from_source(a, uniform_desc(a->descs + find_chunk(a->descs, a->nchunks, b, a->uniform_nblocks)));
+                }
+                if (from_source) { r.kind = REC_RAW_SRC; CIMG_EMU_COUNT(g_emu_src_left); }
+                else wave_copy_l2g(lds, 0, out, neblock);
             }
         }
         // the record: its address is worked out again from the arguments (nothing of it was kept alive across the codec loop)
