@@ -19,18 +19,21 @@ K_DECODE_WINDOW = 16                           # windows: the blocks a window me
 K_UPDATE_PATCH, K_UPDATE_LAYOUT, K_UPDATE_EMIT = 17, 18, 19   # window writes (csrc/update_kernel.h)
 K_PACK, K_INTERLEAVE = 20, 21                  # packed device storage (csrc/pack_kernel.h, csrc/interleave_kernel.h)
 K_DECODE_WINDOW_STRIDED = 22                   # strided windows: the blocks that hold a sampled element (csrc/window_kernel.h)
+K_TRUNC_PREC = 23                              # trunc-prec: the masked copy in front of a compress batch (csrc/trunc_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
 KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cimg_decode_blocks", "cimg_deinterleave",
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
-           "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided")
+           "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
+           "cimg_trunc_prec")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
 BLOSCLZ, LZ4, LZ4HC, ZLIB, ZSTD = 0, 1, 2, 4, 5
 NOFILTER, SHUFFLE, BITSHUFFLE = 0, 1, 2
+TRUNC_PREC = 4                                 # slot 4 only (csrc/trunc_plan.h)
 MAX_OVERHEAD = 32
 
 EXPORTS = (
@@ -201,12 +204,16 @@ def load():
     return L
 
 
-def cparams(typesize, clevel=9, blocksize=32768, compcode=LZ4, splitmode=3, filters=(0, 0, 0, 0, 0, SHUFFLE)):
+def cparams(typesize, clevel=9, blocksize=32768, compcode=LZ4, splitmode=3, filters=(0, 0, 0, 0, 0, SHUFFLE), trunc_prec=None):
+    """trunc_prec: blosc2's trunc-prec filter in slot 4 with this int8 meta (> 0: mantissa bits kept, < 0: bits zeroed)"""
     p = CParams()
     load().cimg_cparams_init(C.byref(p), typesize)
     p.clevel, p.blocksize, p.compcode, p.splitmode = clevel, blocksize, compcode, splitmode
     for i, f in enumerate(filters):
         p.filters[i] = f
+    if trunc_prec is not None:
+        p.filters[4] = TRUNC_PREC
+        p.filters_meta[4] = int(trunc_prec) & 0xFF
     return p
 
 

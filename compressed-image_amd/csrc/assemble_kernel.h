@@ -62,6 +62,8 @@ struct LayoutChunk {
             else if (l >= OFF_NBYTES && l < OFF_NBYTES + 4) v = ((uint32_t)d.nbytes >> (8 * (l - OFF_NBYTES))) & 0xFF;
             else if (l >= OFF_BLOCKSIZE && l < OFF_BLOCKSIZE + 4) v = ((uint32_t)d.blocksize >> (8 * (l - OFF_BLOCKSIZE))) & 0xFF;
             else if (l >= OFF_CBYTES && l < OFF_CBYTES + 4) v = ((uint32_t)cbytes >> (8 * (l - OFF_CBYTES))) & 0xFF;
+            else if (l == OFF_FILTERS + 4) v = (uint32_t)a.p.trunc & 0xFF;          // trunc-prec: named, and its meta (the pixels came truncated)
+            else if (l == OFF_FILTERS_META + 4) v = ((uint32_t)a.p.trunc >> 8) & 0xFF;
             else if (l == OFF_FILTERS + 5) v = (uint32_t)a.p.filter;
             else if (l == OFF_COMPCODE) v = (uint32_t)a.p.compcode;
             else if (l == OFF_BLOSC2_FLAGS) v = (uint32_t)blosc2_flags;

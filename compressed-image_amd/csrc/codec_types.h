@@ -12,6 +12,7 @@ enum : int {
     HEADER_LEN = 32,
     FLAG_SHUFFLE = 0x01, FLAG_MEMCPYED = 0x02, FLAG_BITSHUFFLE = 0x04, FLAG_DONT_SPLIT = 0x10,
     FILTER_NONE = 0, FILTER_SHUFFLE = 1, FILTER_BITSHUFFLE = 2,
+    FILTER_TRUNC_PREC = 4,     // slot 4 only; a no-op on the read side (trunc_plan.h)
     CODEC_BLOSCLZ = 0, CODEC_LZ4 = 1, CODEC_LZ4HC = 2, CODEC_ZLIB = 4, CODEC_ZSTD = 5,
     SPLIT_ALWAYS = 1, SPLIT_NEVER = 2, SPLIT_AUTO = 3, SPLIT_FORWARD_COMPAT = 4,
     OFF_FLAGS = 2, OFF_TYPESIZE = 3, OFF_NBYTES = 4, OFF_BLOCKSIZE = 8, OFF_CBYTES = 12,
@@ -60,6 +61,7 @@ struct CodecParams {
     int32_t max_blocksize; // largest effective block size in the batch (sizes LDS and scratch slots)
     int32_t slot_bytes;    // scratch bytes reserved per block
     int32_t streams_per_block; // record slots per block (typesize if any chunk splits, else 1)
+    int32_t trunc;         // header bytes 20 and 28: filters[4] | filters_meta[4] << 8 (trunc-prec, applied to the pixels BEFORE the launch: trunc_plan.h); 0: none
 };
 
 // per-stream record produced by the encode kernel, consumed by the layout kernel

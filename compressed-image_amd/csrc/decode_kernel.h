@@ -1247,7 +1247,7 @@ struct DecodeBlock {
         if (fmt != 0 && fmt != 1) { fail(fmt == 4 ? ((flags & FLAG_DONT_SPLIT) || ts <= 1 ? STATUS_ZSTD_PENDING : STATUS_ZSTD_PENDING_SPLIT) : ERR_CODEC_SUPPORT); return; }   // zstd: cimg_decode_zstd's
         // filter pipeline: exactly one of {none, shuffle, bitshuffle}, in the last slot
         filter = (int)((f1 >> 8) & 0xFF);
-        if (f0 != 0 || (f1 & 0xFF) != 0) { fail(ERR_CODEC_SUPPORT); return; }
+        if (f0 != 0 || (f1 & 0xFF & ~FILTER_TRUNC_PREC) != 0) { fail(ERR_CODEC_SUPPORT); return; }   // (slot 4: 0, or 4 = trunc-prec, which leaves nothing to undo)
         if (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE) { fail(ERR_CODEC_SUPPORT); return; }
         if (filter == FILTER_BITSHUFFLE && !(flags & FLAG_DONT_SPLIT)) { fail(ERR_CODEC_SUPPORT); return; }   // bit rows are never split
         const bool leftover_blk = bsize != blocksize;

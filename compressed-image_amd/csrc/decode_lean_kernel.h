@@ -105,7 +105,7 @@ struct DecodeLeanWave {
         if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) return;
         h.fmt = flags >> 5;                                                       // 0 blosclz, 1 lz4 / lz4hc
         if (((b2 >> 28) & 7) != 0 || (flags & (FLAG_MEMCPYED | FLAG_DONT_SPLIT)) || (h.fmt != 0 && h.fmt != 1)) return;
-        if (f0 != 0 || (f1 & 0xFF) != 0 || (int)((f1 >> 8) & 0xFF) != FILTER_SHUFFLE) return;
+        if (f0 != 0 || (f1 & 0xFF & ~FILTER_TRUNC_PREC) != 0 || (int)((f1 >> 8) & 0xFF) != FILTER_SHUFFLE) return;
         const int bsz = h.blocksize;
         if ((h.ts != 2 && h.ts != 4) || (bsz & 15) || bsz % h.ts) return;
         h.neblock = bsz / h.ts;

@@ -1019,7 +1019,7 @@ CIMG_DEV AssembleArgs assemble_args(kernarg_ptr<EncodeArgs> ap)
     AssembleArgs aa;
     aa.descs = a->descs; aa.nchunks = a->nchunks; aa.raw = a->raw;
     aa.p.typesize = a->p.typesize; aa.p.clevel = a->p.clevel; aa.p.compcode = a->p.compcode; aa.p.filter = a->p.filter; aa.p.accel = a->p.accel;
-    aa.p.max_blocksize = a->p.max_blocksize; aa.p.slot_bytes = a->p.slot_bytes; aa.p.streams_per_block = a->p.streams_per_block;
+    aa.p.max_blocksize = a->p.max_blocksize; aa.p.slot_bytes = a->p.slot_bytes; aa.p.streams_per_block = a->p.streams_per_block; aa.p.trunc = a->p.trunc;
     aa.scratch = a->scratch; aa.recs = a->recs;
     aa.comp = a->comp; aa.layout = a->layout; aa.uniform_nblocks = a->uniform_nblocks; aa.layout_host = a->layout_host; aa.skip_assembled = 0;
     return aa;

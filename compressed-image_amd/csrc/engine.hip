@@ -22,6 +22,7 @@
 #include "deinterleave_kernel.h"
 #include "interleave_kernel.h"
 #include "pack_kernel.h"
+#include "trunc_kernel.h"
 #include "zstd_kernel.h"
 #include "zstd_walk_kernel.h"
 #include "zstd_seq_kernel.h"
@@ -293,6 +294,13 @@ extern "C" __global__ __launch_bounds__(256) void cimg_update_emit(SpliceArgs a)
     se.run(wave);
 }
 
+// (the last kernel of the file)
+// trunc-prec in front of a compress batch (trunc_kernel.h): one wave per 16 KiB tile of a piece, as cimg_pack_chunks
+extern "C" __global__ __launch_bounds__(64) void cimg_trunc_prec(TruncArgs a)
+{
+    trunc_wave(a, (int)blockIdx.x);
+}
+
 // ====================================================================================================
 //  engine
 // ====================================================================================================
@@ -435,6 +443,9 @@ struct cimg_engine {
     // the pack launch's piece table (pack_kernel.h), and the event cimg_engine_wait_stream records on the caller's stream
     DevBuf pack_tab;
     PinBuf h_pack_tab;
+    // trunc-prec: the pass's piece table, and the truncated copy of a caller's device pixels (grow-only; the encode launch reads it)
+    DevBuf trunc_tab, trunc_src;
+    PinBuf h_trunc_tab;
     hipEvent_t ev_wait = nullptr;
     UpdateStats upd_stats;
     int32_t cflight_chunks = -1;          // chunks of the compress batch between _device_begin and _device_fetch (-1: none)
@@ -595,6 +606,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
     case CIMG_K_PACK: return "cimg_pack_chunks";
     case CIMG_K_INTERLEAVE: return "cimg_interleave";
+    case CIMG_K_TRUNC_PREC: return "cimg_trunc_prec";
     default: return "?";
     }
 }
@@ -668,9 +680,9 @@ void cimg_engine_destroy(cimg_engine* e)
     for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
                     &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots,
                     &e->upd_patch, &e->upd_units, &e->upd_stage, &e->upd_items, &e->upd_descs, &e->upd_chunks, &e->upd_blocks, &e->upd_layout,
-                    &e->upd_src, &e->upd_new, &e->pack_tab})
+                    &e->upd_src, &e->upd_new, &e->pack_tab, &e->trunc_tab, &e->trunc_src})
         if (b->p) (void)hipFree(b->p);
-    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr, &e->h_pack_tab})
+    for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr, &e->h_pack_tab, &e->h_trunc_tab})
         if (b->p) (void)hipHostFree(b->p);
     (void)hipStreamDestroy(e->stream);
     if (e->s_h2d) { (void)hipStreamSynchronize(e->s_h2d); (void)hipStreamDestroy(e->s_h2d); }
@@ -858,19 +870,69 @@ static int compress_launch_wide(cimg_engine* e, EncodePlan& plan, int32_t nchunk
 // their caller's pixels are there when the call is made.
 static int encode_launch(cimg_engine* e, EncodePlan& plan, int32_t nchunks, const void* d_raw, void* d_comp, bool assemble);
 
+// The trunc-prec pass of a compress batch (trunc_kernel.h), enqueued on the engine's stream in front of the encode launches: piece i
+// is chunk i, from src + src_off[i] to dst + dst_off[i] (the same address: in place).
+static int trunc_launch(cimg_engine* e, int typesize, uint64_t mask64, int32_t nchunks, const uint8_t* src, const int64_t* src_off,
+                        uint8_t* dst, const int64_t* dst_off, const int32_t* nbytes)
+{
+    bool any = false;
+    for (int i = 0; i < nchunks; i++) any = any || nbytes[i] > 0;
+    if (!any) return 0;
+    if (!src || !dst) return e->fail(ERR_INVALID_PARAM, "null argument");
+    std::vector<const void*> s((size_t)nchunks);
+    std::vector<void*> d((size_t)nchunks);
+    for (int i = 0; i < nchunks; i++) { s[(size_t)i] = src + src_off[i]; d[(size_t)i] = dst + dst_off[i]; }
+    std::vector<PackPiece> pieces;
+    int64_t ntiles = 0;
+    if (trunc_plan_pieces(nchunks, s.data(), d.data(), nbytes, typesize, pieces, &ntiles)) return e->fail(ERR_INVALID_PARAM, "trunc-prec: too many bytes for one call");
+    if (pieces.empty()) return 0;
+    int rc;
+    const size_t tab = pieces.size() * sizeof(PackPiece);
+    if ((rc = e->reserve(e->trunc_tab, tab))) return rc;
+    if ((rc = e->reserve(e->h_trunc_tab, tab))) return rc;
+    // (every compress batch ends with a stream synchronize before the next begins: the pinned table is free again)
+    memcpy(e->h_trunc_tab.p, pieces.data(), tab);
+    if ((rc = e->hip(hipMemcpyAsync(e->trunc_tab.p, e->h_trunc_tab.p, tab, hipMemcpyHostToDevice, e->stream), "trunc-prec table H2D"))) return rc;
+    TruncArgs a{(const PackPiece*)e->trunc_tab.p, (int32_t)pieces.size(), (int32_t)ntiles, mask64, typesize, 0};
+    return e->launch(CIMG_K_TRUNC_PREC, cimg_trunc_prec, a, (int)ntiles, 64, 0);
+}
+
+// raw_owned: the pixels lie in the engine's own staging area (host calls, deinterleaved planes), where trunc-prec runs in place; a
+// caller's device pixels are const, and are truncated on their way into engine scratch that the encode launches then read.
 static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
                            const void* d_raw, const int64_t* raw_off, const int32_t* nbytes,
-                           void* d_comp, const int64_t* comp_off, const int32_t* destsize, bool inputs_behind_stream = true)
+                           void* d_comp, const int64_t* comp_off, const int32_t* destsize, bool inputs_behind_stream = true, bool raw_owned = false)
 {
     (void)hipSetDevice(e->device);
     e->claunched = false;
     e->begin_batch(0);
+    const HostCParams hp = to_host(p);
+    // trunc-prec (filters[4] == 4): validated before anything runs; the batch is then planned as for the same cparams without slot 4
+    uint64_t mask64 = 0;
+    const int trunc = trunc_from_cparams(hp.typesize, hp.filters, hp.filters_meta, &mask64);
+    if (trunc < 0) return e->fail(ERR_INVALID_PARAM, "trunc-prec: typesize %d with filters_meta[4] = %d is not a valid precision", hp.typesize, (int)(int8_t)hp.filters_meta[4]);
+    std::vector<int64_t> copy_off;                      // where the truncated copy of chunk i lies in trunc_src
+    int64_t copy_total = 0;
+    if (trunc && !raw_owned) {
+        copy_off.resize((size_t)nchunks);
+        for (int i = 0; i < nchunks; i++) { copy_off[(size_t)i] = copy_total; copy_total += ((int64_t)(nbytes[i] > 0 ? nbytes[i] : 0) + 63) & ~63ll; }
+    }
+    const int64_t* const plan_off = copy_off.empty() ? raw_off : copy_off.data();
     EncodePlan plan;
-    int rc = plan_encode_batch(to_host(p), nchunks, raw_off, nbytes, comp_off, destsize, &plan);
-    if (rc == ERR_CODEC_SUPPORT && plan_encode_wide(to_host(p), nchunks, raw_off, nbytes, comp_off, destsize, &plan) == 0)
-        return compress_launch_wide(e, plan, nchunks, d_raw, d_comp);
-    if (rc < 0) return e->fail(rc, "compress batch rejected by the planner (code %d): codec %d / filter pipeline / block size %d not available on the GPU path",
-                               rc, p->compcode, p->blocksize);
+    int rc = plan_encode_batch(hp, nchunks, plan_off, nbytes, comp_off, destsize, &plan, trunc != 0);
+    const bool wide = rc == ERR_CODEC_SUPPORT && plan_encode_wide(hp, nchunks, plan_off, nbytes, comp_off, destsize, &plan, trunc != 0) == 0;
+    if (rc < 0 && !wide) return e->fail(rc, "compress batch rejected by the planner (code %d): codec %d / filter pipeline / block size %d not available on the GPU path",
+                                        rc, p->compcode, p->blocksize);
+    if (trunc) {
+        uint8_t* dst = (uint8_t*)const_cast<void*>(d_raw);
+        if (!raw_owned) {
+            if ((rc = e->reserve(e->trunc_src, (size_t)copy_total + 64))) return rc;
+            dst = (uint8_t*)e->trunc_src.p;
+        }
+        if ((rc = trunc_launch(e, hp.typesize, mask64, nchunks, (const uint8_t*)d_raw, raw_off, dst, plan_off, nbytes))) return rc;
+        d_raw = dst;
+    }
+    if (wide) return compress_launch_wide(e, plan, nchunks, d_raw, d_comp);
     return encode_launch(e, plan, nchunks, d_raw, d_comp, true);
 }
 
@@ -1785,7 +1847,7 @@ int compress_host_pipeline(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     if (ng == 1) {
         // a small batch (the blosc2_compress_ctx shim: one chunk) has nothing to overlap: one stream, no events
         if ((rc = copy_in(e, e->stream, sr, d_raw_off.data(), hr, raw_off, nbytes, 0, nchunks, "pixels H2D"))) return rc;
-        rc = compress_launch(e, p, nchunks, sr, d_raw_off.data(), nbytes, sc, d_comp_off.data(), destsize);
+        rc = compress_launch(e, p, nchunks, sr, d_raw_off.data(), nbytes, sc, d_comp_off.data(), destsize, true, true);
         const int frc = compress_finish(e, nchunks, cbytes);
         if (rc || frc) return rc ? rc : frc;
         if (h_comp) {
@@ -1804,7 +1866,7 @@ int compress_host_pipeline(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     for (int g = 0; g < ng; g++) {
         const int a = G.first[(size_t)g], b = G.first[(size_t)g + 1];
         if ((rc = e->hip(hipStreamWaitEvent(e->stream, e->ev_h2d[g & 1], 0), "stream wait"))) return rc;
-        rc = compress_launch(e, p, b - a, sr, d_raw_off.data() + a, nbytes + a, sc, d_comp_off.data() + a, destsize + a);
+        rc = compress_launch(e, p, b - a, sr, d_raw_off.data() + a, nbytes + a, sc, d_comp_off.data() + a, destsize + a, true, true);
         if (!rc && g + 1 < ng) {
             rc = copy_in(e, e->s_h2d, sr, d_raw_off.data(), hr, raw_off, nbytes, b, G.first[(size_t)g + 2], "pixels H2D");
             if (!rc) rc = e->hip(hipEventRecord(e->ev_h2d[(g + 1) & 1], e->s_h2d), "event record");
@@ -1888,7 +1950,7 @@ int cimg_compress_batch_host_interleaved_begin(cimg_engine* e, const cimg_cparam
     if ((rc = e->hip(hipMemcpyAsync(e->stage_il.p, h_interleaved, il_bytes, hipMemcpyHostToDevice, e->stream), "interleaved pixels H2D"))) return rc;
     e->begin_batch(0);
     if ((rc = deinterleave_launch(e, e->stage_il.p, nchannels, ts, npixels, e->stage_raw.p, plane_stride))) { (void)hipStreamSynchronize(e->stream); return rc; }
-    rc = compress_launch(e, p, nchunks, e->stage_raw.p, raw_off, nbytes, e->stage_comp.p, d_comp_off.data(), destsize);
+    rc = compress_launch(e, p, nchunks, e->stage_raw.p, raw_off, nbytes, e->stage_comp.p, d_comp_off.data(), destsize, true, true);
     const int frc = compress_finish(e, nchunks, cbytes);                // always: nothing may stay in flight on an error path
     if (rc || frc) return rc ? rc : frc;
     e->fetch_off = std::move(d_comp_off);
@@ -2365,8 +2427,17 @@ struct EngineUpdateEnv : EngineChunks {
     int compress(const HostCParams&, const std::vector<int>&, const std::vector<int64_t>& raw_off, const std::vector<int32_t>& nb,
                  const std::vector<int32_t>& ds, const std::vector<int64_t>& new_off, int32_t* cbytes)
     {
-        return cimg_compress_batch_device(e, p, (int32_t)nb.size(), e->win_whole.p, raw_off.data(), nb.data(), d_new, new_off.data(),
-                                          ds.data(), cbytes);
+        // (the chunks lie decoded and patched in the engine's own buffer: trunc-prec, where p names it, runs in place over them)
+        e->cflight_chunks = -1;
+        const int rc = compress_launch(e, p, (int32_t)nb.size(), e->win_whole.p, raw_off.data(), nb.data(), d_new, new_off.data(), ds.data(), e->dflight_open, true);
+        return rc ? rc : compress_finish(e, (int32_t)nb.size(), cbytes);
+    }
+
+    // trunc-prec over patched slots of the patch buffer, in place, in front of the encode launch (same stream: no wait)
+    int trunc(int typesize, uint64_t mask64, const std::vector<int64_t>& off, const std::vector<int32_t>& len)
+    {
+        uint8_t* const b = (uint8_t*)e->upd_patch.p;
+        return trunc_launch(e, typesize, mask64, (int32_t)len.size(), b, off.data(), b, off.data(), len.data());
     }
 };
 

@@ -3,6 +3,7 @@
 // checker's copy of the same rules).  Pure C++, shared by the engine and the emulator.
 #pragma once
 #include "codec_types.h"
+#include "trunc_plan.h"
 #include <stdint.h>
 #include <vector>
 
@@ -35,6 +36,22 @@ inline int single_filter(const HostCParams& p, int* filter)
     for (int i = 0; i < 5; i++) if (p.filters[i] != 0) return ERR_CODEC_SUPPORT;
     if (p.filters[5] > FILTER_BITSHUFFLE) return ERR_CODEC_SUPPORT;
     *filter = p.filters[5];
+    return 0;
+}
+
+// trunc-prec in slot 4 (trunc_plan.h).  The planners below plan for pixels as they ARE: parameters that name the filter are refused
+// like any filter in slots 0 .. 4 unless the caller says the pass has run over the pixels (`truncated`); then the batch is planned as
+// for the same parameters without slot 4, and *trunc carries the two header bytes (CodecParams::trunc).
+inline int strip_trunc(const HostCParams& p, bool truncated, HostCParams* q, int32_t* trunc)
+{
+    *q = p;
+    *trunc = 0;
+    if (!truncated || !trunc_named(p.filters)) return 0;
+    int zeroed = 0;
+    const int rc = trunc_zeroed_bits(p.typesize, p.filters_meta[4], &zeroed);
+    if (rc < 0) return rc;
+    q->filters[4] = 0;
+    *trunc = FILTER_TRUNC_PREC | ((int32_t)p.filters_meta[4] << 8);
     return 0;
 }
 
@@ -116,12 +133,15 @@ struct EncodePlan {
 
 enum : int { MAX_LDS_BYTES = 160 * 1024 };
 
-inline int plan_encode_batch(const HostCParams& p, int nchunks, const int64_t* raw_off, const int32_t* nbytes,
-                             const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan)
+inline int plan_encode_batch(const HostCParams& p_in, int nchunks, const int64_t* raw_off, const int32_t* nbytes,
+                             const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan, bool truncated = false)
 {
     plan->descs.resize((size_t)nchunks);
+    HostCParams p;
     int filter = 0;
-    int rc = single_filter(p, &filter);
+    int rc = strip_trunc(p_in, truncated, &p, &plan->cp.trunc);
+    if (rc < 0) return rc;
+    rc = single_filter(p, &filter);
     if (rc < 0) return rc;
     // lz4 and blosclz: bit-exact encoders.  lz4hc and zstd: FORMAT-VALID encoders whose bytes differ from liblz4's / libzstd's by
     // construction: lz4hc chunks are LZ4 blocks from the fast match finder at acceleration 1, zstd chunks are

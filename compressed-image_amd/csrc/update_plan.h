@@ -17,6 +17,8 @@
 #include "update_kernel.h"
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 
 namespace cimg {
 
@@ -60,7 +62,16 @@ inline bool items_cover(const std::vector<WindowItem>& items, size_t first, size
 //   int encode(const EncodePlan&)                          -- the batch encode launch over the patch buffer, records + slots left
 //   int splice(cp, chunks, blocks, layout)                 -- cimg_update_layout + cimg_update_emit, layout back on the host
 //   int compress(p, list, raw_off, nbytes, destsize, new_off, cbytes)
-//                                                          -- the batch compress of chunks lying in the whole buffer
+//                                                          -- the batch compress of chunks lying in the whole buffer (with trunc-prec
+//                                                             in p: the pass over those chunks, then the compress)
+//   int trunc(typesize, mask64, off, len)    [optional]    -- trunc-prec in place over pieces of the patch buffer, in front of encode().
+//                                                             An env without it cannot truncate: parameters that name the filter are
+//                                                             ERR_INVALID_PARAM there, as they were before the filter was built.
+template <class Env, class = void> struct env_has_trunc : std::false_type {};
+template <class Env>
+struct env_has_trunc<Env, std::void_t<decltype(std::declval<Env&>().trunc(0, uint64_t(0), std::declval<const std::vector<int64_t>&>(),
+                                                                          std::declval<const std::vector<int32_t>&>()))>> : std::true_type {};
+
 template <class Env>
 int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
                const int32_t* blocksize, const int32_t* destsize, int nwindows, const WindowSpec* w, const int64_t* new_off,
@@ -72,7 +83,16 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
     if (nwindows == 0) return 0;
     if (nchunks == 0 || p.typesize <= 0) return ERR_INVALID_PARAM;
     int filter = 0;
-    if (single_filter(p, &filter) < 0) return ERR_INVALID_PARAM;
+    // trunc-prec in slot 4 (trunc_plan.h): header and p must agree on it like on everything else; patched pixels are truncated before
+    // they are encoded, so a new chunk equals the from-scratch compress of (old pixels with the windows written in), truncated
+    uint64_t mask64 = 0;
+    const int trunc = trunc_from_cparams(p.typesize, p.filters, p.filters_meta, &mask64);
+    if (trunc < 0 || (trunc && !env_has_trunc<Env>::value)) return ERR_INVALID_PARAM;
+    {
+        HostCParams q;
+        int32_t tb = 0;
+        if (strip_trunc(p, trunc != 0, &q, &tb) < 0 || single_filter(q, &filter) < 0) return ERR_INVALID_PARAM;
+    }
     const int ts = p.typesize > 255 ? 1 : p.typesize;
     for (int i = 0; i < nchunks; i++) if (destsize[i] < HEADER_LEN) return ERR_INVALID_PARAM;
     const std::vector<int32_t> tsv((size_t)nchunks, ts);
@@ -105,7 +125,8 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
         const int flags = h[OFF_FLAGS];
         bool agree = hnb == nbytes[i] && hbs == blocksize[i] && hbs == d.blocksize && h[OFF_TYPESIZE] == ts &&
                      ((flags ^ d.flags) & ~FLAG_MEMCPYED) == 0 && h[OFF_COMPCODE] == p.compcode && h[OFF_FILTERS + 5] == filter;
-        for (int k = 0; k < 5; k++) agree = agree && h[OFF_FILTERS + k] == 0;
+        for (int k = 0; k < 4; k++) agree = agree && h[OFF_FILTERS + k] == 0;
+        agree = agree && h[OFF_FILTERS + 4] == (trunc ? FILTER_TRUNC_PREC : 0) && (!trunc || h[OFF_FILTERS_META + 4] == p.filters_meta[4]);
         if (!agree) return ERR_INVALID_PARAM;
         old_cbytes[(size_t)i] = hcb;
         const int fmt = flags >> 5, special = (h[OFF_BLOSC2_FLAGS] >> 4) & 7;
@@ -113,7 +134,7 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
         if (splice) {
             EncodePlan ep;
             const int64_t zero = 0;
-            splice = plan_encode_batch(p, 1, &zero, &nbytes[i], &zero, &destsize[i], &ep) == 0;
+            splice = plan_encode_batch(p, 1, &zero, &nbytes[i], &zero, &destsize[i], &ep, trunc != 0) == 0;
         }
         route[(size_t)i] = splice ? ROUTE_SPLICE : ROUTE_WHOLE;
     }
@@ -164,7 +185,7 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
         EncodePlan ep;
         std::vector<int32_t> enc_of(units.size(), -1);
         if (!sl.empty()) {
-            if (plan_encode_batch(p, (int)sl.size(), zoff.data(), snb.data(), zoff.data(), sds.data(), &ep) < 0) return ERR_INVALID_PARAM;
+            if (plan_encode_batch(p, (int)sl.size(), zoff.data(), snb.data(), zoff.data(), sds.data(), &ep, trunc != 0) < 0) return ERR_INVALID_PARAM;
             std::vector<ChunkDesc> pd;
             ep.lds_split = ep.lds_unsplit = 0;
             for (size_t k = 0; k < units.size(); k++) {
@@ -187,6 +208,14 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
             ep.descs = pd;
             ep.total_blocks = (int32_t)pd.size();
             ep.uniform_nblocks = 1;
+            if constexpr (env_has_trunc<Env>::value) {
+                if (trunc && !pd.empty()) {                  // the patched slots, in place (a block starts on an element boundary of its chunk)
+                    std::vector<int64_t> toff;
+                    std::vector<int32_t> tlen;
+                    for (const ChunkDesc& q : pd) { toff.push_back(q.raw_off); tlen.push_back(q.nbytes); }
+                    if ((rc = env.trunc(ts, mask64, toff, tlen)) < 0) return rc;
+                }
+            }
             if (!pd.empty() && (rc = env.encode(ep)) < 0) return rc;
             stats->blocks_encoded = (int64_t)pd.size();
             for (size_t k = 0; k < units.size(); k++) if (enc_of[k] >= 0 && units[k].stage) stats->blocks_decoded++;

@@ -425,7 +425,7 @@ struct WideDecodeBlock : DecodeBlock {
         if (fmt == 4) { fail((flags & FLAG_DONT_SPLIT) || ts <= 1 ? STATUS_ZSTD_PENDING : STATUS_ZSTD_PENDING_SPLIT); return; }   // the zstd read path's (engine.hip)
         if (fmt != 0 && fmt != 1) { fail(ERR_CODEC_SUPPORT); return; }
         filter = (int)((f1 >> 8) & 0xFF);
-        if (f0 != 0 || (f1 & 0xFF) != 0) { fail(ERR_CODEC_SUPPORT); return; }
+        if (f0 != 0 || (f1 & 0xFF & ~FILTER_TRUNC_PREC) != 0) { fail(ERR_CODEC_SUPPORT); return; }
         if (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE) { fail(ERR_CODEC_SUPPORT); return; }
         if (filter == FILTER_BITSHUFFLE && !(flags & FLAG_DONT_SPLIT)) { fail(ERR_CODEC_SUPPORT); return; }
         const bool leftover_blk = bsize != blocksize;

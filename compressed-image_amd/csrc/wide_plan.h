@@ -11,12 +11,15 @@
 namespace cimg {
 
 // Write side: the whole batch goes through cimg_encode_wide (every stream, whatever its length) and the two assembly kernels.
-inline int plan_encode_wide(const HostCParams& p, int nchunks, const int64_t* raw_off, const int32_t* nbytes,
-                            const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan)
+inline int plan_encode_wide(const HostCParams& p_in, int nchunks, const int64_t* raw_off, const int32_t* nbytes,
+                            const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan, bool truncated = false)
 {
     plan->descs.resize((size_t)nchunks);
+    HostCParams p;
     int filter = 0;
-    int rc = single_filter(p, &filter);
+    int rc = strip_trunc(p_in, truncated, &p, &plan->cp.trunc);
+    if (rc < 0) return rc;
+    rc = single_filter(p, &filter);
     if (rc < 0) return rc;
     if (p.compcode != CODEC_LZ4 && p.compcode != CODEC_LZ4HC && p.compcode != CODEC_ZSTD) return ERR_CODEC_SUPPORT;   // BloscLZ / zlib: not built
     if (filter == FILTER_BITSHUFFLE) return ERR_CODEC_SUPPORT;

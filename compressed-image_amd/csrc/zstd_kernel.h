@@ -63,7 +63,7 @@ struct ZstdBlockGeom {
         if (ours && kind_of_launch && split_chunk != (kind_of_launch == 2)) ours = false;
         if (!ours) return 0;
         filter = (int)((f1 >> 8) & 0xFF);
-        if (f0 != 0 || (f1 & 0xFF) != 0 || (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE)) return ERR_CODEC_SUPPORT;
+        if (f0 != 0 || (f1 & 0xFF & ~FILTER_TRUNC_PREC) != 0 || (filter != FILTER_NONE && filter != FILTER_SHUFFLE && filter != FILTER_BITSHUFFLE)) return ERR_CODEC_SUPPORT;
         if (filter == FILTER_BITSHUFFLE && !(flags & FLAG_DONT_SPLIT)) return ERR_CODEC_SUPPORT;          // bit rows are never split
         if (area < ZSTD_KERNEL_AREA_MIN || blocksize > area) return ERR_CODEC_SUPPORT;
         const bool leftover_blk = bsize != blocksize;

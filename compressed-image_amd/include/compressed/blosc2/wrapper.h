@@ -21,6 +21,9 @@
 #include "../macros.h"
 #include "../enums.h"
 #include "../detail/text.h"
+#include "../half.h"
+#include <optional>
+#include <type_traits>
 
 namespace NAMESPACE_COMPRESSED_IMAGE
 {
@@ -107,9 +110,24 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		}
 
 		// ---- contexts -----------------------------------------------------------------------------------------
+		/// Lossy float storage (blosc2's trunc-prec filter, slot 4): the mantissa bits KEPT, 1 .. M with M = 10 / 23 / 52 for
+		/// half / float / double.  std::invalid_argument for any other element type or a value out of range.
 		template <typename T>
-		blosc2_cparams create_blosc2_cparams(size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size)
+		inline constexpr int mantissa_width = std::is_same_v<T, half> ? 10 : std::is_same_v<T, float> ? 23 : std::is_same_v<T, double> ? 52 : 0;
+		template <typename T>
+		void ensure_mantissa_bits(const std::optional<int>& mantissa_bits)
 		{
+			if (!mantissa_bits) return;
+			if (mantissa_width<T> == 0)
+				throw std::invalid_argument("mantissa_bits is only available for floating-point element types (half, float, double)");
+			if (*mantissa_bits < 1 || *mantissa_bits > mantissa_width<T>)
+				throw std::invalid_argument(detail::text("mantissa_bits must lie in 1 .. ", mantissa_width<T>, " for this element type, got ", *mantissa_bits));
+		}
+		template <typename T>
+		blosc2_cparams create_blosc2_cparams(size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size,
+			std::optional<int> mantissa_bits = std::nullopt)
+		{
+			ensure_mantissa_bits<T>(mantissa_bits);
 			if (nthreads > static_cast<size_t>(std::numeric_limits<int16_t>::max()))
 				throw std::out_of_range(detail::text("Number of threads may not exceed ", std::numeric_limits<int16_t>::max(), ", got ", nthreads));
 			blosc2_cparams p = BLOSC2_CPARAMS_DEFAULTS;
@@ -119,20 +137,27 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			p.clevel = compression_level;
 			p.nthreads = static_cast<int16_t>(nthreads == 0 ? 1 : nthreads);    // accepted, ignored: the parallelism is the GPU's
 			p.compcode = codec_to_blosc2(codec);
+			if (mantissa_bits)
+			{
+				p.filters[BLOSC2_MAX_FILTERS - 2] = BLOSC_TRUNC_PREC;
+				p.filters_meta[BLOSC2_MAX_FILTERS - 2] = static_cast<uint8_t>(*mantissa_bits);
+			}
 			// All four codecs of the reference construct (enums.h:18-24).  lz4 and blosclz chunks are the reference's bytes; lz4hc
 			// and zstd chunks are FORMAT-VALID -- every LZ4 / zstd decoder, c-blosc2 included, reads them -- but not liblz4-HC's /
 			// libzstd's bytes (csrc/plan.h, csrc/zstd_encode.h).
 			return p;
 		}
 		template <typename T>
-		context_ptr create_compression_context(size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size)
+		context_ptr create_compression_context(size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size,
+			std::optional<int> mantissa_bits = std::nullopt)
 		{
-			return context_ptr(blosc2_create_cctx(create_blosc2_cparams<T>(nthreads, codec, compression_level, block_size)));
+			return context_ptr(blosc2_create_cctx(create_blosc2_cparams<T>(nthreads, codec, compression_level, block_size, mantissa_bits)));
 		}
 		template <typename T>
-		context_ptr create_compression_context(schunk_ptr& schunk, size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size)
+		context_ptr create_compression_context(schunk_ptr& schunk, size_t nthreads, enums::codec codec, uint8_t compression_level, size_t block_size,
+			std::optional<int> mantissa_bits = std::nullopt)
 		{
-			auto p = create_blosc2_cparams<T>(nthreads, codec, compression_level, block_size);
+			auto p = create_blosc2_cparams<T>(nthreads, codec, compression_level, block_size, mantissa_bits);
 			p.schunk = schunk.get();
 			return context_ptr(blosc2_create_cctx(p));
 		}

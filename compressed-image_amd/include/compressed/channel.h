@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <span>
 #include <stdexcept>
 #include <thread>
@@ -39,12 +40,15 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			make_contexts(s_default_blocksize);
 		}
 
-		/// Compress `data` (width * height elements).  Chunks are aligned to whole scanlines.
+		/// Compress `data` (width * height elements).  Chunks are aligned to whole scanlines.  mantissa_bits (float types only, 1 .. 10 /
+		/// 23 / 52): lossy storage -- only that many mantissa bits of every element are kept (blosc2's trunc-prec filter), here and in
+		/// everything written later (set_chunk, the iterator's write-back, set_region).
 		channel(const std::span<const T> data, size_t width, size_t height,
 			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
-			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_Width(width), m_Height(height)
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
+			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_MantissaBits(mantissa_bits), m_Width(width), m_Height(height)
 		{
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
 			if (data.size() != width * height)
 				throw std::runtime_error(detail::text("Invalid channel data passed. Expected its size to match up to width * height (", width, " * ", height,
 					") which would be ", width * height, ". Instead received ", data.size()));
@@ -55,9 +59,10 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 
 		/// Adopt an existing chunk table.
 		channel(blosc2::schunk_var<T> schunk, size_t width, size_t height,
-			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9)
-			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_Width(width), m_Height(height)
+			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9, std::optional<int> mantissa_bits = std::nullopt)
+			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_MantissaBits(mantissa_bits), m_Width(width), m_Height(height)
 		{
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
 			const size_t have = std::visit([](auto& s) { return s.size(); }, schunk);
 			if (have != width * height)
 				throw std::invalid_argument(detail::text("Invalid schunk passed to compressed::channel constructor. Expected a size of ", width * height, " but instead got ", have));
@@ -101,6 +106,8 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		size_t height() const noexcept { return m_Height; }
 		enums::codec compression() const noexcept { return m_Codec; }
 		uint8_t compression_level() const noexcept { return m_CompressionLevel; }
+		/// mantissa bits kept by everything this channel writes (nullopt: lossless)
+		std::optional<int> mantissa_bits() const noexcept { return m_MantissaBits; }
 
 		size_t compressed_bytes() const { return visit([](auto& s) { return s.csize(); }); }
 		size_t uncompressed_size() const { return visit([](auto& s) { return s.size(); }); }
@@ -239,6 +246,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		blosc2::context_ptr m_CompressionContext = nullptr;
 		blosc2::context_ptr m_DecompressionContext = nullptr;
 		uint8_t m_CompressionLevel = 9;
+		std::optional<int> m_MantissaBits = std::nullopt;
 		bool m_Adopted = false;
 		size_t m_Width = 1;
 		size_t m_Height = 1;
@@ -247,7 +255,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		// libraries' bytes -- enums.h), so an adopted chunk table of any of them can be rewritten like one built from pixels.
 		void make_contexts(size_t block_size)
 		{
-			m_CompressionContext = blosc2::create_compression_context<T>(m_Nthreads, m_Codec, m_CompressionLevel, block_size);
+			m_CompressionContext = blosc2::create_compression_context<T>(m_Nthreads, m_Codec, m_CompressionLevel, block_size, m_MantissaBits);
 			m_DecompressionContext = blosc2::create_decompression_context(m_Nthreads);
 		}
 		void require_encoder() const

@@ -173,12 +173,14 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		device_channel& operator=(const device_channel&) = delete;
 
 		/// Compress `d_data` (width * height elements in device memory).  Chunks are aligned to whole scanlines, as channel<T>'s.
+		/// mantissa_bits: as channel<T>'s (the caller's pixels are not modified; set_region truncates what it writes).
 		device_channel(const T* d_data, size_t width, size_t height,
 			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
-			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_BlockSize(block_size),
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
+			: m_Codec(compression_codec), m_CompressionLevel(util::ensure_compression_level(compression_level)), m_MantissaBits(mantissa_bits), m_BlockSize(block_size),
 			  m_ChunkSize(util::align_chunk_to_scanlines_bytes<T>(width, chunk_size)), m_Width(width), m_Height(height)
 		{
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
 			util::validate_chunk_size<T>(m_ChunkSize, "device_channel");
 			cimg_engine* e = blosc2::batch::engine();
 			const size_t total = width * height * sizeof(T);
@@ -198,7 +200,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		/// The compressed chunks of a host channel, moved over PCIe as they are (fill-value chunks are materialised).
 		static device_channel from_channel(const channel<T>& host)
 		{
-			device_channel out(host.compression(), host.compression_level(), host.block_size(), host.chunk_size(), host.width(), host.height());
+			device_channel out(host.compression(), host.compression_level(), host.block_size(), host.chunk_size(), host.width(), host.height(), host.mantissa_bits());
 			std::vector<std::vector<std::byte>> chunks;
 			detail::host_chunks(host, chunks);
 			const size_t n = chunks.size();
@@ -224,7 +226,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				const std::byte* c = staged.data() + (static_cast<size_t>(m_Store->off[i]) - a);
 				table.append_chunk(std::vector<std::byte>(c, c + m_Store->cbytes[i]));
 			}
-			return channel<T>(blosc2::schunk_var<T>(std::move(table)), m_Width, m_Height, m_Codec, m_CompressionLevel);
+			return channel<T>(blosc2::schunk_var<T>(std::move(table)), m_Width, m_Height, m_Codec, m_CompressionLevel, m_MantissaBits);
 		}
 
 		/// The engine's stream waits for what `stream` (a hipStream_t; nullptr: the null stream) holds now.
@@ -238,6 +240,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		size_t height() const noexcept { return m_Height; }
 		enums::codec compression() const noexcept { return m_Codec; }
 		uint8_t compression_level() const noexcept { return m_CompressionLevel; }
+		std::optional<int> mantissa_bits() const noexcept { return m_MantissaBits; }
 		size_t compressed_bytes() const
 		{
 			require();
@@ -339,7 +342,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		/// The codec parameters the chunks were made with (what set_region hands the engine).
 		cimg_cparams cparams() const
 		{
-			auto ctx = blosc2::create_compression_context<T>(1, m_Codec, m_CompressionLevel, m_BlockSize);
+			auto ctx = blosc2::create_compression_context<T>(1, m_Codec, m_CompressionLevel, m_BlockSize, m_MantissaBits);
 			cimg_cparams out{};
 			const int rc = cimg_context_cparams(ctx.get(), &out);
 			if (rc < 0) throw std::runtime_error(detail::text("Unable to read the compression parameters, error code ", rc));
@@ -432,13 +435,14 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		bool m_ReadOnly = false;
 		enums::codec m_Codec = enums::codec::lz4;
 		uint8_t m_CompressionLevel = 9;
+		std::optional<int> m_MantissaBits = std::nullopt;
 		size_t m_BlockSize = s_default_blocksize;
 		size_t m_ChunkSize = s_default_chunksize;
 		size_t m_Width = 1;
 		size_t m_Height = 1;
 
-		device_channel(enums::codec codec, uint8_t level, size_t block_size, size_t chunk_size, size_t width, size_t height)
-			: m_Codec(codec), m_CompressionLevel(level), m_BlockSize(block_size), m_ChunkSize(chunk_size), m_Width(width), m_Height(height) {}
+		device_channel(enums::codec codec, uint8_t level, size_t block_size, size_t chunk_size, size_t width, size_t height, std::optional<int> mantissa_bits = std::nullopt)
+			: m_Codec(codec), m_CompressionLevel(level), m_MantissaBits(mantissa_bits), m_BlockSize(block_size), m_ChunkSize(chunk_size), m_Width(width), m_Height(height) {}
 		void require() const
 		{
 			if (!m_Store || m_Count == 0)

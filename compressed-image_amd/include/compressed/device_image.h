@@ -26,8 +26,10 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		/// Compress planar channels (each width * height elements in device memory), all in one engine batch.
 		device_image(const std::vector<const T*>& d_channels, size_t width, size_t height, std::vector<std::string> channel_names = {},
 			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
 		{
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
+			m_MantissaBits = mantissa_bits;
 			init(compression_codec, compression_level, block_size, chunk_size, width, height, d_channels.size(), channel_names);
 			if (d_channels.empty()) return;
 			cimg_engine* e = blosc2::batch::engine();
@@ -52,9 +54,10 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		/// Channels that arrive INTERLEAVED in device memory (R G B A R G B A ...): split into planes on the device, then as above.
 		static device_image from_interleaved(const T* d_interleaved, size_t width, size_t height, size_t nchannels, std::vector<std::string> channel_names = {},
 			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
 		{
 			if (nchannels == 0) throw std::runtime_error("Invalid interleaved data passed. Expected at least one channel");
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
 			cimg_engine* e = blosc2::batch::engine();
 			const size_t npixels = width * height;
 			detail::device_range(e, d_interleaved, npixels * nchannels * sizeof(T), "from_interleaved");
@@ -67,7 +70,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			std::vector<const T*> ch(nchannels);
 			for (size_t c = 0; c < nchannels; ++c) ch[c] = reinterpret_cast<const T*>(planes.base + c * stride);
 			// (the batch is enqueued on the engine's stream behind the split, and returns after the stream has been synchronised)
-			return device_image(ch, width, height, std::move(channel_names), compression_codec, compression_level, block_size, chunk_size);
+			return device_image(ch, width, height, std::move(channel_names), compression_codec, compression_level, block_size, chunk_size, mantissa_bits);
 		}
 
 		/// The compressed chunks of a host image, moved over PCIe as they are.  Its channels must share codec, level, block and chunk size.
@@ -79,11 +82,13 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			out.init(chans[0].compression(), chans[0].compression_level(), chans[0].block_size(), chans[0].chunk_size(), host.width(), host.height(),
 				chans.size(), host.channelnames());
 			out.m_ChunkSize = chans[0].chunk_size();
+			out.m_MantissaBits = chans[0].mantissa_bits();
 			std::vector<std::vector<std::byte>> chunks;
 			for (const auto& c : chans)
 			{
-				if (c.compression() != out.m_Codec || c.compression_level() != out.m_CompressionLevel || c.block_size() != out.m_BlockSize || c.chunk_size() != out.m_ChunkSize)
-					throw std::invalid_argument("from_image: the channels of the image differ in codec, level, block size or chunk size");
+				if (c.compression() != out.m_Codec || c.compression_level() != out.m_CompressionLevel || c.block_size() != out.m_BlockSize || c.chunk_size() != out.m_ChunkSize ||
+					c.mantissa_bits() != out.m_MantissaBits)
+					throw std::invalid_argument("from_image: the channels of the image differ in codec, level, block size, chunk size or mantissa bits");
 				detail::host_chunks(c, chunks);
 			}
 			if (chunks.size() != out.m_NumChannels * out.chunks_per_channel()) throw std::runtime_error("from_image: unexpected chunk count");
@@ -218,6 +223,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_ChannelNames = std::move(names);
 		}
 		enums::codec compression() const noexcept { return m_Codec; }
+		std::optional<int> mantissa_bits() const noexcept { return m_MantissaBits; }
 		uint8_t compression_level() const noexcept { return m_CompressionLevel; }
 		size_t chunk_size() const
 		{
@@ -249,6 +255,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		size_t m_NumChannels = 0;
 		enums::codec m_Codec = enums::codec::lz4;
 		uint8_t m_CompressionLevel = 9;
+		std::optional<int> m_MantissaBits = std::nullopt;
 		size_t m_BlockSize = s_default_blocksize;
 		size_t m_ChunkSize = s_default_chunksize;
 		size_t m_Width = 1;
@@ -276,7 +283,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return (total + m_ChunkSize - 1) / m_ChunkSize;
 		}
 		/// a store-less channel with this image's geometry and codec (region checks, windows, cparams)
-		device_channel<T> prototype() const { return device_channel<T>(m_Codec, m_CompressionLevel, m_BlockSize, m_ChunkSize, m_Width, m_Height); }
+		device_channel<T> prototype() const { return device_channel<T>(m_Codec, m_CompressionLevel, m_BlockSize, m_ChunkSize, m_Width, m_Height, m_MantissaBits); }
 		cimg_window channel_window(size_t c, size_t x, size_t y, size_t width, size_t height, size_t out_off) const
 		{
 			device_channel<T> p = prototype();

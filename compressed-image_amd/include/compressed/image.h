@@ -38,10 +38,10 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		image(const image&) = delete;
 		image& operator=(const image&) = delete;
 
-		/// Compress planar channels (each width * height elements).
+		/// Compress planar channels (each width * height elements).  mantissa_bits: as channel<T>'s, for every channel.
 		image(std::vector<std::span<const T>> channels, size_t width, size_t height, std::vector<std::string> channel_names = {},
 			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
 			: m_Width(width), m_Height(height)
 		{
 			adopt_names(channel_names, channels.size());
@@ -54,7 +54,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 
 			// one engine call for every chunk of every channel
 			const size_t aligned = util::align_chunk_to_scanlines_bytes<T>(width, chunk_size);
-			auto cctx = blosc2::create_compression_context<T>(1, compression_codec, level, block_size);
+			auto cctx = blosc2::create_compression_context<T>(1, compression_codec, level, block_size, mantissa_bits);
 			std::vector<blosc2::batch::piece> pieces;
 			std::vector<size_t> first(channels.size() + 1, 0);
 			for (size_t ch = 0; ch < channels.size(); ++ch)
@@ -69,14 +69,14 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			{
 				blosc2::schunk<T> table(block_size, aligned);
 				for (size_t i = first[ch]; i < first[ch + 1]; ++i) table.append_chunk(std::move(chunks[i]));
-				m_Channels.push_back(compressed::channel<T>(blosc2::schunk_var<T>(std::move(table)), width, height, compression_codec, level));
+				m_Channels.push_back(compressed::channel<T>(blosc2::schunk_var<T>(std::move(table)), width, height, compression_codec, level, mantissa_bits));
 			}
 		}
 
 		image(std::vector<std::vector<T>> channels, size_t width, size_t height, std::vector<std::string> channel_names = {},
 			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
-			: image(as_spans(channels), width, height, std::move(channel_names), compression_codec, compression_level, block_size, chunk_size) {}
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
+			: image(as_spans(channels), width, height, std::move(channel_names), compression_codec, compression_level, block_size, chunk_size, mantissa_bits) {}
 
 		/// Compress channels that arrive INTERLEAVED (R G B A R G B A ..., what an image reader hands out per block of
 		/// scanlines; the reference's read path deinterleaves them on the host before compressing, image.h:1555-1880 with
@@ -85,7 +85,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		/// from there, all channels in one engine call.
 		static image from_interleaved(std::span<const T> interleaved, size_t width, size_t height, size_t nchannels, std::vector<std::string> channel_names = {},
 			enums::codec compression_codec = enums::codec::lz4, size_t compression_level = 9,
-			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize)
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
 		{
 			if (nchannels == 0 || interleaved.size() != width * height * nchannels)
 				throw std::runtime_error(detail::text("Invalid interleaved data passed. Expected its size to match up to width * height * channels (", width, " * ", height,
@@ -95,7 +95,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			out.adopt_names(channel_names, nchannels);
 			const uint8_t level = util::ensure_compression_level(compression_level);
 			const size_t aligned = util::align_chunk_to_scanlines_bytes<T>(width, chunk_size);
-			auto cctx = blosc2::create_compression_context<T>(1, compression_codec, level, block_size);
+			auto cctx = blosc2::create_compression_context<T>(1, compression_codec, level, block_size, mantissa_bits);
 			const size_t npixels = width * height, total = npixels * sizeof(T);
 			const size_t stride = blosc2::batch::planar_stride(npixels, sizeof(T));
 			std::vector<blosc2::batch::planar_piece> pieces;
@@ -110,7 +110,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			{
 				blosc2::schunk<T> table(block_size, aligned);
 				for (size_t i = first[ch]; i < first[ch + 1]; ++i) table.append_chunk(std::move(chunks[i]));
-				out.m_Channels.push_back(compressed::channel<T>(blosc2::schunk_var<T>(std::move(table)), width, height, compression_codec, level));
+				out.m_Channels.push_back(compressed::channel<T>(blosc2::schunk_var<T>(std::move(table)), width, height, compression_codec, level, mantissa_bits));
 			}
 			return out;
 		}
@@ -136,11 +136,12 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		}
 		/// note the reference's default level for THIS overload is 5, not 9 (image.h:999)
 		void add_channel(std::span<const T> data, size_t width, size_t height, std::optional<std::string> name = std::nullopt,
-			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 5)
+			enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 5, std::optional<int> mantissa_bits = std::nullopt)
 		{
 			check_dims(width, height, name.value_or(""));
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
 			push_name(name);
-			m_Channels.push_back(compressed::channel<T>(data, width, height, compression_codec, compression_level));
+			m_Channels.push_back(compressed::channel<T>(data, width, height, compression_codec, compression_level, s_default_blocksize, s_default_chunksize, mantissa_bits));
 		}
 
 		void remove_channel(size_t index) { (void)extract_channel(index); }
@@ -327,6 +328,8 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			if (m_Channels.empty()) throw std::runtime_error("Unable to get chunk size from image without channels");
 			return m_Channels.front().chunk_size();
 		}
+		/// mantissa bits kept by the first channel (nullopt: lossless, or no channels)
+		std::optional<int> mantissa_bits() const noexcept { return m_Channels.empty() ? std::nullopt : m_Channels.front().mantissa_bits(); }
 		size_t block_size() const
 		{
 			if (m_Channels.empty()) throw std::runtime_error("Unable to get block size from image without channels");

@@ -166,13 +166,14 @@ namespace
 			});
 		}
 
-		static Channel from_array(const py::array& data, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk)
+		static Channel from_array(const py::array& data, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk, std::optional<int> mantissa)
 		{
 			return dispatch(data.dtype(), [&]<typename T>() {
+				compressed::blosc2::ensure_mantissa_bits<T>(mantissa);          // (ValueError before anything else happens)
 				auto [keep, px] = elements<T>(data);
 				if (px.size() != width * height)
 					throw py::value_error("Channel data has " + std::to_string(px.size()) + " elements, expected width * height = " + std::to_string(width * height));
-				return Channel{ std::make_shared<compressed::channel<T>>(px, width, height, c, static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk) };
+				return Channel{ std::make_shared<compressed::channel<T>>(px, width, height, c, static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk, mantissa) };
 			});
 		}
 		static Channel full(const py::object& dtype, const py::object& fill, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk)
@@ -190,6 +191,7 @@ namespace
 		}
 
 		py::dtype dtype() const { return visit([]<typename T>(compressed::channel<T>&) { return np_dtype<T>(); }); }
+		std::optional<int> mantissa_bits() const { return visit([](auto& c) { return c.mantissa_bits(); }); }
 		size_t width() const { return visit([](auto& c) { return c.width(); }); }
 		size_t height() const { return visit([](auto& c) { return c.height(); }); }
 
@@ -300,9 +302,10 @@ namespace
 
 		explicit Image(any_image adopted) : impl(std::move(adopted)) {}          // (DeviceImage.to_image)
 		Image(const py::object& dtype, const std::vector<py::array>& channels, size_t width, size_t height, std::vector<std::string> names,
-			codec c, size_t level, size_t block, size_t chunk)
+			codec c, size_t level, size_t block, size_t chunk, std::optional<int> mantissa)
 		{
 			impl = dispatch(as_dtype(dtype), [&]<typename T>() -> any_image {
+				compressed::blosc2::ensure_mantissa_bits<T>(mantissa);
 				std::vector<py::array> keep;
 				std::vector<std::span<const T>> spans;
 				for (const auto& a : channels)
@@ -312,20 +315,21 @@ namespace
 					keep.push_back(k);
 					spans.push_back(px);
 				}
-				try { return std::make_shared<compressed::image<T>>(spans, width, height, std::move(names), c, level, block, chunk); }
+				try { return std::make_shared<compressed::image<T>>(spans, width, height, std::move(names), c, level, block, chunk, mantissa); }
 				catch (const std::runtime_error& e) { throw py::value_error(e.what()); }
 			});
 		}
 
-		void add_channel(const py::array& data, size_t width, size_t height, std::optional<std::string> name, codec c, size_t level, size_t block, size_t chunk)
+		void add_channel(const py::array& data, size_t width, size_t height, std::optional<std::string> name, codec c, size_t level, size_t block, size_t chunk, std::optional<int> mantissa)
 		{
 			visit([&]<typename T>(const img_ptr<T>& img) {
+				compressed::blosc2::ensure_mantissa_bits<T>(mantissa);
 				if (!data.dtype().is(np_dtype<T>())) throw py::value_error("channel dtype does not match the image dtype");
 				if (data.ndim() == 2 && (static_cast<size_t>(data.shape(0)) != height || static_cast<size_t>(data.shape(1)) != width))
 					throw py::value_error("array shape does not match (height, width)");
 				auto [keep, px] = elements<T>(data);
 				if (px.size() != width * height) throw py::value_error("array size does not match width * height");
-				compressed::channel<T> ch(px, width, height, c, static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk);
+				compressed::channel<T> ch(px, width, height, c, static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk, mantissa);
 				img->add_channel(std::move(ch), std::move(name));
 				return 0;
 			});
@@ -535,17 +539,19 @@ namespace
 		template <typename F> auto visit(F&& f) const { return std::visit([&](auto& p) { return f(*p); }, impl); }
 
 		static DeviceChannel from_array(const py::object& data, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk,
-			std::optional<uintptr_t> stream)
+			std::optional<uintptr_t> stream, std::optional<int> mantissa)
 		{
 			const device_view v = view_of(data, "DeviceChannel");
 			return dispatch(v.dt, [&]<typename T>() {
+				compressed::blosc2::ensure_mantissa_bits<T>(mantissa);
 				if (v.count() != width * height)
 					throw py::value_error("Channel data has " + std::to_string(v.count()) + " elements, expected width * height = " + std::to_string(width * height));
 				wait_for(stream);
 				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(static_cast<const T*>(v.ptr), width, height, c,
-					static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk) };
+					static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk, mantissa) };
 			});
 		}
+		std::optional<int> mantissa_bits() const { return visit([](auto& c) { return c.mantissa_bits(); }); }
 		static DeviceChannel from_channel(const Channel& host)
 		{
 			return host.visit([]<typename T>(compressed::channel<T>& ch) {
@@ -620,9 +626,10 @@ namespace
 
 		// channels: a list of (H, W) device arrays or one (C, H, W) device array
 		static DeviceImage from_arrays(const py::object& dtype, const py::object& channels, size_t width, size_t height, std::vector<std::string> names,
-			codec c, size_t level, size_t block, size_t chunk, std::optional<uintptr_t> stream)
+			codec c, size_t level, size_t block, size_t chunk, std::optional<uintptr_t> stream, std::optional<int> mantissa)
 		{
 			const py::dtype dt = as_dtype(dtype);
+			dispatch(dt, [&]<typename T>() { compressed::blosc2::ensure_mantissa_bits<T>(mantissa); return 0; });
 			std::vector<device_view> views;
 			if (py::isinstance<py::list>(channels) || py::isinstance<py::tuple>(channels))
 				for (auto o : channels) views.push_back(view_of(py::reinterpret_borrow<py::object>(o), "DeviceImage"));
@@ -649,18 +656,19 @@ namespace
 					ptrs.push_back(static_cast<const T*>(v.ptr));
 				}
 				wait_for(stream);
-				return std::make_shared<compressed::device_image<T>>(ptrs, width, height, std::move(names), c, level, block, chunk);
+				return std::make_shared<compressed::device_image<T>>(ptrs, width, height, std::move(names), c, level, block, chunk, mantissa);
 			}) };
 		}
 		static DeviceImage from_interleaved(const py::object& array, std::vector<std::string> names, codec c, size_t level, size_t block, size_t chunk,
-			std::optional<uintptr_t> stream)
+			std::optional<uintptr_t> stream, std::optional<int> mantissa)
 		{
 			const device_view v = view_of(array, "from_interleaved");
 			if (v.shape.size() != 3) throw py::value_error("from_interleaved: expected an array of the shape (height, width, channels)");
 			return DeviceImage{ dispatch(v.dt, [&]<typename T>() -> any_dimage {
+				compressed::blosc2::ensure_mantissa_bits<T>(mantissa);
 				wait_for(stream);
 				return std::make_shared<compressed::device_image<T>>(compressed::device_image<T>::from_interleaved(static_cast<const T*>(v.ptr),
-					static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]), static_cast<size_t>(v.shape[2]), std::move(names), c, level, block, chunk));
+					static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]), static_cast<size_t>(v.shape[2]), std::move(names), c, level, block, chunk, mantissa));
 			}) };
 		}
 		static DeviceImage from_image(const Image& host)
@@ -740,7 +748,8 @@ PYBIND11_MODULE(compressed_image, m)
 
 	py::class_<Channel>(m, "Channel", py::module_local())
 		.def(py::init(&Channel::from_array), py::arg("data"), py::arg("width"), py::arg("height"), py::arg("compression_codec") = codec::lz4,
-			py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk)
+			py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("mantissa_bits") = std::nullopt)
+		.def("mantissa_bits", &Channel::mantissa_bits)
 		.def_static("full", &Channel::full, py::arg("dtype"), py::arg("fill_value"), py::arg("width"), py::arg("height"),
 			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk)
 		.def_static("zeros", [](const py::object& dtype, size_t w, size_t h, codec c, size_t level, size_t block, size_t chunk) {
@@ -775,11 +784,14 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"));
 
 	py::class_<Image>(m, "Image", py::module_local())
-		.def(py::init<const py::object&, const std::vector<py::array>&, size_t, size_t, std::vector<std::string>, codec, size_t, size_t, size_t>(),
+		.def(py::init<const py::object&, const std::vector<py::array>&, size_t, size_t, std::vector<std::string>, codec, size_t, size_t, size_t, std::optional<int>>(),
 			py::arg("dtype"), py::arg("channels"), py::arg("width"), py::arg("height"), py::arg("channel_names") = std::vector<std::string>{},
-			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk)
+			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk,
+			py::arg("mantissa_bits") = std::nullopt)
+		.def("mantissa_bits", [](const Image& i) { return i.visit([](auto& img) { return img->mantissa_bits(); }); })
 		.def("add_channel", &Image::add_channel, py::arg("data"), py::arg("width"), py::arg("height"), py::arg("name") = std::nullopt,
-			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk)
+			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk,
+			py::arg("mantissa_bits") = std::nullopt)
 		.def("remove_channel", &Image::remove_channel, py::arg("name_or_index"))
 		.def("__getitem__", &Image::channel, py::arg("key"))
 		.def("__len__", [](const Image& i) { return i.visit([](auto& img) { return img->num_channels(); }); })
@@ -814,7 +826,9 @@ PYBIND11_MODULE(compressed_image, m)
 
 	py::class_<DeviceChannel>(m, "DeviceChannel", py::module_local())
 		.def(py::init(&DeviceChannel::from_array), py::arg("data"), py::arg("width"), py::arg("height"), py::arg("compression_codec") = codec::lz4,
-			py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt)
+			py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt,
+			py::arg("mantissa_bits") = std::nullopt)
+		.def("mantissa_bits", &DeviceChannel::mantissa_bits)
 		.def_static("from_channel", &DeviceChannel::from_channel, py::arg("channel"))
 		.def("to_channel", &DeviceChannel::to_channel)
 		.def_property_readonly("dtype", [](const DeviceChannel& c) { return c.visit([]<typename T>(compressed::device_channel<T>&) { return np_dtype<T>(); }); })
@@ -843,10 +857,11 @@ PYBIND11_MODULE(compressed_image, m)
 	py::class_<DeviceImage>(m, "DeviceImage", py::module_local())
 		.def(py::init(&DeviceImage::from_arrays), py::arg("dtype"), py::arg("channels"), py::arg("width"), py::arg("height"),
 			py::arg("channel_names") = std::vector<std::string>{}, py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9,
-			py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt)
+			py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("stream") = std::nullopt, py::arg("mantissa_bits") = std::nullopt)
+		.def("mantissa_bits", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->mantissa_bits(); }); })
 		.def_static("from_interleaved", &DeviceImage::from_interleaved, py::arg("array"), py::arg("channel_names") = std::vector<std::string>{},
 			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk,
-			py::arg("stream") = std::nullopt)
+			py::arg("stream") = std::nullopt, py::arg("mantissa_bits") = std::nullopt)
 		.def_static("from_image", &DeviceImage::from_image, py::arg("image"))
 		.def("to_image", &DeviceImage::to_image)
 		.def("__getitem__", &DeviceImage::channel, py::arg("key"))

@@ -39,8 +39,12 @@ typedef struct cimg_cparams {
     int32_t compcode;        /* BLOSC_LZ4 = 1, BLOSC_BLOSCLZ = 0: the CPU codec's bytes; BLOSC_LZ4HC = 2, BLOSC_ZSTD = 5: format-valid
                               * streams (any LZ4 / zstd decoder reads them), NOT liblz4-HC's / libzstd's bytes.  BLOSC_ZLIB: refused. */
     int32_t splitmode;       /* BLOSC_AUTO_SPLIT = 3 */
-    uint8_t filters[6];      /* default {0,0,0,0,0,BLOSC_SHUFFLE} */
-    uint8_t filters_meta[6];
+    uint8_t filters[6];      /* default {0,0,0,0,0,BLOSC_SHUFFLE}.  filters[5]: none / shuffle / bitshuffle.  filters[4] may be
+                              * BLOSC_TRUNC_PREC = 4 (filters[0..3] == 0): every compress call then zeroes the low mantissa bits of the
+                              * pixels first (a caller's device pixels are left alone: the truncated copy lives in engine scratch) */
+    uint8_t filters_meta[6]; /* filters_meta[4], as int8 m: m > 0 mantissa bits kept, m < 0 bits zeroed; typesize 2 / 4 / 8 = IEEE
+                              * binary16 / 32 / 64.  m == 0, |m| above the mantissa width, nothing kept, or another typesize:
+                              * BLOSC2_ERROR_INVALID_PARAM before anything runs */
 } cimg_cparams;
 
 void cimg_cparams_init(cimg_cparams* p, int32_t typesize);   /* the reference's defaults: lz4, level 9, 32 KiB blocks */
@@ -236,7 +240,8 @@ int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const 
  * the other blocks' streams are copied from the old chunk.  zstd chunks, blocks beyond the normal kernels' LDS, memcpyed and
  * special-zero chunks are decoded, patched and compressed whole on the device.  The input chunks are never modified.
  * Nothing runs, and the call returns BLOSC2_ERROR_INVALID_PARAM, unless every window passes the checks of the window reads, every
- * touched chunk's header agrees with `p` (typesize, codec, filters, split decision, effective blocksize for its nbytes) and every
+ * touched chunk's header agrees with `p` (typesize, codec, filters -- trunc-prec and its meta included: written pixels are truncated
+ * like the chunk's own --, split decision, effective blocksize for its nbytes) and every
  * destsize[i] >= 32.  A damaged touched chunk gets its decode error in status[i] and new_cbytes[i] = 0; the others are still
  * written; the call returns the first failing code.  clevel is not in the header: passing the one the chunks were made with is
  * the caller's job, as it is for compress. */
@@ -330,7 +335,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* packed device storage: the batched gather copy, planes -> interleaved pixels */
        CIMG_K_PACK = 20, CIMG_K_INTERLEAVE = 21,
        /* the window launch of cimg_decompress_windows_strided_device / _host */
-       CIMG_K_DECODE_WINDOW_STRIDED = 22, CIMG_K_COUNT = 23 };
+       CIMG_K_DECODE_WINDOW_STRIDED = 22,
+       /* trunc-prec (filters[4] == 4): the masked copy in front of a compress batch */
+       CIMG_K_TRUNC_PREC = 23, CIMG_K_COUNT = 24 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);
