@@ -20,6 +20,7 @@ K_UPDATE_PATCH, K_UPDATE_LAYOUT, K_UPDATE_EMIT = 17, 18, 19   # window writes (c
 K_PACK, K_INTERLEAVE = 20, 21                  # packed device storage (csrc/pack_kernel.h, csrc/interleave_kernel.h)
 K_DECODE_WINDOW_STRIDED = 22                   # strided windows: the blocks that hold a sampled element (csrc/window_kernel.h)
 K_TRUNC_PREC = 23                              # trunc-prec: the masked copy in front of a compress batch (csrc/trunc_kernel.h)
+K_DECODE_WINDOW_GROUPED = 24                   # grouped windows: every block staged once for all its windows (csrc/window_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -27,7 +28,7 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
-           "cimg_trunc_prec")
+           "cimg_trunc_prec", "cimg_decode_window_grouped")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -50,6 +51,7 @@ EXPORTS = (
     "cimg_engine_debug_stamps", "cimg_engine_read_stamps", "cimg_shared_engine", "cimg_context_cparams",
     "cimg_decompress_windows_device", "cimg_decompress_windows_host", "cimg_engine_window_stats",
     "cimg_decompress_windows_strided_device", "cimg_decompress_windows_strided_host",
+    "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
     "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
     "cimg_interleave_device", "cimg_engine_wait_stream", "cimg_device_range_check",
@@ -189,6 +191,8 @@ def load():
     L.cimg_engine_window_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.cimg_decompress_windows_strided_device.argtypes = L.cimg_decompress_windows_device.argtypes
     L.cimg_decompress_windows_strided_host.argtypes = L.cimg_decompress_windows_host.argtypes
+    L.cimg_decompress_windows_grouped_device.argtypes = L.cimg_decompress_windows_device.argtypes
+    L.cimg_decompress_windows_grouped_host.argtypes = L.cimg_decompress_windows_host.argtypes
     L.cimg_update_windows_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_update_windows_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
     L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
@@ -470,31 +474,37 @@ class Engine:
 
     # ---- windows (include/cimg_hip.h: cimg_window) ----
     def decompress_windows_device(self, d_comp, comp_off, nbytes, blocksize, typesize, specs, d_out, comp_size=None, check=True,
-                                  strided=False):
+                                  strided=False, grouped=False):
         """windows of device-resident chunks into device memory at d_out; returns the per-chunk status.  strided: the specs are
-        cimg_window_strided (with col_pitch) and go through cimg_decompress_windows_strided_device"""
+        cimg_window_strided (with col_pitch) and go through cimg_decompress_windows_strided_device; grouped: the same specs
+        through cimg_decompress_windows_grouped_device (every block staged once)"""
         comp_off, nbytes, blocksize = _i64(comp_off), _i32(nbytes), _i32(blocksize)
         cs = _i32(comp_size) if comp_size is not None else None
-        w = strided_windows(specs) if strided else windows(specs)
+        w = strided_windows(specs) if strided or grouped else windows(specs)
         status = np.zeros(nbytes.size, np.int32)
         fn = load().cimg_decompress_windows_strided_device if strided else load().cimg_decompress_windows_device
+        if grouped:
+            fn = load().cimg_decompress_windows_grouped_device
         rc = fn(self.handle, nbytes.size, d_comp, _ptr(comp_off), _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), typesize,
                 len(specs), w, d_out, _ptr(status))
         if check:
             self._check(rc)
         return status if check else (rc, status)
 
-    def decompress_windows_host(self, chunks, specs, out, check=True, strided=False):
+    def decompress_windows_host(self, chunks, specs, out, check=True, strided=False, grouped=False):
         """chunks: list of bytes; out: a writable uint8 numpy array the windows' out_off / out_pitch point into.  strided: the
-        specs are cimg_window_strided and go through cimg_decompress_windows_strided_host"""
+        specs are cimg_window_strided and go through cimg_decompress_windows_strided_host; grouped: through
+        cimg_decompress_windows_grouped_host"""
         sizes = [len(c) for c in chunks]
         comp_off = _i64(np.concatenate([[0], np.cumsum(sizes[:-1], dtype=np.int64)]))
         comp = np.frombuffer(b"".join(chunks) + bytes(16), np.uint8)
         held = _i32(sizes)
-        w = strided_windows(specs) if strided else windows(specs)
+        w = strided_windows(specs) if strided or grouped else windows(specs)
         status = np.zeros(len(chunks), np.int32)
         assert out.dtype == np.uint8 and out.flags.c_contiguous
         fn = load().cimg_decompress_windows_strided_host if strided else load().cimg_decompress_windows_host
+        if grouped:
+            fn = load().cimg_decompress_windows_grouped_host
         rc = fn(self.handle, len(chunks), _ptr(comp), _ptr(comp_off), _ptr(held), len(specs), w, _ptr(out), _ptr(status))
         if check:
             self._check(rc)

@@ -244,6 +244,18 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_window_strided(Str
     wb.phase_w(wave);
 }
 
+// Grouped windows: workgroup k stages the block of unit k once and writes every item of the unit -- every window that meets the
+// block (GroupedWindowBlock).  The write phase only reads LDS, so the items need no barrier between them.
+extern "C" __global__ __launch_bounds__(256) void cimg_decode_window_grouped(GroupedWindowArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    GroupedWindowBlock gb(a, lds, (int)blockIdx.x);
+    gb.phase_a(wave);
+    __syncthreads();
+    gb.phase_w(wave);
+}
+
 // zstd blocks beyond the normal kernels' LDS.  Encode: cimg_encode_wide's waves with zstd_wide_encode (hash table and FSE tables in
 // LDS, sequences in a device-memory area per wave).  Decode, behind cimg_zstd_walk: the replay with its planes in a device-memory
 // slot per single-wave workgroup, which walks blocks blk_first + k, k + G, ... of the group.
@@ -399,7 +411,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14)
+    int max_dyn_lds[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -601,6 +613,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_ZSTD_LIT: return "cimg_zstd_lit";
     case CIMG_K_DECODE_WINDOW: return "cimg_decode_window";
     case CIMG_K_DECODE_WINDOW_STRIDED: return "cimg_decode_window_strided";
+    case CIMG_K_DECODE_WINDOW_GROUPED: return "cimg_decode_window_grouped";
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
@@ -2122,14 +2135,23 @@ struct EngineWindowEnv : EngineChunks {
 
     int run_items(const WindowPlan& plan, const std::vector<WindowItem>& items, int32_t* status) { return run(plan, items, status); }
     int run_items(const StridedWindowPlan& plan, const std::vector<StridedWindowItem>& items, int32_t* status) { return run(plan, items, status); }
+    // (GroupedEnv: the items sorted by block, one workgroup per unit)
+    int run_units(const StridedWindowPlan& plan, const std::vector<StridedWindowItem>& items, const std::vector<int32_t>& order,
+                  const std::vector<WindowUnit>& units, int32_t* status)
+    {
+        return run(plan, items, status, &units, &order);
+    }
 
-    // the launch over a table of items: cimg_decode_window, or its strided form over StridedWindowItem
+    // the launch over a table of items: cimg_decode_window, or its strided form over StridedWindowItem; units: the grouped form,
+    // whose items go into the table in `order` and whose unit table rides behind them in the same upload
     template <class Item>
-    int run(const WindowPlanT<Item>& plan, const std::vector<Item>& items, int32_t* status)
+    int run(const WindowPlanT<Item>& plan, const std::vector<Item>& items, int32_t* status, const std::vector<WindowUnit>* units = nullptr,
+            const std::vector<int32_t>* order = nullptr)
     {
         int rc;
         const int nchunks = (int)plan.descs.size();
-        const size_t ib = items.size() * sizeof(Item), db = plan.descs.size() * sizeof(ChunkDesc), sb = (size_t)nchunks * 4;
+        const size_t tb = items.size() * sizeof(Item), ub = units ? units->size() * sizeof(WindowUnit) : 0, ib = tb + ub;
+        const size_t db = plan.descs.size() * sizeof(ChunkDesc), sb = (size_t)nchunks * 4;
         if ((rc = e->reserve(e->h_win_items, ib)) || (rc = e->reserve(e->win_items, ib))) return rc;
         if ((rc = e->reserve(e->h_win_descs, db)) || (rc = e->reserve(e->win_descs, db))) return rc;
         if ((rc = e->reserve(e->h_win_st, sb))) return rc;
@@ -2139,7 +2161,13 @@ struct EngineWindowEnv : EngineChunks {
             hd[i].comp_off = plan.touched[(size_t)i] ? comp_off[i] : 0;
             hd[i].destsize = comp_size ? comp_size[i] : 0x7fffffff;
         }
-        memcpy(e->h_win_items.p, items.data(), ib);
+        if (order) {
+            Item* hi = (Item*)e->h_win_items.p;
+            for (size_t k = 0; k < items.size(); k++) hi[k] = items[(size_t)(*order)[k]];
+        } else {
+            memcpy(e->h_win_items.p, items.data(), tb);
+        }
+        if (ub) memcpy((uint8_t*)e->h_win_items.p + tb, units->data(), ub);
         memset(e->h_win_st.p, 0, sb);
         int32_t* d_st = nullptr;
         if ((rc = e->device_alias(e->h_win_st, &d_st))) return rc;
@@ -2152,10 +2180,18 @@ struct EngineWindowEnv : EngineChunks {
         wa.typesize = typesize;
         wa.nitems = (int32_t)items.size();
         if constexpr (std::is_same_v<Item, StridedWindowItem>) {
-            const StridedWindowArgs sa{wa, (const StridedWindowItem*)e->win_items.p};
-            if ((rc = e->allow_lds(cimg_decode_window_strided, 14, plan.lds_bytes))) return rc;
-            e->begin_batch(1);
-            rc = e->launch(CIMG_K_DECODE_WINDOW_STRIDED, cimg_decode_window_strided, sa, (int)items.size(), 256, plan.lds_bytes);
+            if (units) {
+                const GroupedWindowArgs ga{wa, (const StridedWindowItem*)e->win_items.p, (const WindowUnit*)((const uint8_t*)e->win_items.p + tb),
+                                           (int32_t)units->size()};
+                if ((rc = e->allow_lds(cimg_decode_window_grouped, 15, plan.lds_bytes))) return rc;
+                e->begin_batch(1);
+                rc = e->launch(CIMG_K_DECODE_WINDOW_GROUPED, cimg_decode_window_grouped, ga, (int)units->size(), 256, plan.lds_bytes);
+            } else {
+                const StridedWindowArgs sa{wa, (const StridedWindowItem*)e->win_items.p};
+                if ((rc = e->allow_lds(cimg_decode_window_strided, 14, plan.lds_bytes))) return rc;
+                e->begin_batch(1);
+                rc = e->launch(CIMG_K_DECODE_WINDOW_STRIDED, cimg_decode_window_strided, sa, (int)items.size(), 256, plan.lds_bytes);
+            }
         } else {
             wa.items = (const WindowItem*)e->win_items.p;
             if ((rc = e->allow_lds(cimg_decode_window, 12, plan.lds_bytes))) return rc;
@@ -2204,14 +2240,17 @@ int copy_rows(cimg_engine* e, void* dst, int64_t dst_pitch, const void* src, int
     return e->hip(hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)row, (size_t)height, kind, e->stream), what);
 }
 
-template <class Spec>
+// (Grouped: a strided call whose launches are grouped, run_windows_grouped)
+template <bool Grouped = false, class Spec>
 int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
                 const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int32_t check_ts, const std::vector<uint8_t>& hint,
                 int32_t nwindows, const Spec* w, void* d_out, int32_t* status)
 {
     EngineWindowEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, (uint8_t*)d_out, check_ts};
     WindowStats st;
-    const int rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
+    int rc;
+    if constexpr (Grouped) rc = run_windows_grouped(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
+    else rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
     e->win_stats = st;
     if (rc == ERR_INVALID_PARAM) return invalid_window(e, w);
     if (rc < 0) {
@@ -2220,8 +2259,8 @@ int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64
     return rc;
 }
 
-// cimg_decompress_windows_device and its strided form
-template <class Spec>
+// cimg_decompress_windows_device, its strided form and the grouped one
+template <bool Grouped = false, class Spec>
 int windows_device_call(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
                         const int32_t* nbytes, const int32_t* blocksize, int32_t typesize, int32_t nwindows, const Spec* w, void* d_out,
                         int32_t* status)
@@ -2235,11 +2274,11 @@ int windows_device_call(cimg_engine* e, int32_t nchunks, const void* d_comp, con
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     std::vector<int32_t> ts((size_t)nchunks, typesize);
-    return windows_run(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows, w, d_out, status);
+    return windows_run<Grouped>(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, ts.data(), typesize, {}, nwindows, w, d_out, status);
 }
 
-// cimg_decompress_windows_host and its strided form
-template <class Spec>
+// cimg_decompress_windows_host, its strided form and the grouped one
+template <bool Grouped = false, class Spec>
 int windows_host_call(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
                       int32_t nwindows, const Spec* w, void* h_out, int32_t* status)
 {
@@ -2268,8 +2307,8 @@ int windows_host_call(cimg_engine* e, int32_t nchunks, const void* h_comp, const
         HostPin pin_in(e, h_comp, comp_off, hp.up.data(), nchunks, false);
         if ((rc = copy_in(e, e->stream, sc, hp.d_comp_off.data(), hc, comp_off, hp.up.data(), 0, nchunks, "chunk H2D"))) return rc;
         if ((rc = e->hip(hipMemsetAsync(so, 0, (size_t)hp.rows_total, e->stream), "window memset"))) return rc;
-        rc = windows_run(e, nchunks, sc, hp.d_comp_off.data(), hp.cbytes.data(), hp.nbytes.data(), hp.blocksize.data(), hp.typesize.data(), 0,
-                         hp.hint, nwindows, dw.data(), so, status);
+        rc = windows_run<Grouped>(e, nchunks, sc, hp.d_comp_off.data(), hp.cbytes.data(), hp.nbytes.data(), hp.blocksize.data(),
+                                  hp.typesize.data(), 0, hp.hint, nwindows, dw.data(), so, status);
     }
     e->win_stats.comp_bytes_uploaded = hp.comp_bytes_uploaded;
     if (rc == ERR_INVALID_PARAM || rc == ERR_FAILURE) return rc;
@@ -2318,6 +2357,22 @@ int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const 
                                          int32_t* status)
 {
     return windows_host_call(e, nchunks, h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const StridedWindowSpec*>(w), h_out, status);
+}
+
+int cimg_decompress_windows_grouped_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                           const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, int32_t typesize,
+                                           int32_t nwindows, const cimg_window_strided* w, void* d_out, int32_t* status)
+{
+    return windows_device_call<true>(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, typesize, nwindows,
+                                     reinterpret_cast<const StridedWindowSpec*>(w), d_out, status);
+}
+
+int cimg_decompress_windows_grouped_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
+                                         int32_t* status)
+{
+    return windows_host_call<true>(e, nchunks, h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const StridedWindowSpec*>(w), h_out,
+                                   status);
 }
 
 void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded)

@@ -6,6 +6,7 @@
 // chunks are cut from the chunk (or from nothing) without staging; items of chunks that were decoded whole beforehand
 // (zstd, blocks beyond LDS: the batch path into engine scratch) are cut from that copy (`b < 0`).
 // cimg_decode_window_strided (below) stages the same way and writes only every col_pitch-th element of each window row.
+// cimg_decode_window_grouped (at the end) runs one workgroup per distinct block and writes every window that meets it.
 #pragma once
 #include "decode_kernel.h"
 
@@ -238,6 +239,103 @@ struct StridedWindowBlock {
                 }
             }
         }
+    }
+};
+
+// ---- grouped windows: cimg_decode_window_grouped ------------------------------------------------------------------------------
+// One workgroup per UNIT: a block with every item that meets it (window_plan.h: group_items), so a block shared by many windows is
+// staged once.  The unit's first item stages the block (WindowBlock::phase_a, unchanged); after the barrier every item is written
+// with the strided write phase, which only reads LDS -- no barrier between items.  A unit of one item is written by all 256
+// threads, as cimg_decode_window_strided writes it; a unit of more deals its items round-robin over the four waves, each wave
+// writing its item alone with 64 lanes.  A copy-mode item (b < 0) is a unit of its own.
+struct WindowUnit {
+    int32_t item0, nitems;     // items [item0, item0 + nitems) of the table, in window order
+};
+
+struct GroupedWindowArgs {
+    WindowArgs w;              // (w.items unused; w.nitems: items of the table)
+    const StridedWindowItem* items;
+    const WindowUnit* units;
+    int32_t nunits;
+};
+
+struct GroupedWindowBlock {
+    const GroupedWindowArgs& a;
+    WindowUnit u;
+    WindowBlock wb;            // the staged block, through the unit's first item
+
+    CIMG_DEV static WindowUnit uniform_unit(const WindowUnit* p)
+    {
+        WindowUnit t = *p;
+        t.item0 = uni(t.item0); t.nitems = uni(t.nitems);
+        return t;
+    }
+
+    CIMG_DEV GroupedWindowBlock(const GroupedWindowArgs& a_, uint8_t* lds, int k)
+        : a(a_), u(uniform_unit(a_.units + k)), wb(a_.w, lds, WindowBlock::uniform_item(a_.items + u.item0)) {}
+
+    CIMG_DEV void phase_a(int wave) { wb.phase_a(wave); }
+
+    // StridedWindowBlock::phase_w for item k of the table over the staged block, by threads tid0 + lane, + stride, ...
+    // (p0 is the item's own: windows of two planes that share the chunk see the block at different plane offsets)
+    CIMG_DEV void write_item(int k, int tid0, int stride)
+    {
+        const WindowItem it = WindowBlock::uniform_item(a.items + k);
+        const int64_t cpitch = uni64(a.items[k].cpitch);
+        const int ts = uni(a.items[k].ts);
+        const int lg = (ts & (ts - 1)) == 0 ? __builtin_ctz((unsigned)ts) : -1;
+        const int64_t blen = wb.blen, width = it.wbytes / ts;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the block
+            // elements c_lo .. c_hi of the row have a byte in [0, blen)
+            const int64_t lo = -rel - (ts - 1), hi = blen - 1 - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = lo <= 0 ? 0 : (lo + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            const int64_t base = rel + c_lo * cpitch;                          // block offset of element c_lo (>= -(ts - 1))
+            uint8_t* dst = a.w.out + it.out_off + (int64_t)r * it.out_pitch + c_lo * ts;
+            const int64_t n = (c_hi + 1 - c_lo) * ts;                          // (< 2^32: at most blen / ts + 2 elements)
+            // 4-byte units aligned on the destination, as in WindowBlock::phase_w
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t un = u0 + l;
+                    if (un < units) {
+                        const int64_t q0 = 4 * un - mis;
+                        int64_t at[4];
+                        bool all = true;
+                        for (int i = 0; i < 4; i++) {
+                            const int64_t q = q0 + i;
+                            at[i] = -1;
+                            if (q >= 0 && q < n) {
+                                const uint32_t e = lg >= 0 ? (uint32_t)q >> lg : (uint32_t)q / (uint32_t)ts;
+                                const int64_t p = base + (int64_t)e * cpitch + (int64_t)((uint32_t)q - e * (uint32_t)ts);
+                                if (p >= 0 && p < blen) at[i] = p;
+                            }
+                            all = all && at[i] >= 0;
+                        }
+                        if (all) {
+                            const uint32_t v = (uint32_t)wb.byte_at(at[0]) | ((uint32_t)wb.byte_at(at[1]) << 8) |
+                                               ((uint32_t)wb.byte_at(at[2]) << 16) | ((uint32_t)wb.byte_at(at[3]) << 24);
+                            *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                        } else {
+                            for (int i = 0; i < 4; i++)
+                                if (at[i] >= 0) dst[q0 + i] = wb.byte_at(at[i]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    CIMG_DEV void phase_w(int wave)
+    {
+        if (wb.mode == 3) return;                                              // (the block failed to stage: nothing for any item)
+        if (u.nitems == 1) { write_item(u.item0, wave * 64, 256); return; }
+        for (int k = wave; k < u.nitems; k += 4) write_item(u.item0 + k, 0, 64);
     }
 };
 

@@ -8,7 +8,8 @@
 // row -- each once per window -- as work items.  Chunks whose blocks the window kernel cannot stage (zstd, blocks beyond LDS)
 // are decoded whole through the batch path first and cut from there (copy-mode items).  A strided window (StridedWindowSpec, for
 // cimg_decode_window_strided) takes every col_pitch-th element of its rows; its planner lists only the blocks that hold a byte of
-// a sampled element, and run_windows and plan_windows_host serve both kinds of window.
+// a sampled element, and run_windows and plan_windows_host serve both kinds of window.  A grouped call (run_windows_grouped, for
+// cimg_decode_window_grouped) plans and runs the same way and regroups each launch's items by block: group_items.
 //
 // The host-buffer call (cimg_decompress_windows_host) is planned here too, for the engine and the emulator alike: open_window_call
 // (the opening of both read calls), read_named_headers, stage_chunk and pack_rows (shared with update_plan.h) and plan_windows_host,
@@ -16,6 +17,8 @@
 #pragma once
 #include "wide_plan.h"
 #include "window_kernel.h"
+#include <algorithm>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -323,6 +326,120 @@ int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blo
     }
     for (int i = 0; i < nchunks; i++) if (status[i] != 0) return status[i];
     return 0;
+}
+
+// ---- grouped windows: every block staged once, for all the windows that meet it ---------------------------------------------
+// (cimg_decode_window_grouped, window_kernel.h).  plan_windows and run_windows stay as they are -- validation, item listing, the
+// whole route and the second round for chunks found to be zstd -- and the grouping sits between the plan and the launch: the
+// items of a launch are stable-sorted by batch-wide block and cut into units, one per distinct block, whose items keep window
+// order (each with its own p0: windows of two planes may share a chunk).  Copy-mode items follow, each a unit of its own.
+// The sort is given as a permutation -- order[k]: the item that goes to place k of the launch's table -- so that the 96-byte items
+// are moved once, by whoever fills the table; the units name places.  The blocks of a call usually lie close together: a counting
+// sort over their range where that range is small against the items, a sort of (block, index) keys otherwise.
+inline void group_items(const std::vector<StridedWindowItem>& items, std::vector<int32_t>* order, std::vector<WindowUnit>* units)
+{
+    const size_t n = items.size();
+    order->resize(n);
+    units->clear();
+    int64_t lo = INT64_MAX, hi = -1;
+    size_t ndec = 0;
+    for (const StridedWindowItem& t : items)
+        if (t.b >= 0) { lo = t.b < lo ? t.b : lo; hi = t.b > hi ? t.b : hi; ndec++; }
+    size_t at = 0;
+    if (ndec) {
+        const uint64_t range = (uint64_t)(hi - lo) + 1;
+        if (range <= 8 * (uint64_t)ndec + 4096) {
+            std::vector<int32_t> start((size_t)range + 1, 0);
+            for (const StridedWindowItem& t : items) if (t.b >= 0) start[(size_t)(t.b - lo) + 1]++;
+            int32_t pos = 0;
+            for (size_t j = 0; j < (size_t)range; j++) {
+                const int32_t c = start[j + 1];
+                start[j] = pos;
+                if (c) units->push_back(WindowUnit{pos, c});
+                pos += c;
+            }
+            for (size_t k = 0; k < n; k++) if (items[k].b >= 0) (*order)[(size_t)start[(size_t)(items[k].b - lo)]++] = (int32_t)k;
+            at = ndec;
+        } else {
+            std::vector<uint64_t> keys;
+            keys.reserve(ndec);
+            for (size_t k = 0; k < n; k++) if (items[k].b >= 0) keys.push_back(((uint64_t)(uint32_t)items[k].b << 32) | (uint64_t)k);
+            std::sort(keys.begin(), keys.end());                      // (the index in the low half keeps window order inside a block)
+            for (const uint64_t key : keys) {
+                (*order)[at] = (int32_t)(key & 0xffffffffu);
+                if (!units->empty() && items[(size_t)(*order)[(size_t)units->back().item0]].b == (int32_t)(key >> 32)) units->back().nitems++;
+                else units->push_back(WindowUnit{(int32_t)at, 1});
+                at++;
+            }
+        }
+    }
+    for (size_t k = 0; k < n; k++)
+        if (items[k].b < 0) { (*order)[at] = (int32_t)k; units->push_back(WindowUnit{(int32_t)at, 1}); at++; }
+}
+
+// An upper bound of the items plan_windows lists, without listing them: a sample has bytes in at most `typesize` blocks.  The
+// tables of a grouped launch index items and units with int32 (WindowUnit).
+inline bool grouped_counts_fit(int nchunks, const int32_t* typesize, int nwindows, const StridedWindowSpec* w)
+{
+    int64_t bound = 0;
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].width <= 0 || w[k].height <= 0) continue;
+        const int ts = w[k].chunk_first >= 0 && w[k].chunk_first < nchunks && typesize[w[k].chunk_first] > 0 ? typesize[w[k].chunk_first] : 1;
+        const int64_t samples = (int64_t)w[k].width * w[k].height;             // (< 2^62)
+        if (samples > INT32_MAX) return false;
+        bound += samples * ts;                                                 // (< 2^39 a window; the sum is checked as it grows)
+        if (bound > INT32_MAX) return false;
+    }
+    return true;
+}
+
+// run_windows' Env for a grouped call, over an Env that provides decode_whole and
+//   int run_units(const StridedWindowPlan& plan, const std::vector<StridedWindowItem>& items, const std::vector<int32_t>& order,
+//                 const std::vector<WindowUnit>& units, int32_t* status)
+//       -- one grouped launch, waited for, over the table items[order[0]], items[order[1]], ... whose places the units name.
+// blocks: the decode units whose chunk was not found to be zstd, that is, the distinct blocks staged block by block.
+template <class Env>
+struct GroupedEnv {
+    Env& env;
+    int64_t blocks = 0;
+
+    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
+    {
+        return env.decode_whole(list, dst_off, total, st);
+    }
+    int run_items(const StridedWindowPlan& plan, const std::vector<StridedWindowItem>& items, int32_t* status)
+    {
+        if (items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
+        std::vector<int32_t> order;
+        std::vector<WindowUnit> units;
+        group_items(items, &order, &units);
+        const int rc = env.run_units(plan, items, order, units, status);
+        if (rc < 0) return rc;
+        for (const WindowUnit& u : units) {
+            const StridedWindowItem& t = items[(size_t)order[(size_t)u.item0]];
+            if (t.b >= 0 && status[t.chunk] != STATUS_ZSTD_PENDING && status[t.chunk] != STATUS_ZSTD_PENDING_SPLIT) blocks++;
+        }
+        return 0;
+    }
+};
+
+// run_windows with every launch grouped.  Output, status and return value are those of run_windows over the same windows;
+// stats->blocks_decoded counts distinct blocks.  A call whose items might not fit the tables' int32 fields is planned once more up
+// front and refused before anything runs.
+template <class Env>
+int run_windows_grouped(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const StridedWindowSpec* w, std::vector<uint8_t> hint, int32_t* status, WindowStats* stats)
+{
+    if (nwindows > 0 && w && !grouped_counts_fit(nchunks, typesize, nwindows, w)) {
+        StridedWindowPlan plan;
+        const int rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.empty() ? nullptr : hint.data(), &plan);
+        if (rc < 0) return rc;
+        if (plan.items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
+    }
+    GroupedEnv<Env> g{env};
+    const int rc = run_windows(g, nchunks, nbytes, blocksize, typesize, nwindows, w, std::move(hint), status, stats);
+    stats->blocks_decoded = g.blocks;
+    return rc;
 }
 
 // ---- the host-buffer calls: what is decided before anything is staged -----------------------------------------------------------

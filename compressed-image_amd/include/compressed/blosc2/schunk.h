@@ -239,8 +239,7 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 						}
 						else if (r0 < r1)
 						{
-							const int32_t first = static_cast<int32_t>(job.chunks.size());
-							for (size_t k = i; k < j; ++k) { job.chunks.push_back(m_Chunks[k].bytes().data()); job.held.push_back(m_Chunks[k].bytes().size()); }
+							const int32_t first = job.queue_run(i, j - i, [&](size_t k) { return std::pair(m_Chunks[k].bytes().data(), m_Chunks[k].bytes().size()); });
 							auto add = [&](size_t ra, size_t rb, bool partial) {
 								if (ra >= rb) return;
 								size_t ca = 0, cb = ow;

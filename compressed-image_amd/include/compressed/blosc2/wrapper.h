@@ -3,6 +3,7 @@
 // context factories :313-413, size helpers :416-468), served by libcimg_hip.so through
 // include/blosc2.h, plus the *batched* helpers the re-shaped chunk loops use (include/cimg_hip.h).
 #pragma once
+#include <unordered_map>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -368,6 +369,25 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				std::vector<size_t> held;               // bytes each chunk buffer holds
 				std::vector<Window> windows;
 				std::vector<std::byte*> outs;
+				// share_runs (get_regions): a run of chunks that an earlier region of the job queued is not queued again -- first_of
+				// finds it by its first chunk (a table always queues a run whole) -- so that windows of different regions name the
+				// same batch chunks: the condition for the grouped call to stage a shared block once and upload a shared chunk once
+				bool share_runs = false;
+				std::unordered_map<const std::byte*, int32_t> runs;     // a queued run's first chunk -> its index in `chunks`
+				/// Index in `chunks` of the run [first, first + count) of `chunk_at(k)` = {bytes, size}, queued now unless shared
+				template <typename ChunkAt>
+				int32_t queue_run(size_t first, size_t count, ChunkAt&& chunk_at)
+				{
+					const std::byte* key = chunk_at(first).first;
+					if (share_runs)
+						if (auto it = runs.find(key); it != runs.end()) return it->second;
+					if (chunks.size() + count > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+						throw std::out_of_range("too many chunks for one window call");
+					const int32_t at = static_cast<int32_t>(chunks.size());
+					for (size_t k = first; k < first + count; ++k) { auto c = chunk_at(k); chunks.push_back(c.first); held.push_back(c.second); }
+					if (share_runs) runs.emplace(key, at);
+					return at;
+				}
 			};
 			using window_job = window_job_of<cimg_window>;
 			using strided_window_job = window_job_of<cimg_window_strided>;
@@ -383,8 +403,15 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				return cimg_decompress_windows_strided_host(engine(), n, comp, comp_off, held, nwindows, w, out, status);
 			}
 
-			template <typename Window>
-			inline void decompress_windows(window_job_of<Window>& job)
+			// (grouped: cimg_decompress_windows_grouped_host -- every block staged once for all the windows that meet it)
+			inline int decompress_windows_grouped_call(int32_t n, const void* comp, const int64_t* comp_off, const int32_t* held, int32_t nwindows,
+				const cimg_window_strided* w, void* out, int32_t* status)
+			{
+				return cimg_decompress_windows_grouped_host(engine(), n, comp, comp_off, held, nwindows, w, out, status);
+			}
+
+			template <typename Window, typename Call>
+			inline void decompress_windows_with(window_job_of<Window>& job, Call&& call)
 			{
 				if (job.windows.empty()) return;
 				const std::byte* cbase = job.chunks.empty() ? nullptr : job.chunks[0];
@@ -392,6 +419,8 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				std::byte* obase = job.outs[0];
 				for (auto* o : job.outs) if (o < obase) obase = o;
 				const size_t n = job.chunks.size();
+				if (n > static_cast<size_t>(std::numeric_limits<int32_t>::max()) || job.windows.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+					throw std::out_of_range(detail::text("too many chunks or windows for one call: ", n, " chunks, ", job.windows.size(), " windows"));
 				std::vector<int64_t> comp_off(n);
 				std::vector<int32_t> held(n), status(n);
 				for (size_t i = 0; i < n; ++i)
@@ -402,10 +431,22 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					held[i] = static_cast<int32_t>(job.held[i]);
 				}
 				for (size_t k = 0; k < job.windows.size(); ++k) job.windows[k].out_off = job.outs[k] - obase;
-				const int rc = decompress_windows_call(static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+				const int rc = call(static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
 					static_cast<int32_t>(job.windows.size()), job.windows.data(), obase, status.data());
 				if (rc < 0)
 					throw std::runtime_error(detail::text("Error code ", rc, " while decompressing a region of blosc2 chunks (", cimg_last_error(engine()), ")"));
+			}
+			template <typename Window>
+			inline void decompress_windows(window_job_of<Window>& job)
+			{
+				decompress_windows_with(job, [](auto... a) { return decompress_windows_call(a...); });
+			}
+
+			// Many regions in one grouped call (cimg_decompress_windows_grouped_host).  The job was planned with share_runs, so the
+			// regions' windows name the same batch chunks wherever they read the same table.
+			inline void decompress_windows_grouped(strided_window_job& job)
+			{
+				decompress_windows_with(job, [](auto... a) { return decompress_windows_grouped_call(a...); });
 			}
 
 			// Window writes of several planes in one engine call (cimg_update_windows_host): only the blocks the windows meet are decoded

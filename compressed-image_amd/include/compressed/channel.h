@@ -23,6 +23,16 @@
 
 namespace NAMESPACE_COMPRESSED_IMAGE
 {
+	/// One rectangle of a batched read (get_regions): [x, x + width) x [y, y + height), of which every step_y-th row and every
+	/// step_x-th element of those rows are taken -- out_height() rows of out_width() elements.
+	struct region
+	{
+		size_t x = 0, y = 0, width = 0, height = 0, step_x = 1, step_y = 1;
+		size_t out_width() const noexcept { return step_x ? (width + step_x - 1) / step_x : 0; }
+		size_t out_height() const noexcept { return step_y ? (height + step_y - 1) / step_y : 0; }
+		size_t out_elems() const noexcept { return out_width() * out_height(); }
+	};
+
 	template <typename T>
 	struct channel
 	{
@@ -181,6 +191,43 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			blosc2::batch::strided_window_job job;
 			plan_region(out.data(), ow, x, y, width, height, step_x, step_y, job);
 			blosc2::batch::decompress_windows(job);
+		}
+		/// Many rectangles in ONE engine call that decodes every block once, however many of the regions meet it (blocks are runs of
+		/// whole scanlines: regions that share rows share blocks).  The results lie back to back in region order, each row-major
+		/// with its subsampled shape out_height() x out_width().  Every region is checked before anything runs (get_region's
+		/// exceptions); an empty list does nothing.
+		std::vector<T> get_regions(std::span<const region> regions) const
+		{
+			std::vector<T> out(check_regions(regions));
+			get_regions(std::span<T>(out), regions);
+			return out;
+		}
+		void get_regions(std::span<T> out, std::span<const region> regions) const
+		{
+			const size_t total = check_regions(regions);
+			if (out.size() < total)
+				throw std::invalid_argument(detail::text("get_regions: buffer holds ", out.size(), " elements, the regions have ", total));
+			blosc2::batch::strided_window_job job;
+			job.share_runs = true;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				plan_region(out.data() + at, r.out_width(), r.x, r.y, r.width, r.height, r.step_x, r.step_y, job);
+				at += r.out_elems();
+			}
+			blosc2::batch::decompress_windows_grouped(job);
+		}
+		/// Every region checked as get_region checks it; returns the elements of all results together.
+		size_t check_regions(std::span<const region> regions) const
+		{
+			size_t total = 0;
+			for (const region& r : regions)
+			{
+				check_region(r.x, r.y, r.width, r.height);
+				check_steps(r.step_x, r.step_y);
+				total += r.out_elems();
+			}
+			return total;
 		}
 		/// Write `data` (width * height elements, row-major) over the rectangle [x, x + width) x [y, y + height).  Only the blocks
 		/// the rectangle meets are decoded and re-encoded, on the device; the result is what compressing the edited pixels from

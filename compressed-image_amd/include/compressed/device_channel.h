@@ -316,6 +316,41 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)), 1, &w,
 				d_out, status.data()), "Decoding the subsampled region");
 		}
+		/// Many rectangles into device memory in ONE engine call that decodes every block once, however many of the regions meet it.
+		/// The results lie back to back in region order, each row-major with its subsampled shape.  Every region is checked before
+		/// anything runs; an empty list does nothing.
+		void get_regions(T* d_out, std::span<const region> regions) const
+		{
+			const size_t total = check_regions(regions);
+			require();
+			std::vector<cimg_window_strided> w;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				if (r.width && r.height) w.push_back(region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, at * sizeof(T)));
+				at += r.out_elems();
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("get_regions: too many regions for one call");
+			cimg_engine* e = m_Store->engine;
+			detail::device_range(e, d_out, total * sizeof(T), "get_regions");
+			std::vector<int32_t> status(m_Store->num_chunks(), 0);
+			detail::engine_call(e, cimg_decompress_windows_grouped_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base,
+				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)),
+				static_cast<int32_t>(w.size()), w.data(), d_out, status.data()), "Decoding the regions");
+		}
+		/// Every region checked as get_region checks it; returns the elements of all results together.
+		size_t check_regions(std::span<const region> regions) const
+		{
+			size_t total = 0;
+			for (const region& r : regions)
+			{
+				check_region(r.x, r.y, r.width, r.height);
+				check_steps(r.step_x, r.step_y);
+				total += r.out_elems();
+			}
+			return total;
+		}
 		/// Write `d_src` (width * height elements in device memory, row-major) over the rectangle.  Only the blocks it meets are decoded
 		/// and re-encoded; the store is then repacked into a new exact-size allocation (untouched chunks from the old one).
 		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)

@@ -198,6 +198,37 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				detail::engine_call(e, cimg_interleave_device(e, scratch.base, static_cast<int64_t>(stride), static_cast<int32_t>(m_NumChannels),
 					static_cast<int32_t>(sizeof(T)), static_cast<int64_t>(ow * oh), d_out), "Interleaving the region");
 		}
+		/// Many rectangles of every channel into device memory in ONE engine call that decodes every block once.  The results lie back
+		/// to back in region order and, within a region, in channel order (region-major, channel-minor): (N, C, h', w') for N regions
+		/// of one shape.  Every region is checked before anything runs; an empty list does nothing.
+		void get_regions(T* d_out, std::span<const region> regions) const
+		{
+			const size_t per_channel = prototype().check_regions(regions);
+			if (m_NumChannels == 0) return;
+			std::vector<cimg_window_strided> w;
+			size_t at = 0;
+			for (const region& r : regions)
+				for (size_t c = 0; c < m_NumChannels; ++c)
+				{
+					if (r.width && r.height)
+					{
+						device_channel<T> p = prototype();
+						p.m_First = c * chunks_per_channel();
+						p.m_Count = chunks_per_channel();
+						w.push_back(p.region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, at * sizeof(T)));
+					}
+					at += r.out_elems();
+				}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("get_regions: too many regions for one call");
+			cimg_engine* e = m_Store->engine;
+			detail::device_range(e, d_out, per_channel * m_NumChannels * sizeof(T), "get_regions");
+			std::vector<int32_t> status(m_Store->num_chunks(), 0);
+			detail::engine_lock lock(e);
+			detail::engine_call(e, cimg_decompress_windows_grouped_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base,
+				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)),
+				static_cast<int32_t>(w.size()), w.data(), d_out, status.data()), "Decoding the regions");
+		}
 		/// Write planes (num_channels x height x width elements in device memory, channel-major) over the rectangle of every channel:
 		/// one update call, one repack of the store.  Nothing changes unless the whole call succeeds.
 		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)

@@ -222,6 +222,39 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return out;
 		}
 
+		/// Many rectangles of every channel in ONE engine call that decodes every block once (channel<T>::get_regions).  The results
+		/// lie back to back in region order and, within a region, in channel order (region-major, channel-minor), each row-major with
+		/// the region's subsampled shape.  Every region is checked before anything runs; an empty list does nothing.
+		std::vector<T> get_regions(std::span<const region> regions) const
+		{
+			std::vector<T> out(check_regions(regions));
+			get_regions(std::span<T>(out), regions);
+			return out;
+		}
+		void get_regions(std::span<T> out, std::span<const region> regions) const
+		{
+			const size_t total = check_regions(regions);
+			if (out.size() < total)
+				throw std::invalid_argument(detail::text("get_regions: buffer holds ", out.size(), " elements, the regions have ", total));
+			blosc2::batch::strided_window_job job;
+			job.share_runs = true;
+			size_t at = 0;
+			for (const region& r : regions)
+				for (const auto& ch : m_Channels)
+				{
+					ch.plan_region(out.data() + at, r.out_width(), r.x, r.y, r.width, r.height, r.step_x, r.step_y, job);
+					at += r.out_elems();
+				}
+			blosc2::batch::decompress_windows_grouped(job);
+		}
+		/// Every region checked against every channel; returns the elements of all results together.
+		size_t check_regions(std::span<const region> regions) const
+		{
+			size_t total = 0;
+			for (const auto& ch : m_Channels) total += ch.check_regions(regions);
+			return total;
+		}
+
 		/// Write one span per channel (width * height elements each, row-major) over the rectangle of every channel: one engine call
 		/// for all channels that share their codec parameters.  Nothing changes unless the whole call succeeds.
 		void set_region(const std::vector<std::span<const T>>& data, size_t x, size_t y, size_t width, size_t height)

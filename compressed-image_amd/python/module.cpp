@@ -142,6 +142,46 @@ namespace
 		return p;
 	}
 
+	// ---- batched reads: get_regions(xs, ys, width, height, step_x, step_y) and get_pixels(xs, ys) -------------------------
+	// xs / ys: integer sequences or arrays of one length N (anything else: ValueError; a coordinate outside the image: IndexError)
+	inline std::vector<py::ssize_t> coordinate_list(const py::object& o, const char* name)
+	{
+		py::array a = py::array::ensure(o);
+		if (!a) { PyErr_Clear(); throw py::value_error(std::string(name) + " must be a sequence or an array of integers"); }
+		if (a.ndim() != 1) throw py::value_error(std::string(name) + " must be one-dimensional");
+		const char kind = a.dtype().kind();
+		if (a.size() > 0 && kind != 'i' && kind != 'u') throw py::value_error(std::string(name) + " must hold integers, got dtype " + std::string(py::str(a.dtype())));
+		py::array_t<int64_t, py::array::c_style | py::array::forcecast> v(a);
+		std::vector<py::ssize_t> out(static_cast<size_t>(v.size()));
+		for (size_t i = 0; i < out.size(); ++i) out[i] = static_cast<py::ssize_t>(v.data()[i]);
+		return out;
+	}
+	inline std::vector<compressed::region> region_list(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height,
+		py::ssize_t step_x, py::ssize_t step_y)
+	{
+		if (width < 0 || height < 0) throw py::value_error("region sizes must be >= 0");
+		check_steps(step_x, step_y);
+		const auto x = coordinate_list(xs, "xs"), y = coordinate_list(ys, "ys");
+		if (x.size() != y.size()) throw py::value_error("xs and ys must have the same length, got " + std::to_string(x.size()) + " and " + std::to_string(y.size()));
+		std::vector<compressed::region> r(x.size());
+		for (size_t i = 0; i < r.size(); ++i)
+		{
+			if (x[i] < 0 || y[i] < 0) throw py::index_error("region " + std::to_string(i) + " starts at a negative coordinate");
+			r[i] = compressed::region{ static_cast<size_t>(x[i]), static_cast<size_t>(y[i]), static_cast<size_t>(width), static_cast<size_t>(height),
+				static_cast<size_t>(step_x), static_cast<size_t>(step_y) };
+		}
+		return r;
+	}
+	// the result's shape: (N, [C,] h', w') for get_regions, (N, [C]) for get_pixels
+	inline std::vector<py::ssize_t> regions_shape(size_t n, std::optional<size_t> channels, py::ssize_t width, py::ssize_t height, py::ssize_t step_x,
+		py::ssize_t step_y, bool pixels)
+	{
+		std::vector<py::ssize_t> shape{ static_cast<py::ssize_t>(n) };
+		if (channels) shape.push_back(static_cast<py::ssize_t>(*channels));
+		if (!pixels) { shape.push_back(ceil_div(height, step_y)); shape.push_back(ceil_div(width, step_x)); }
+		return shape;
+	}
+
 	// ---- Channel ------------------------------------------------------------------------------------------
 	template <typename T> using chan_ptr = std::shared_ptr<compressed::channel<T>>;
 	using any_channel = std::variant<chan_ptr<compressed::half>, chan_ptr<float>, chan_ptr<double>, chan_ptr<uint8_t>, chan_ptr<int8_t>,
@@ -254,6 +294,20 @@ namespace
 				py::array out(np_dtype<T>(), std::vector<py::ssize_t>{ ceil_div(height, step_y), ceil_div(width, step_x) });
 				ch.get_region(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(out.size())), static_cast<size_t>(x),
 					static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height), static_cast<size_t>(step_x), static_cast<size_t>(step_y));
+				return out;
+			});
+		}
+
+		// N rectangles of one size at (xs[i], ys[i]) as an (N, h', w') array (pixels: 1 x 1 regions as an (N,) array): one engine call
+		// that decodes every block once
+		py::array get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, py::ssize_t step_x, py::ssize_t step_y,
+			bool pixels) const
+		{
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			return visit([&]<typename T>(compressed::channel<T>& ch) {
+				ch.check_regions(regions);
+				py::array out(np_dtype<T>(), regions_shape(regions.size(), std::nullopt, width, height, step_x, step_y, pixels));
+				if (out.size() > 0) ch.get_regions(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(out.size())), regions);
 				return out;
 			});
 		}
@@ -390,6 +444,18 @@ namespace
 				compressed::blosc2::batch::decompress_windows(job);
 				py::list out;
 				for (auto& a : arrays) out.append(a);
+				return out;
+			});
+		}
+		// N rectangles of every channel as an (N, C, h', w') array (pixels: an (N, C) array): one engine call
+		py::array get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, py::ssize_t step_x, py::ssize_t step_y,
+			bool pixels) const
+		{
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			return visit([&]<typename T>(const img_ptr<T>& img) {
+				img->check_regions(regions);
+				py::array out(np_dtype<T>(), regions_shape(regions.size(), img->num_channels(), width, height, step_x, step_y, pixels));
+				if (out.size() > 0) img->get_regions(std::span<T>(static_cast<T*>(out.mutable_data()), static_cast<size_t>(out.size())), regions);
 				return out;
 			});
 		}
@@ -588,6 +654,20 @@ namespace
 				return ret;
 			});
 		}
+		// Channel.get_regions / get_pixels into device memory: `out` or a new DeviceArray
+		py::object get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& out,
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels) const
+		{
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				ch.check_regions(regions);
+				auto [p, ret] = result_target<T>(out, regions_shape(regions.size(), std::nullopt, width, height, step_x, step_y, pixels),
+					pixels ? "get_pixels" : "get_regions");
+				wait_for(stream);
+				ch.get_regions(p, regions);
+				return ret;
+			});
+		}
 		// a[key] as Channel.__getitem__ has it, into a new DeviceArray
 		py::object getitem(const py::object& key) const
 		{
@@ -715,6 +795,20 @@ namespace
 				return ret;
 			});
 		}
+		// Image.get_regions / get_pixels into device memory: `out` or a new DeviceArray
+		py::object get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& out,
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels) const
+		{
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+				if (img->num_channels()) img->channel(0).check_regions(regions);
+				auto [p, ret] = result_target<T>(out, regions_shape(regions.size(), img->num_channels(), width, height, step_x, step_y, pixels),
+					pixels ? "get_pixels" : "get_regions");
+				wait_for(stream);
+				img->get_regions(p, regions);
+				return ret;
+			});
+		}
 		// one (C, h, w) device array over the rectangle at (x, y) of every channel
 		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream)
 		{
@@ -780,6 +874,11 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_decompressed", &Channel::get_decompressed)
 		.def("get_region", &Channel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1,
 			py::arg("step_y") = 1)
+		.def("get_regions", [](const Channel& c, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, py::ssize_t sx, py::ssize_t sy) {
+				return c.get_regions(xs, ys, w, h, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_pixels", [](const Channel& c, const py::object& xs, const py::object& ys) { return c.get_regions(xs, ys, 1, 1, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"))
 		.def("__getitem__", &Channel::getitem, py::arg("key"))
 		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"));
 
@@ -800,6 +899,11 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_decompressed", &Image::get_decompressed)
 		.def("get_region", &Image::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1,
 			py::arg("step_y") = 1)
+		.def("get_regions", [](const Image& i, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, py::ssize_t sx, py::ssize_t sy) {
+				return i.get_regions(xs, ys, w, h, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_pixels", [](const Image& i, const py::object& xs, const py::object& ys) { return i.get_regions(xs, ys, 1, 1, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"))
 		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("print_statistics", [](const Image& i) { i.visit([](auto& img) { img->print_statistics(); return 0; }); })
@@ -851,6 +955,13 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_decompressed", &DeviceChannel::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceChannel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
 			py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_regions", [](const DeviceChannel& c, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& out,
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy) { return c.get_regions(xs, ys, w, h, out, stream, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt,
+			py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_pixels", [](const DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream) {
+				return c.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
 		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt);
 
@@ -870,6 +981,13 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_decompressed", &DeviceImage::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceImage::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
 			py::arg("interleaved") = false, py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_regions", [](const DeviceImage& i, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& out,
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy) { return i.get_regions(xs, ys, w, h, out, stream, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt,
+			py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("get_pixels", [](const DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream) {
+				return i.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt)
 		.def("get_channel_index", [](const DeviceImage& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("get_channel_names", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->channelnames(); }); })

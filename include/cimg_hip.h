@@ -231,6 +231,20 @@ int cimg_decompress_windows_strided_device(cimg_engine* e, int32_t nchunks, cons
 int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                                          const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
                                          int32_t* status);
+/* Grouped windows: many windows a call, every block staged once.  The strided calls above run one workgroup per (window, block), so a
+ * block that several windows meet -- blocks are runs of whole scanlines: regions that share rows share blocks wherever they lie in x
+ * -- is decoded once per window.  These two take the same arguments and give the same output bytes, status[] and return value as
+ * the strided call with the same windows (col_pitch 1 is the plain window), with the same locking and the same voiding of pending
+ * _begin calls; the host call uploads the same chunks.  They run one workgroup per distinct block, which writes every window that
+ * meets it, and cimg_engine_window_stats reports blocks_decoded as the number of distinct blocks staged.  A call whose work items
+ * do not fit the launch tables' int32 fields is refused with BLOSC2_ERROR_INVALID_PARAM. */
+int cimg_decompress_windows_grouped_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                           const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize,
+                                           int32_t typesize, int32_t nwindows, const cimg_window_strided* w, void* d_out,
+                                           int32_t* status);
+int cimg_decompress_windows_grouped_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
+                                         int32_t* status);
 
 /* ---- window writes: edit compressed planes in place of get_chunk + set_chunk ------------------------
  * The windows are cimg_window, with out_off / out_pitch describing the SOURCE: row r of a window is taken from
@@ -337,7 +351,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* the window launch of cimg_decompress_windows_strided_device / _host */
        CIMG_K_DECODE_WINDOW_STRIDED = 22,
        /* trunc-prec (filters[4] == 4): the masked copy in front of a compress batch */
-       CIMG_K_TRUNC_PREC = 23, CIMG_K_COUNT = 24 };
+       CIMG_K_TRUNC_PREC = 23,
+       /* the window launch of cimg_decompress_windows_grouped_device / _host */
+       CIMG_K_DECODE_WINDOW_GROUPED = 24, CIMG_K_COUNT = 25 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

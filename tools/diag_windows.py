@@ -17,6 +17,12 @@ Strided leg (second table), against the route it replaces:
       It runs in a child process (`--strided-leg`) that imports torch first, so that torch and the engine share one HIP runtime;
       and the Python module: Channel.get_region(0, 0, 4096, 4096, step_x=8, step_y=8) on the 4096^2 float16 channel of (2) against
       get_decompressed()[::8, ::8], wall time.
+Grouped leg (third table): many regions a call on the plane of (1), in a child process (`--grouped-leg`, torch
+first) that can also be run on its own -- `python tools/diag_windows.py --grouped-leg` writes profiles/grouped/diag_windows_grouped.json:
+  (6) sixteen 1024^2 tiles in a row, 64 seeded random 256^2 crops, 4096 seeded random pixels and 64 disjoint windows that share no
+      block, each through cimg_decompress_windows_grouped_device against the strided multi-window call over the same windows
+      (kernel time, wall time with its spread over the REPS runs, both block counts), against the whole decode followed by torch
+      indexing (its kernel time: K_DECODE plus torch's indexing between two events), and against N single get_region calls through DeviceChannel (and DeviceChannel.get_regions / get_pixels itself).
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -27,7 +33,8 @@ import sysconfig
 import time
 
 STRIDED_LEG = "--strided-leg" in sys.argv
-if STRIDED_LEG:
+GROUPED_LEG = "--grouped-leg" in sys.argv
+if STRIDED_LEG or GROUPED_LEG:
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,6 +109,117 @@ def strided_leg():
                 parent_copy_kernel_us=round(float(np.median(copy_us[1:])), 1), parent_kernel_us=round(par_k, 1), parent_wall_us=round(par_w, 1),
                 strided_kernel_ratio=round(par_k / str_k, 2), strided_wall_ratio=round(par_w / str_w, 2))
 
+
+def grouped_leg():
+    """(6), in the child process: many regions a call, grouped against strided, whole decode + torch indexing, and N single calls"""
+    rng = np.random.default_rng(6)
+    cases = {
+        "tiles16_1024": [(1024 * k, 7000, 1024, 1024) for k in range(16)],
+        "crops64_256": [(int(x), int(y), 256, 256) for x, y in zip(rng.integers(0, n - 256, 64), rng.integers(0, n - 256, 64))],
+        "pixels4096": [(int(x), int(y), 1, 1) for x, y in zip(rng.integers(0, n, 4096), rng.integers(0, n, 4096))],
+        # a 32 KiB block is half a row: windows in different rows, or in the two halves of the same rows, share none
+        "disjoint64": [(1000 + (k % 2) * 8192, 200 * (k // 2), 256, 64) for k in range(64)],
+    }
+    full = torch.empty(n * n, dtype=torch.float32, device="cuda")
+    plane_t = torch.from_numpy(img).cuda()
+    path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
+    spec_m = importlib.util.spec_from_file_location("compressed_image", path)
+    ci = importlib.util.module_from_spec(spec_m)
+    spec_m.loader.exec_module(ci)
+    dch = ci.DeviceChannel(plane_t, n, n, block_size=32768, chunk_size=chunk)
+    del plane_t
+    out = {}
+
+    def timed_all(fn, kernels, extra=None):
+        """extra: a function that returns the microseconds of the kernels fn ran outside the engine (torch's, from events)"""
+        fn()
+        eng.enable_timing(1)
+        walls, kus = [], []
+        for _ in range(REPS):
+            eng.reset_timing()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t) * 1e6)
+            kus.append(sum(eng.kernel_time(k)[0] for k in kernels) * 1e3 + (extra() if extra else 0.0))
+        eng.enable_timing(0)
+        return dict(kernel_us=round(float(np.median(kus)), 1), wall_us=round(float(np.median(walls)), 1),
+                    wall_min_us=round(float(np.min(walls)), 1), wall_max_us=round(float(np.max(walls)), 1),
+                    kernel_min_us=round(float(np.min(kus)), 1), kernel_max_us=round(float(np.max(kus)), 1))
+
+    for name, regs in cases.items():
+        specs, at = [], 0
+        for (x, y, w_, h_) in regs:
+            specs.append(dict(chunk_first=0, chunk_count=nch, origin=y * n + x, row_pitch=n, col_pitch=1, width=w_, height=h_, out_off=at,
+                              out_pitch=w_ * 4))
+            at += w_ * h_ * 4
+        d_out = eng.alloc(at)
+        want = np.concatenate([img[y:y + h_, x:x + w_].ravel() for (x, y, w_, h_) in regs])
+        r = {"regions": len(regs), "out_bytes": at}
+        for kind, kid in (("grouped", hip.K_DECODE_WINDOW_GROUPED), ("strided", hip.K_DECODE_WINDOW_STRIDED)):
+            d_out.upload(np.zeros(at, np.uint8))
+            call = lambda: eng.decompress_windows_device(d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, 4, specs, d_out.ptr, comp_size=cb,  # noqa: E731
+                                                         strided=kind == "strided", grouped=kind == "grouped")
+            r[kind] = timed_all(call, (kid,))
+            r[kind]["blocks"] = eng.window_stats()["blocks_decoded"]
+            assert np.array_equal(d_out.download().view(np.float32), want), (name, kind)
+        d_out.free()
+        xs, ys = [g[0] for g in regs], [g[1] for g in regs]
+        w_, h_ = regs[0][2], regs[0][3]
+        kept = []
+        ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def whole_route():
+            eng.decompress_device(d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, full.data_ptr(), raw_off, comp_size=cb)
+            f2 = full.view(n, n)
+            ev_a.record()                                  # torch's part (index upload, gather or stack) between two events
+            if w_ == 1:
+                kept[:] = [f2[torch.as_tensor(ys, device="cuda"), torch.as_tensor(xs, device="cuda")]]
+            else:
+                kept[:] = [torch.stack([f2[y:y + h_, x:x + w_] for x, y in zip(xs, ys)])]
+            ev_b.record()
+
+        index_us = []
+
+        def torch_part():                                  # (timed_all has synchronized)
+            index_us.append(ev_a.elapsed_time(ev_b) * 1e3)
+            return index_us[-1]
+
+        r["whole_decode_torch_index"] = timed_all(whole_route, (hip.K_DECODE, hip.K_DECODE_ZSTD), torch_part)
+        r["whole_decode_torch_index"]["index_us"] = round(float(np.median(index_us)), 1)
+        assert np.array_equal(kept[0].cpu().numpy().ravel(), want), name
+        res_t = torch.empty(at // 4, dtype=torch.float32, device="cuda")
+
+        def singles():
+            o = 0
+            for (x, y, ww, hh) in regs:
+                dch.get_region(x, y, ww, hh, out=res_t[o:o + ww * hh].view(hh, ww))
+                o += ww * hh
+
+        r["single_get_region_calls"] = timed_all(singles, ())
+        assert np.array_equal(res_t.cpu().numpy(), want), name
+        if w_ == 1:
+            r["device_channel_batched"] = timed_all(lambda: dch.get_pixels(xs, ys, out=res_t), ())
+        else:
+            r["device_channel_batched"] = timed_all(lambda: dch.get_regions(xs, ys, w_, h_, out=res_t.view(len(regs), h_, w_)), ())
+        assert np.array_equal(res_t.cpu().numpy(), want), name
+        out[name] = r
+    return out
+
+
+if GROUPED_LEG:
+    line = json.dumps(grouped_leg())
+    print("GROUPED " + line)
+    if "--out" in sys.argv:
+        dst = sys.argv[sys.argv.index("--out") + 1]
+    else:
+        dst = os.path.join(ROOT, "profiles", "grouped", "diag_windows_grouped.json")
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    open(dst, "w").write(line + "\n")
+    d_raw.free(); d_comp.free(); d_win.free()
+    eng.close()
+    sys.exit(0)
 
 if STRIDED_LEG:
     print("STRIDED " + json.dumps(strided_leg()))
@@ -208,6 +326,11 @@ child = subprocess.run([sys.executable, os.path.abspath(__file__), "--strided-le
 got = [ln for ln in child.stdout.splitlines() if ln.startswith("STRIDED ")]
 assert child.returncode == 0 and got, child.stdout[-2000:] + child.stderr[-4000:]
 res.update(json.loads(got[0][len("STRIDED "):]))
+# (6): in a process of its own; it writes profiles/grouped/diag_windows_grouped.json itself
+child = subprocess.run([sys.executable, os.path.abspath(__file__), "--grouped-leg"], capture_output=True, text=True, timeout=1800)
+got = [ln for ln in child.stdout.splitlines() if ln.startswith("GROUPED ")]
+assert child.returncode == 0 and got, child.stdout[-2000:] + child.stderr[-4000:]
+res["grouped"] = json.loads(got[0][len("GROUPED "):])
 line = json.dumps(res)
 print(line)
 if len(sys.argv) > 2 and sys.argv[1] == "--out":
