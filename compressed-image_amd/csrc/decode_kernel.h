@@ -701,7 +701,9 @@ CIMG_DEV int lz4_decode_wave(uint8_t* lds, int base, int n, int cs, int csize, i
 // ---- a batch of up to 63 tokens, executed at once (shared by lz4_decode_wave2 and the zstd executor) --------------------------------
 // Token k < cnt: lit[k] literal bytes at offset lsrc[k], then a match of ml[k] bytes at distance off[k] (ml 0: none).  All
 // offsets are relative to `lds` (MP: a generic pointer, or an address-space-3 one where the compiler cannot see that it is LDS);
-// [base, oend) is the output, clampmax the last dword that may be READ.  op: where the batch's output starts (moved behind it).
+// [base, oend) is the output, clampmax the last dword that may be READ (every byte a token NEEDS -- its literals, its match's
+// source -- must lie at or below that dword: the clamp only keeps the bytes a 16-byte fetch takes along in range).  op: where the
+// batch's output starts (moved behind it).
 // A batch that would overrun oend is executed up to the first token that does not fit: cut_out = its index (-1: none).
 // Returns 0, or ERR_DATA for a match that reaches in front of `base`.
 #define LZ_LD32(p) (*(LZ_WP)(p))

@@ -735,7 +735,12 @@ CIMG_DEV int zstd_execute_batch(DP dst, int dcap, int* dpos_io, DP lit, int rege
         const bool shared_turn = true;
 #endif
         // (its positions are 18-bit: an output that reaches 2^18 bytes -- a 256 KiB stream -- takes the byte-exact form below)
-        if (shared_turn && mlo != nullptr && gd - mis >= (uintptr_t)mlo && (uintptr_t)mhi >= gd - mis + 8 && dcap + mis + 64 <= (1 << 18)) {
+        // Its dword loads are CLAMPED to the readable range, which is right for the bytes a fetch takes along behind what it needs and
+        // wrong for bytes it needs: the whole output area -- the block's literals lie at its END -- must be readable dword by dword,
+        // i.e. mhi (4-byte aligned) must not lie below dst + dcap.  A capacity that is no multiple of four next to the end of readable
+        // memory (the host tests: mhi = the output buffer's end rounded DOWN) left the last dcap % 4 bytes outside: literals parked
+        // there were fetched from the dword in front of them.  Such an output takes the byte-exact form below.
+        if (shared_turn && mlo != nullptr && gd - mis >= (uintptr_t)mlo && (uintptr_t)mhi >= gd - mis + 8 && (uintptr_t)mhi >= gd + (uintptr_t)dcap && dcap + mis + 64 <= (1 << 18)) {
             const int64_t span = (int64_t)((uintptr_t)mhi - (gd - mis));
             const int clampmax = (int)(((span < (1 << 18) ? span : (1 << 18) - 4) - 4) & ~3ll);
             const int lit0 = (int)((uintptr_t)(const uint8_t*)lit - gd) + mis + lpos;
@@ -759,7 +764,13 @@ CIMG_DEV int zstd_execute_batch(DP dst, int dcap, int* dpos_io, DP lit, int rege
             const uintptr_t a = (uintptr_t)(const uint8_t*)(sp) & ~(uintptr_t)3;
             fast[l] = act[l] & (ll[l] > 0) & (mlo != nullptr) & (a >= (uintptr_t)mlo) & (a + 20 <= (uintptr_t)mhi);
             slow[l] = act[l] & (ll[l] > 0) & !fast[l];
-            if (mlo != nullptr) first[l] = zstd_fetch16_t<DP>(fast[l] ? sp : dst);          // (a lane that is not fast fetches from the start of the output and drops it)
+        }
+        // (a lane that is not fast fetches from the start of the output and drops it -- readable when some lane is fast: the literals
+        // lie behind it, at the end of the output.  With no fast lane nothing is fetched: an output of less than 20 bytes has no such
+        // range, and the fetch used to read past its end)
+        const bool any_fast = ballot(fast) != 0;
+        FOR_LANES(l) {
+            if (any_fast) first[l] = zstd_fetch16_t<DP>(fast[l] ? lit + lpos + lsum[l] : dst);
             else { first[l].x = 0; first[l].y = 0; first[l].z = 0; first[l].w = 0; }
         }
         // runs with more than 16 bytes (and runs next to unreadable memory: whole) in sequence order, by the whole wave

@@ -14,12 +14,15 @@ format and in the BloscLZ stream format (the one described at the top of oracle/
            bytes: distance = 8192 + that, up to 73727).  A stream does not end in a match.
 
 Everything is generated from seeds: the CPU and the GPU leg build the same streams and chunks.
+
+Codec "zstd" (codec format 4, compcode 5): a stream of a chunk is one complete zstd frame, written by tests/_zstd_streams.py
+(coded_stream hands over to it; zstd_plane_cases are its planes, for test_emu_zstd_streams.py and test_gpu_zstd_streams.py).
 """
 import numpy as np
 
-LZ4, BLOSCLZ = "lz4", "blosclz"
-COMPCODE = {BLOSCLZ: 0, LZ4: 1}
-COMPFORMAT = {BLOSCLZ: 0, LZ4: 1}
+LZ4, BLOSCLZ, ZSTD = "lz4", "blosclz", "zstd"
+COMPCODE = {BLOSCLZ: 0, LZ4: 1, ZSTD: 5}
+COMPFORMAT = {BLOSCLZ: 0, LZ4: 1, ZSTD: 4}
 LZ4_MAX_OFFSET = 65535
 BLZ_MAX_NEAR = 8191
 BLZ_MAX_FAR = 65535 + 8192
@@ -403,6 +406,9 @@ def header(codec, ts, nbytes, blocksize, cbytes, filt, split):
 
 def coded_stream(rng, n, codec, flavor):
     """(stream bytes, reference) of a coded plane of n bytes, or None when the flavor's stream would not be smaller than n"""
+    if codec == ZSTD:                                # (one complete frame per stream: tests/_zstd_streams.py)
+        import _zstd_streams as Z
+        return Z.coded_frame(rng, n, flavor)
     if flavor == "headtail" and n >= 64:
         seqs, ref = head_tail(rng, n, codec, slack=int(rng.choice([1, 2, 9])))
     elif flavor == "tokens" and n >= 256:
@@ -433,7 +439,8 @@ def make_chunk(rng, codec, ts, blocksize, nbytes, filt, split, layout="natural",
     """A blosc2 chunk of generated streams -> (chunk bytes, expected pixels, {kind: count}).
 
     Every stream picks a kind on its own: coded (a generated stream of one of `flavors`), stored, zero run or byte run
-    (policy "lean": at most one coded plane a block, the blocks the lean decode kernel takes; "coded": mostly coded planes).  layout: "natural" (blocks in
+    (policy "lean": at most one coded plane a block, the blocks the lean decode kernel takes; "coded": mostly coded planes; "all":
+    every plane coded).  layout: "natural" (blocks in
     order, back to back), "shuffled" (bstarts in a shuffled order) or "gaps" (shuffled, with garbage between the blocks)."""
     assert blocksize % ts == 0 and blocksize <= nbytes
     nblocks = -(-nbytes // blocksize)
@@ -448,6 +455,8 @@ def make_chunk(rng, codec, ts, blocksize, nbytes, filt, split, layout="natural",
         for s in range(ns):
             if policy == "lean":
                 kind = "coded" if s == coded_plane else str(rng.choice(["stored", "zero", "run"]))
+            elif policy == "all":
+                kind = "coded"
             else:
                 kind = str(rng.choice(["coded"] * (6 if policy == "coded" else 3) + ["stored", "zero", "run"]))
             got = coded_stream(rng, ne, codec, str(rng.choice(list(flavors)))) if kind == "coded" else None
@@ -513,6 +522,32 @@ def plane_cases():
     return cases
 
 
+def zstd_plane_cases():
+    """Planes of zstd chunks (codec format 4; every stream one spec-built frame of tests/_zstd_streams.py): typesizes 1, 2, 4, 8, split and
+    unsplit, the three filters, leftover blocks and the three layouts; then unsplit blocks of 128 KiB + 15 / 17 / 33 bytes (a
+    tight second zstd block in every frame) and blocks of 192 KiB (frames of two blocks)."""
+    cases = []
+    layouts = ("natural", "shuffled", "gaps")
+    flavors = ("raw", "huf", "repeat", "tokens", "blocks", "counts")
+    k = 0
+    for ts in (1, 2, 4, 8):
+        for filt in (NOFILTER, SHUFFLE, BITSHUFFLE):
+            split = filt == SHUFFLE and ts > 1
+            bs = {1: 8192, 2: 8192, 4: 16384, 8: 32768}[ts]
+            cases.append(("zstd_ts%d_f%d" % (ts, filt), ZSTD, ts, dict(
+                blocksize=bs, chunk=4 * bs + 3 * ts, last=bs + 5 * ts, filt=filt, split=split, layout=layouts[k % 3],
+                policy="any" if k % 2 else "coded", flavors=flavors)))
+            k += 1
+    cases.append(("zstd_ts4_unsplit_shuffle", ZSTD, 4, dict(blocksize=16384, chunk=3 * 16384 + 8, last=16384 + 4, filt=SHUFFLE, split=False,
+                                                            layout="gaps", policy="coded", flavors=flavors)))
+    for t in (15, 17, 33):
+        cases.append(("zstd_tail%d" % t, ZSTD, 1, dict(blocksize=131072 + t, chunk=131072 + t, last=131072 + t + 5, filt=NOFILTER, split=False,
+                                                       layout=layouts[t % 3], policy="all", flavors=("tail", "tail", "huf"), nchunks=2)))
+    cases.append(("zstd_192k", ZSTD, 2, dict(blocksize=196608, chunk=196608, last=196608 + 98, filt=SHUFFLE, split=False, layout="shuffled",
+                                             policy="all", flavors=("tail", "repeat", "blocks"), nchunks=2)))
+    return cases
+
+
 def wide_cases():
     """Blocks of 128 to 256 KiB: the wide decode kernel, BloscLZ planes beyond 64 KiB with far matches and long headers"""
     return [
@@ -532,7 +567,8 @@ def wide_cases():
 
 
 def build_plane(name, codec, ts, kw, seed=7, nchunks=4):
-    """-> (chunks, plane pixels, kind counts): nchunks chunks, the last one `kw['last']` bytes"""
+    """-> (chunks, plane pixels, kind counts): nchunks chunks (kw['nchunks'] where a case says so), the last one `kw['last']` bytes"""
+    nchunks = kw.get("nchunks", nchunks)
     rng = np.random.default_rng([seed, sum(name.encode())])
     chunks, pix = [], []
     counts = {"coded": 0, "stored": 0, "zero": 0, "run": 0}
