@@ -59,6 +59,7 @@ EXPORTS = (
     "blosc2_create_cctx", "blosc2_create_dctx", "blosc2_free_ctx", "blosc2_compress_ctx",
     "blosc2_decompress_ctx", "blosc2_cbuffer_sizes", "blosc2_schunk_new", "blosc2_schunk_free",
     "blosc2_schunk_append_chunk", "register_filters", "print_error", "blosc2_getitem_ctx",
+    "blosc2_chunk_zeros", "blosc2_chunk_nans", "blosc2_chunk_repeatval", "blosc2_chunk_uninit",
 )
 
 
@@ -203,6 +204,10 @@ def load():
     L.cimg_engine_wait_stream.argtypes = [vp, vp]
     L.cimg_device_range_check.argtypes = [vp, vp, C.c_size_t]
     L.blosc2_getitem_ctx.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_int, vp, C.c_int32]
+    if hasattr(L, "blosc2_chunk_repeatval"):                # (a CIMG_LIB build from before them: a benchmark against an older library)
+        for name in ("blosc2_chunk_zeros", "blosc2_chunk_nans", "blosc2_chunk_uninit"):      # host-only writers of special chunks
+            getattr(L, name).argtypes = [Blosc2CParams, C.c_int32, vp, C.c_int32]
+        L.blosc2_chunk_repeatval.argtypes = [Blosc2CParams, C.c_int32, vp, C.c_int32, vp]
     L.print_error.restype = C.c_char_p
     _lib = L
     return L

@@ -1,6 +1,7 @@
 // blosc2_shim.cpp -- the eleven c-blosc2 entry points the reference binds (include/blosc2.h),
 // implemented on the MI355X engine.  One chunk per call, host pointers in and out, exactly like
 // c-blosc2; the batched calls in cimg_hip.h are what the re-shaped host loops use instead.
+// Beside them: the four special-chunk constructors (blosc2_chunk_zeros & co.), host-only writers that need no engine.
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -11,6 +12,7 @@
 #include "../../include/cimg_hip.h"
 
 #include "blosc2_context.h"
+#include "special_plan.h"
 
 namespace {
 
@@ -33,6 +35,23 @@ cimg_engine* shared_engine()
 }
 
 int32_t rd32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
+
+// a special chunk of `nbytes` bytes for `cparams` (special_plan.h: the rules, the header and the codes)
+int special_chunk(const blosc2_cparams& cparams, int code, int32_t nbytes, const void* value, void* dest, int32_t destsize)
+{
+    if (!dest) return BLOSC2_ERROR_NULL_POINTER;
+    if (cparams.use_dict != 0 || cparams.prefilter != nullptr) return BLOSC2_ERROR_CODEC_SUPPORT;
+    if (nbytes > BLOSC2_MAX_BUFFERSIZE) return BLOSC2_ERROR_MAX_BUFSIZE_EXCEEDED;
+    cimg::HostCParams p;
+    p.typesize = cparams.typesize;
+    p.clevel = cparams.clevel;
+    p.blocksize = cparams.blocksize;
+    p.compcode = cparams.compcode;
+    p.splitmode = cparams.splitmode;
+    memcpy(p.filters, cparams.filters, BLOSC2_MAX_FILTERS);
+    memcpy(p.filters_meta, cparams.filters_meta, BLOSC2_MAX_FILTERS);
+    return cimg::special_chunk_write(p, code, nbytes, value, dest, destsize);
+}
 
 }  // namespace
 
@@ -127,6 +146,28 @@ int blosc2_cbuffer_sizes(const void* cbuffer, int32_t* nbytes, int32_t* cbytes, 
     if (blocksize) *blocksize = bs;
     if (cb < BLOSC_MIN_HEADER_LENGTH || bs <= 0 || (nb > 0 && bs > nb) || c[3] == 0) return BLOSC2_ERROR_INVALID_HEADER;
     return 0;
+}
+
+// ---- special chunks: a header (and, for a repeated value, the value) that stands for nbytes bytes -------
+int blosc2_chunk_zeros(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize)
+{
+    return special_chunk(cparams, cimg::SPECIAL_ZERO, nbytes, nullptr, dest, destsize);
+}
+
+int blosc2_chunk_nans(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize)
+{
+    return special_chunk(cparams, cimg::SPECIAL_NAN, nbytes, nullptr, dest, destsize);
+}
+
+int blosc2_chunk_repeatval(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize, const void* repeatval)
+{
+    if (!repeatval) return BLOSC2_ERROR_NULL_POINTER;
+    return special_chunk(cparams, cimg::SPECIAL_VALUE, nbytes, repeatval, dest, destsize);
+}
+
+int blosc2_chunk_uninit(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize)
+{
+    return special_chunk(cparams, cimg::SPECIAL_UNINIT, nbytes, nullptr, dest, destsize);
 }
 
 // ---- in-memory super-chunk: an append-only list of finished chunks ---------------------------------

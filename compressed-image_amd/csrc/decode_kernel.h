@@ -20,10 +20,11 @@
 // HBM traffic per block: compressed bytes read once, pixels written once (the algorithmic bytes).
 // Blocks with at most one LZ4-coded plane are normally taken by the lean launch in front of this kernel
 // (decode_lean_kernel.h); `done[b] == gen` marks them and this kernel skips them.
-// Memcpyed and special-zero chunks skip LDS.  Written in the wave.h vocabulary; see wave.h for the
+// Memcpyed and special chunks (zero, value, NaN, uninit: special_plan.h) skip LDS.  Written in the wave.h vocabulary; see wave.h for the
 // host-emulation build used by tests/emu.
 #pragma once
 #include "codec_types.h"
+#include "special_plan.h"
 #include "wave.h"
 #include <type_traits>
 
@@ -200,6 +201,63 @@ CIMG_DEV void wave_fill_global(uint8_t* dst, int nbytes, uint32_t byte, int wave
     if (wave == 0) {
         const int done = units << 4;
         FOR_LANES(l) { if (done + l < nbytes) dst[done + l] = (uint8_t)byte; }
+    }
+}
+
+// dst[k] = pat.at((phase + k) % typesize) for k in [0, nbytes): a block of a special-value or NaN chunk (special_plan.h), whose
+// first byte is byte `phase` of an element.  Where the typesize divides 16 the 16-byte pattern is the same at every 16-byte
+// boundary of the destination: it is built once, rotated to the phase of the first boundary, and goes out in aligned 16-byte stores
+// between a byte-wise head and tail.  Any other typesize: dwords aligned on the destination, each put together from the value as it
+// lies in the chunk -- right for every typesize and phase, and in no hurry.
+CIMG_DEV void wave_fill_pattern(uint8_t* dst, int nbytes, const SpecialPattern& pat, int phase, int wave, int nwaves)
+{
+    if (nbytes <= 0) return;
+    const int ts = pat.ts;
+    if ((16 % ts) == 0) {
+        const int mask = ts - 1;                                     // (1, 2, 4, 8, 16)
+        int head = (int)((16 - ((uintptr_t)dst & 15)) & 15);
+        if (head > nbytes) head = nbytes;
+        const int rot = (phase + head) & mask;
+        uint32_t w[4];
+        for (int i = 0; i < 4; i++) {
+            w[i] = 0;
+            for (int k = 0; k < 4; k++) w[i] |= pat.at((rot + 4 * i + k) & mask) << (8 * k);
+        }
+        const u128 q = {w[0], w[1], w[2], w[3]};
+        uint8_t* body = dst + head;
+        const int units = (nbytes - head) >> 4;
+        for (int u0 = wave * 64; u0 < units; u0 += nwaves * 64) {
+            FOR_LANES(l) { if (u0 + l < units) st128a(body + 16 * (u0 + l), q); }
+        }
+        if (wave == 0) {
+            const int done = head + (units << 4);
+            FOR_LANES(l) {
+                if (l < head) dst[l] = (uint8_t)pat.at((phase + l) & mask);
+                if (done + l < nbytes) dst[done + l] = (uint8_t)pat.at((phase + done + l) & mask);
+            }
+        }
+        return;
+    }
+    const int mis = (int)((uintptr_t)dst & 3);
+    const int units = (mis + nbytes + 3) >> 2;
+    for (int u0 = wave * 64; u0 < units; u0 += nwaves * 64) {
+        FOR_LANES(l) {
+            const int u = u0 + l;
+            if (u < units) {
+                const int q0 = 4 * u - mis;
+                if (q0 >= 0 && q0 + 4 <= nbytes) {
+                    int idx = (phase + q0) % ts;
+                    uint32_t v = 0;
+                    for (int i = 0; i < 4; i++) { v |= pat.at(idx) << (8 * i); idx = idx + 1 == ts ? 0 : idx + 1; }
+                    *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                } else {
+                    for (int i = 0; i < 4; i++) {
+                        const int q = q0 + i;
+                        if (q >= 0 && q < nbytes) dst[q] = (uint8_t)pat.at((phase + q) % ts);
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -1215,6 +1273,20 @@ struct DecodeBlock {
 
     CIMG_DEV void fail(int code) { a.status[chunk] = code; }
 
+    // a block of a value or NaN chunk (special_plan.h): the pattern at the block's element phase, straight to the output.
+    // (c, j, ts, bsize and out are set; mode is 3)
+    CIMG_DEV void phase_a_special(int special, int nbytes, int blocksize, int cbytes, int wave)
+    {
+        const int rc = special_check(special, ts, nbytes, cbytes);
+        if (rc < 0) { fail(rc); return; }
+        mode = 2;
+        const SpecialPattern pat{special == SPECIAL_VALUE ? c + HEADER_LEN : nullptr, ts};
+        const int left = special_covered(nbytes, ts) - j * blocksize;            // (j * blocksize < nbytes)
+        wave_fill_pattern(out, left < bsize ? left : bsize, pat, special_phase(j, blocksize, ts), wave, 4);
+    }
+
+    // FILL_SPECIAL = false: the caller has settled special chunks itself (WindowBlock, window_kernel.h) and none arrives here
+    template <bool FILL_SPECIAL = true>
     CIMG_DEV void phase_a(int wave)
     {
         mode = 3;
@@ -1237,8 +1309,11 @@ struct DecodeBlock {
         if (cbytes > d.destsize) { fail(ERR_READ_BUFFER); return; }          // the header claims more than the caller's buffer holds: nothing behind the header is read
         if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) { fail(ERR_VERSION_SUPPORT); return; }
         const int special = (int)((b2 >> 28) & 7);
-        if (special == SPECIAL_ZERO) { mode = 2; wave_fill_global(out, bsize, 0, wave, 4); return; }
-        if (special != 0) { fail(ERR_DATA); return; }
+        if (special == SPECIAL_ZERO || special == SPECIAL_UNINIT) { mode = 2; wave_fill_global(out, bsize, 0, wave, 4); return; }   // (uninit: zeros, special_plan.h)
+        if (special != 0) {
+            if constexpr (FILL_SPECIAL) phase_a_special(special, nbytes, blocksize, cbytes, wave); else fail(ERR_DATA);
+            return;
+        }
         if (flags & FLAG_MEMCPYED) {
             if (cbytes != nbytes + HEADER_LEN) { fail(ERR_DATA); return; }
             mode = 1;

@@ -413,8 +413,8 @@ struct WideDecodeBlock : DecodeBlock {
         if (cbytes > d.destsize) { fail(ERR_READ_BUFFER); return; }
         if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) { fail(ERR_VERSION_SUPPORT); return; }
         const int special = (int)((b2 >> 28) & 7);
-        if (special == SPECIAL_ZERO) { mode = 2; wave_fill_global(out, bsize, 0, wave, 4); return; }
-        if (special != 0) { fail(ERR_DATA); return; }
+        if (special == SPECIAL_ZERO || special == SPECIAL_UNINIT) { mode = 2; wave_fill_global(out, bsize, 0, wave, 4); return; }
+        if (special != 0) { phase_a_special(special, nbytes, blocksize, cbytes, wave); return; }
         if (flags & FLAG_MEMCPYED) {
             if (cbytes != nbytes + HEADER_LEN) { fail(ERR_DATA); return; }
             mode = 1;

@@ -2,8 +2,9 @@
 // (window_plan.h builds the work items).  One 256-thread workgroup per item (window, batch-wide block): the block is staged
 // by DecodeBlock::phase_a (decode_kernel.h) exactly as cimg_decode_blocks stages it, and phase_w then writes, for every
 // window row that meets the block, the row's bytes inside the block -- unfiltered straight out of LDS -- to
-// out + out_off + r * out_pitch + (column * typesize).  Nothing outside the window is written.  Memcpyed and special-zero
-// chunks are cut from the chunk (or from nothing) without staging; items of chunks that were decoded whole beforehand
+// out + out_off + r * out_pitch + (column * typesize).  Nothing outside the window is written.  Memcpyed and special chunks
+// (zero and uninit: zeros; value and NaN: the pattern at the block's phase, special_plan.h) are cut from the chunk (or from
+// nothing) without staging; items of chunks that were decoded whole beforehand
 // (zstd, blocks beyond LDS: the batch path into engine scratch) are cut from that copy (`b < 0`).
 // cimg_decode_window_strided (below) stages the same way and writes only every col_pitch-th element of each window row.
 // cimg_decode_window_grouped (at the end) runs one workgroup per distinct block and writes every window that meets it.
@@ -39,10 +40,11 @@ struct WindowBlock {
     uint8_t* lds;
     WindowItem it;
     DecodeBlock blk;
-    int mode = 3;          // 0 staged in LDS, 1 memcpyed chunk, 2 zeros, 3 nothing to write, 4 copy mode
+    int mode = 3;          // 0 staged in LDS, 1 memcpyed chunk, 2 zeros, 3 nothing to write, 4 copy mode, 5 pattern (value / NaN chunk)
     int64_t blen = 0;      // bytes of the block (chunk) the item covers
-    const uint8_t* src = nullptr;   // memcpyed / copy mode: the block's first byte
+    const uint8_t* src = nullptr;   // memcpyed / copy mode: the block's first byte; pattern: the chunk's value (null: the NaN)
     int lg = -1;           // log2(typesize) when it is a power of two
+    int pts = 1, phase = 0;         // pattern: the typesize, and the element phase of the block's first byte
 
     CIMG_DEV static WindowItem uniform_item(const WindowItem* p)
     {
@@ -85,15 +87,24 @@ struct WindowBlock {
         if (cbytes > d.destsize) { fail(ERR_READ_BUFFER); return; }
         if ((flags & (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) != (FLAG_SHUFFLE | FLAG_BITSHUFFLE)) { fail(ERR_VERSION_SUPPORT); return; }
         const int special = (int)((b2 >> 28) & 7);
-        if (special == SPECIAL_ZERO) { mode = 2; return; }
-        if (special != 0) { fail(ERR_DATA); return; }
+        if (special == SPECIAL_ZERO || special == SPECIAL_UNINIT) { mode = 2; return; }
+        if (special != 0) {
+            const int rc = special_check(special, ts, nbytes, cbytes);
+            if (rc < 0) { fail(rc); return; }
+            mode = 5;
+            src = special == SPECIAL_VALUE ? c + HEADER_LEN : nullptr;
+            pts = ts;
+            phase = special_phase(j, blocksize, ts);
+            if ((ts & (ts - 1)) == 0) lg = __builtin_ctz((unsigned)ts);
+            return;
+        }
         if (flags & FLAG_MEMCPYED) {
             if (cbytes != nbytes + HEADER_LEN) { fail(ERR_DATA); return; }
             mode = 1;
             src = c + HEADER_LEN + (int64_t)j * blocksize;
             return;
         }
-        blk.phase_a(wave);
+        blk.phase_a<false>(wave);
         mode = blk.mode == 0 ? 0 : 3;
         if (mode == 0 && (blk.ts & (blk.ts - 1)) == 0) lg = __builtin_ctz((unsigned)blk.ts);
     }
@@ -121,6 +132,10 @@ struct WindowBlock {
     {
         if (mode == 0) return staged((int)k);
         if (mode == 2) return 0;
+        if (mode == 5) {
+            const int idx = lg >= 0 ? (phase + (int)k) & (pts - 1) : (phase + (int)k) % pts;
+            return (uint8_t)SpecialPattern{src, pts}.at(idx);
+        }
         return src[k];
     }
 

@@ -457,7 +457,7 @@ inline int open_window_call(int nchunks, int nwindows, int32_t* status)
 // What both host calls plan.  Per-chunk arrays cover the whole batch; a chunk no window names keeps the defaults and is never
 // dereferenced, a chunk no window row meets is not staged (up 0).
 struct HostCallPlan {
-    std::vector<uint8_t> named, flags, version;                 // named: some window's [chunk_first, +chunk_count) holds the chunk
+    std::vector<uint8_t> named, flags, version, special;        // named: some window's [chunk_first, +chunk_count) holds the chunk; special: the header's special field
     std::vector<int32_t> nbytes, blocksize, cbytes, typesize;   // from the named chunks' headers
     int bad_window = -1;                // ERR_INVALID_PARAM: this window's chunks leave the batch
     int short_chunk = -1;               // ERR_READ_BUFFER: this named chunk's buffer cannot hold a header
@@ -478,7 +478,7 @@ inline int read_named_headers(int nchunks, const uint8_t* comp, const int64_t* c
                               const Spec* w, HostCallPlan* hp)
 {
     const size_t n = (size_t)nchunks;
-    hp->named.assign(n, 0); hp->flags.assign(n, 0); hp->version.assign(n, 0);
+    hp->named.assign(n, 0); hp->flags.assign(n, 0); hp->version.assign(n, 0); hp->special.assign(n, 0);
     hp->nbytes.assign(n, 0); hp->blocksize.assign(n, 1); hp->cbytes.assign(n, 0); hp->typesize.assign(n, 0);
     hp->d_comp_off.assign(n, 0); hp->up.assign(n, 0);
     for (int k = 0; k < nwindows; k++) {
@@ -493,6 +493,7 @@ inline int read_named_headers(int nchunks, const uint8_t* comp, const int64_t* c
         hp->typesize[(size_t)i] = c[OFF_TYPESIZE];
         hp->flags[(size_t)i] = c[OFF_FLAGS];
         hp->version[(size_t)i] = c[0];
+        hp->special[(size_t)i] = (c[OFF_BLOSC2_FLAGS] >> 4) & 7;
     }
     return 0;
 }
@@ -540,7 +541,8 @@ inline int plan_windows_host(int nchunks, const uint8_t* comp, const int64_t* co
     int rc = read_named_headers(nchunks, comp, comp_off, comp_size, nwindows, w, hp);
     if (rc < 0) return rc;
     hp->hint.assign((size_t)nchunks, 0);
-    for (int i = 0; i < nchunks; i++) hp->hint[(size_t)i] = (hp->flags[(size_t)i] >> 5) == 4 && !(hp->flags[(size_t)i] & FLAG_MEMCPYED);
+    // (the special field is decided before the memcpyed flag and the codec format, here as in the kernels: special_plan.h)
+    for (int i = 0; i < nchunks; i++) hp->hint[(size_t)i] = (hp->flags[(size_t)i] >> 5) == 4 && !(hp->flags[(size_t)i] & FLAG_MEMCPYED) && hp->special[(size_t)i] == 0;
     typename PlanOf<Spec>::type plan;
     if ((rc = plan_windows(nchunks, hp->nbytes.data(), hp->blocksize.data(), hp->typesize.data(), nwindows, w, hp->hint.data(), &plan)) < 0) return rc;
     for (int i = 0; i < nchunks; i++) {

@@ -210,6 +210,52 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			out.m_Count = n;
 			return out;
 		}
+		/// A channel whose every element is `value`, at 64 bytes of device memory a chunk: the store is built on the host from blosc2
+		/// special-value chunks -- a header and the value; special-zero chunks where the value is all zero bytes -- and uploaded once.
+		/// Nothing is launched and no pixel buffer exists anywhere.  Everything a device_channel does works on it; set_region makes the
+		/// chunks it touches regular and leaves the others as they are.  mantissa_bits: the value is stored truncated.
+		static device_channel full(T value, size_t width, size_t height, enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9,
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
+		{
+			blosc2::ensure_mantissa_bits<T>(mantissa_bits);
+			if (width == 0 || height == 0) throw std::invalid_argument("device_channel::full: width and height must be at least 1");
+			const size_t chunk_bytes = util::align_chunk_to_scanlines_bytes<T>(width, chunk_size);
+			util::validate_chunk_size<T>(chunk_bytes, "device_channel");
+			device_channel out(compression_codec, util::ensure_compression_level(compression_level), block_size, chunk_bytes, width, height, mantissa_bits);
+			const blosc2_cparams p = blosc2::create_blosc2_cparams<T>(1, compression_codec, out.m_CompressionLevel, block_size, mantissa_bits);
+			unsigned char raw[sizeof(T)];
+			std::memcpy(raw, &value, sizeof(T));
+			const bool zero = std::all_of(raw, raw + sizeof(T), [](unsigned char b) { return b == 0; });
+			const size_t total = width * height * sizeof(T);
+			std::vector<std::vector<std::byte>> chunks;
+			for (size_t off = 0; off < total; off += chunk_bytes)
+			{
+				const int32_t nbytes = static_cast<int32_t>(std::min(chunk_bytes, total - off));
+				std::vector<std::byte> c(BLOSC_EXTENDED_HEADER_LENGTH + sizeof(T));
+				const int rc = zero ? blosc2_chunk_zeros(p, nbytes, c.data(), static_cast<int32_t>(c.size()))
+					: blosc2_chunk_repeatval(p, nbytes, c.data(), static_cast<int32_t>(c.size()), raw);
+				if (rc < 0) throw std::runtime_error(detail::text("Unable to write the fill chunk ", chunks.size(), ", error code ", rc));
+				c.resize(static_cast<size_t>(rc));
+				chunks.push_back(std::move(c));
+			}
+			out.m_Count = chunks.size();
+			out.m_Store = detail::upload_store(chunks);
+			out.m_First = 0;
+			return out;
+		}
+		static device_channel zeros(size_t width, size_t height, enums::codec compression_codec = enums::codec::lz4, uint8_t compression_level = 9,
+			size_t block_size = s_default_blocksize, size_t chunk_size = s_default_chunksize, std::optional<int> mantissa_bits = std::nullopt)
+		{
+			return full(T{}, width, height, compression_codec, compression_level, block_size, chunk_size, mantissa_bits);
+		}
+		/// full / zeros with the geometry and the codec parameters of `other`
+		static device_channel full_like(const device_channel& other, T value)
+		{
+			return full(value, other.width(), other.height(), other.compression(), other.compression_level(), other.block_size(), other.chunk_size(),
+				other.mantissa_bits());
+		}
+		static device_channel zeros_like(const device_channel& other) { return full_like(other, T{}); }
+
 		/// The same chunks back in host memory, as a channel<T>.
 		channel<T> to_channel() const
 		{

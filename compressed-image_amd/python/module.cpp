@@ -618,6 +618,21 @@ namespace
 			});
 		}
 		std::optional<int> mantissa_bits() const { return visit([](auto& c) { return c.mantissa_bits(); }); }
+		// blank channels: special-value chunks written on the host, 64 bytes of device memory a chunk (device_channel.h: full)
+		static DeviceChannel full(const py::object& dtype, const py::object& fill, size_t width, size_t height, codec c, size_t level, size_t block, size_t chunk,
+			std::optional<int> mantissa)
+		{
+			return dispatch(as_dtype(dtype), [&]<typename T>() {
+				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(compressed::device_channel<T>::full(from_scalar<T>(fill), width, height, c,
+					static_cast<uint8_t>(std::min<size_t>(level, 255)), block, chunk, mantissa)) };
+			});
+		}
+		static DeviceChannel full_like(const DeviceChannel& other, const py::object& fill)
+		{
+			return other.visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				return DeviceChannel{ std::make_shared<compressed::device_channel<T>>(compressed::device_channel<T>::full_like(ch, from_scalar<T>(fill))) };
+			});
+		}
 		static DeviceChannel from_channel(const Channel& host)
 		{
 			return host.visit([]<typename T>(compressed::channel<T>& ch) {
@@ -934,6 +949,15 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("mantissa_bits") = std::nullopt)
 		.def("mantissa_bits", &DeviceChannel::mantissa_bits)
 		.def_static("from_channel", &DeviceChannel::from_channel, py::arg("channel"))
+		.def_static("full", &DeviceChannel::full, py::arg("dtype"), py::arg("fill_value"), py::arg("width"), py::arg("height"),
+			py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9, py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk,
+			py::arg("mantissa_bits") = std::nullopt)
+		.def_static("zeros", [](const py::object& dtype, size_t w, size_t h, codec c, size_t level, size_t block, size_t chunk, std::optional<int> mantissa) {
+				return DeviceChannel::full(dtype, py::int_(0), w, h, c, level, block, chunk, mantissa); },
+			py::arg("dtype"), py::arg("width"), py::arg("height"), py::arg("compression_codec") = codec::lz4, py::arg("compression_level") = 9,
+			py::arg("block_size") = d_block, py::arg("chunk_size") = d_chunk, py::arg("mantissa_bits") = std::nullopt)
+		.def_static("full_like", &DeviceChannel::full_like, py::arg("other"), py::arg("fill_value"))
+		.def_static("zeros_like", [](const DeviceChannel& other) { return DeviceChannel::full_like(other, py::int_(0)); }, py::arg("other"))
 		.def("to_channel", &DeviceChannel::to_channel)
 		.def_property_readonly("dtype", [](const DeviceChannel& c) { return c.visit([]<typename T>(compressed::device_channel<T>&) { return np_dtype<T>(); }); })
 		.def_property_readonly("shape", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return py::make_tuple(ch.height(), ch.width()); }); })

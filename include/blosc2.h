@@ -20,6 +20,8 @@
  *   wrapper.h:286, schunk.h:113              blosc2_schunk_append_chunk
  *   wrapper.h:34                             register_filters
  *   blosc2/util.h:18                         print_error
+ * Beyond what the reference binds: blosc2_getitem_ctx, and the four special-chunk constructors blosc2_chunk_zeros / _nans /
+ * _repeatval / _uninit (the device-resident classes build blank channels from them).
  */
 #ifndef CIMG_BLOSC2_SHIM_H
 #define CIMG_BLOSC2_SHIM_H
@@ -132,6 +134,16 @@ int blosc2_cbuffer_sizes(const void* cbuffer, int32_t* nbytes, int32_t* cbytes, 
  * (dest too small), BLOSC2_ERROR_READ_BUFFER (srcsize below the header's cbytes), BLOSC2_ERROR_NULL_POINTER, or the context checks
  * of blosc2_decompress_ctx. */
 int blosc2_getitem_ctx(blosc2_context* context, const void* src, int32_t srcsize, int start, int nitems, void* dest, int32_t destsize);
+
+/* Special chunks (c-blosc2's constructors, its signatures): a 32-byte header that stands for `nbytes` bytes of zeros, of quiet NaNs
+ * (typesize 4 or 8), of one repeated value (the header and the cparams.typesize bytes at `repeatval`: 32 + typesize bytes) or of
+ * unspecified values (this library reads those as zeros).  Host-only writers: no engine, no GPU.  With trunc-prec in the cparams
+ * the stored value is the truncated one.  Return the chunk's size, or BLOSC2_ERROR_DATA when dest cannot hold it or nbytes is no
+ * multiple of the typesize (a NaN chunk: or the typesize is neither 4 nor 8), or the code blosc2_compress_ctx gives for the cparams. */
+int blosc2_chunk_zeros(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize);
+int blosc2_chunk_nans(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize);
+int blosc2_chunk_repeatval(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize, const void* repeatval);
+int blosc2_chunk_uninit(blosc2_cparams cparams, int32_t nbytes, void* dest, int32_t destsize);
 
 blosc2_schunk* blosc2_schunk_new(blosc2_storage* storage);
 int blosc2_schunk_free(blosc2_schunk* schunk);

@@ -252,7 +252,7 @@ int cimg_decompress_windows_grouped_host(cimg_engine* e, int32_t nchunks, const 
  * bytes equal what cimg_compress_batch_* with `p` and destsize[i] produces from the chunk's decoded pixels with the windows
  * written in (for lz4 and blosclz: blosc2_compress_ctx's bytes).  Only the blocks a window row meets are decoded and re-encoded;
  * the other blocks' streams are copied from the old chunk.  zstd chunks, blocks beyond the normal kernels' LDS, memcpyed and
- * special-zero chunks are decoded, patched and compressed whole on the device.  The input chunks are never modified.
+ * special chunks (zero, NaN, repeated value, uninitialised) are decoded, patched and compressed whole on the device.  The input chunks are never modified.
  * Nothing runs, and the call returns BLOSC2_ERROR_INVALID_PARAM, unless every window passes the checks of the window reads, every
  * touched chunk's header agrees with `p` (typesize, codec, filters -- trunc-prec and its meta included: written pixels are truncated
  * like the chunk's own --, split decision, effective blocksize for its nbytes) and every

@@ -1,0 +1,37 @@
+"""compressed::device_channel<T>::full / zeros / full_like / zeros_like through C++ (compressed/device_channel.h), and a blank
+channel's special chunks inside a device_image<T>: tests/cpp/special_channel_test.cpp compiled against the emulator-backed mock of
+the C ABI -- with tests/emu/mock_device.cpp, mock_window_grouped.cpp and mock_window_write.cpp beside it -- and, on the GPU, against
+libcimg_hip.so."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "special_channel_test.cpp")
+EMU = os.path.join(ROOT, "tests", "emu")
+FLAGS = ["g++", "-std=c++20", "-O1", "-g", "-Wall", "-Wextra", "-fno-strict-aliasing", "-I", os.path.join(ROOT, "include"),
+         "-I", os.path.join(ROOT, "compressed-image_amd", "include")]
+
+
+def _run(exe):
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+    assert "0 failures" in res.stdout
+
+
+def test_blank_channels_on_emulator(tmp_path):
+    subprocess.check_call(["make", "-s", "-C", EMU])
+    exe = str(tmp_path / "special_channel_test_mock")
+    mocks = [os.path.join(EMU, f) for f in ("mock_device.cpp", "mock_window_grouped.cpp", "mock_window_write.cpp")]
+    subprocess.check_call(FLAGS + ["-I", os.path.join(ROOT, "compressed-image_amd", "csrc"), SRC, *mocks, "-o", exe,
+                                   "-L", EMU, "-lcimg_hip_mock", "-Wl,-rpath," + EMU, "-pthread"])
+    _run(exe)
+
+
+@pytest.mark.gpu
+def test_blank_channels_on_gpu(tmp_path):
+    libdir = os.path.join(ROOT, "compressed-image_amd")
+    exe = str(tmp_path / "special_channel_test_gpu")
+    subprocess.check_call(FLAGS + [SRC, "-o", exe, "-L", libdir, "-lcimg_hip", "-Wl,-rpath," + libdir, "-pthread"])
+    _run(exe)
