@@ -20,6 +20,9 @@ namespace cimg {
 #ifdef CIMG_EMULATE
 // test-side statistics only: streams the encoder left as REC_RAW_SRC, streams placed from the source
 inline long g_emu_src_left = 0, g_emu_src_placed = 0;
+// ... and of the streams placed from the source: by the wave that encoded them, by another wave (a helper), and those their owner
+// skipped because the block's mark said a helper had placed them
+inline long g_emu_src_by_owner = 0, g_emu_src_by_helper = 0, g_emu_src_owner_skipped = 0;
 #define CIMG_EMU_COUNT(x) (++(x))
 #else
 #define CIMG_EMU_COUNT(x) ((void)0)
@@ -280,6 +283,19 @@ CIMG_DEV void wave_plane_from_source(const uint8_t* src, int bsize, int ts, int 
 struct EmitBlock {
     const AssembleArgs& a;
     int b;
+    // inside the encode launch, where idle waves help to place stored planes (encode_kernel.h: encode_emit_own): block b's REC_RAW_SRC
+    // streams are in place in this launch when placed[b] == gen.  Placing such a stream is idempotent -- the same bytes from the
+    // launch's read-only input to the same address, whoever does it -- so the mark is read and written with plain agent-scope loads
+    // and stores and never claimed: the worst a stale mark causes is a plane written twice.  ("In place": placed, or taken by a
+    // helper that is placing it -- all an owner needs to know is that it need not.)
+    // With plane items the stored planes of one block have different owners: an owner also marks its own plane, in a word per
+    // stream (placed_streams[b * streams_per_block + s]), and sets the block's mark when it sees every other stored plane of the
+    // block marked so.  (Two owners that finish together may both see the other's word unset: the block then stays open, and a
+    // helper places it again.)
+    uint32_t* placed = nullptr;
+    uint32_t* placed_streams = nullptr;
+    uint32_t gen = 0;
+    bool src_skipped = false, src_placed = false;   // what copy() did with the block's stored planes (diagnostics: tools/diag_assemble.py)
     CIMG_DEV EmitBlock(const AssembleArgs& a_, int b_) : a(a_), b(b_) {}
 
     // the stand-alone kernel: `wave` of `nwaves` cooperating waves copy the whole block
@@ -288,9 +304,10 @@ struct EmitBlock {
     // closer's layout word and bstarts[j], the records of the block's other streams -- is read with agent-scope loads straight from
     // memory (the writers wrote it through / wrote it back); the payload is this wave's own and comes out of its own L2.  No
     // acquire fence: an L2 invalidate per wave and chunk, a thousand waves at once, cost the launch more than the copies.
-    CIMG_DEV void run_streams(int s_begin, int s_end) { copy(0, 1, s_begin, s_end, true); }
+    // only_src: the caller is a helper, not the owner -- it places the block's REC_RAW_SRC streams and nothing else.
+    CIMG_DEV void run_streams(int s_begin, int s_end, bool only_src = false) { copy(0, 1, s_begin, s_end, true, only_src); }
     // (A REC_RAW_SRC stream has nothing in the scratch slot: its bytes are selected from the launch's input, which nobody writes.)
-    CIMG_DEV void copy(int wave, int nwaves, int s_begin, int s_end, bool coherent = false)
+    CIMG_DEV void copy(int wave, int nwaves, int s_begin, int s_end, bool coherent = false, bool only_src = false)
     {
         const int chunk = find_chunk(a.descs, a.nchunks, b, a.uniform_nblocks);
         const ChunkDesc d = uniform_desc(a.descs + chunk);
@@ -303,7 +320,7 @@ struct EmitBlock {
         const StreamRec* rp = a.recs + (int64_t)b * a.p.streams_per_block;
         // What other waves wrote: the layout word, bstarts[j], {kind, value, csize} of the block's streams.  Coherent form: ONE
         // round trip of agent-scope loads, lane 0 the mode, lane 1 bstarts[j], lanes 2 + 3 s .. 4 + 3 s the record of stream s
-        // (MAX_STREAMS = 16 streams: 50 lanes).  (bstarts[] is 4-byte aligned whenever the chunk is; a caller-chosen odd chunk
+        // (MAX_STREAMS = 16 streams: 50 lanes), lane 50 the block's mark, lanes 51 + s the mark of stream s < 13.  (bstarts[] is 4-byte aligned whenever the chunk is; a caller-chosen odd chunk
         // address takes a fence instead.)
         const bool aligned = ((uintptr_t)(c + HEADER_LEN) & 3) == 0;
         LV<int32_t> meta;
@@ -312,6 +329,8 @@ struct EmitBlock {
             FOR_LANES(l) {
                 const int k = l - 2, sidx = k >= 0 ? k / 3 : 0, f = k >= 0 ? k - 3 * sidx : 0;
                 const uint32_t* p = l == 0 ? reinterpret_cast<const uint32_t*>(&a.layout[chunk].mode)
+                                  : (l == 50 && placed) ? placed + b
+                                  : (l > 50 && placed_streams && l - 51 < ns) ? placed_streams + (int64_t)b * a.p.streams_per_block + (l - 51)
                                   : l == 1 ? reinterpret_cast<const uint32_t*>(c + HEADER_LEN + (aligned ? 4 * j : 0))
                                            : reinterpret_cast<const uint32_t*>(rp + (sidx < ns ? sidx : 0)) + f;
                 meta[l] = (l == 1 && !aligned) ? ld32s(c + HEADER_LEN + 4 * j) : (int32_t)atomic_load_agent(p);
@@ -324,6 +343,7 @@ struct EmitBlock {
             }
         }
         const int mode = readlane(meta, 0);
+        if (only_src && mode != 0) return;                            // (a helper keeps out of memcpyed, special and failed chunks)
         if (mode == 1) {
             // memcpyed chunk: the raw pixels of the block; a caller that owns streams [s_begin, s_end) of ns copies that share of them
             const int lo = s_begin <= 0 ? 0 : (int)((int64_t)bsize * s_begin / ns) & ~15;
@@ -333,13 +353,23 @@ struct EmitBlock {
             return;
         }
         if (mode != 0) return;
+        // the mark (in-launch placing only): set, the block's REC_RAW_SRC streams are in place or being placed by a helper -- their
+        // owner skips them, csize word and plane; a helper finds nothing left to do.  Whoever places ALL of them sets it afterwards
+        // (a plane item's owner only when the block's other planes are not REC_RAW_SRC: those have owners of their own).
+        const bool marked = coherent && placed && (uint32_t)readlane(meta, 50) == gen;
+        if (only_src && marked) return;
+        // A helper marks the block BEFORE it places it: from here on it places every stored plane of the block without fail, and the
+        // sooner the others see the mark, the fewer take the same block.  (An owner that skips on this mark reads nothing of the
+        // block; the launch does not end before the helper has placed it.)
+        if (only_src && coherent && placed) { FOR_LANES_W(l) { if (l == 0) atomic_store_agent(placed + b, gen); } }
         const int neblock = bsize / ns;
         const uint8_t* slot = a.scratch + (int64_t)b * a.p.slot_bytes;
         int pos = readlane(meta, 1);
         for (int s = 0; s < ns && s < s_end && s < MAX_STREAMS; s++) {
             StreamRec r;
             r.kind = readlane(meta, 2 + 3 * s); r.value = readlane(meta, 3 + 3 * s); r.csize = readlane(meta, 4 + 3 * s); r.need = 0;
-            const bool mine = s >= s_begin;
+            const bool mine = s >= s_begin && (r.kind == REC_RAW_SRC ? !marked : !only_src);
+            if (r.kind == REC_RAW_SRC && marked && s >= s_begin) { src_skipped = true; CIMG_EMU_COUNT(g_emu_src_owner_skipped); }
             if (wave == 0 && mine) {
                 const int word = r.kind == REC_RUN ? -r.value : r.csize;
                 FOR_LANES(l) {
@@ -352,11 +382,25 @@ struct EmitBlock {
                 // (the stand-alone kernel never meets one: the kind exists only in chunks assembled inside the encode launch, by one wave)
                 if (mine) {
                     CIMG_EMU_COUNT(g_emu_src_placed);
+                    src_placed = true;
+                    if (only_src) CIMG_EMU_COUNT(g_emu_src_by_helper); else CIMG_EMU_COUNT(g_emu_src_by_owner);
                     wave_plane_from_source(a.raw + d.raw_off + (int64_t)j * d.blocksize, bsize, a.p.typesize, s, neblock, a.p.filter == FILTER_SHUFFLE, c + pos);
                 }
             }
             else if (r.kind != REC_RUN && mine) { if (nwaves == 1) wave_copy_g2g<16>(slot + (int64_t)s * neblock, c + pos, r.csize, 0, 1); else wave_copy_g2g(slot + (int64_t)s * neblock, c + pos, r.csize, wave, nwaves); }
             pos += rec_payload(r);
+        }
+        if (coherent && placed && !marked && !only_src) {
+            // every stored plane of the block in place?  An owner counts its own and those whose owners marked them.  (More streams than the 13 whose marks were read: the block is left to a helper.)
+            bool all = true;
+            const bool part = s_begin > 0 || s_end < ns;
+            for (int s = 0; s < ns && s < MAX_STREAMS; s++) {
+                if (readlane(meta, 2 + 3 * s) != REC_RAW_SRC) continue;
+                const bool own = s >= s_begin && s < s_end;
+                if (own && part && placed_streams) { FOR_LANES_W(l) { if (l == 0) atomic_store_agent(placed_streams + (int64_t)b * a.p.streams_per_block + s, gen); } }
+                if (!own && !(placed_streams && s < 13 && (uint32_t)readlane(meta, 51 + s) == gen)) all = false;
+            }
+            if (all) { FOR_LANES_W(l) { if (l == 0) atomic_store_agent(placed + b, gen); } }
         }
     }
 };

@@ -82,6 +82,14 @@ struct EncodeArgs {
     uint32_t* ready;          // per chunk: == gen once the chunk is laid out
     int32_t* next_item;       // per item of this launch: the item the same wave encoded before it (-1: none)
     uint32_t gen;
+    // ---- idle waves place stored planes of busy waves (round 7; encode_emit_own) ---------------------------------------------
+    // placed[b] == gen: the REC_RAW_SRC streams of block b are in place in this launch (`total_blocks` words); behind them one word
+    // per chunk, placed[total_blocks + c] == gen: some wave has seen every block of chunk c marked (a hint that spares the next
+    // helper the look); behind those one word per stream, placed[total_blocks + nchunks + b * streams_per_block + s] == gen: its
+    // owner has placed stored plane s of block b (plane items: EmitBlock::placed_streams).  Plain agent-scope loads and stores,
+    // never a read-modify-write.  Zeroed when allocated, like ready[].
+    uint32_t* placed = nullptr;
+    int32_t helpers = 0;      // 0: every wave places its own streams and nothing else; n > 0: marks are kept, and every n-th wave helps
 };
 
 // ---- the work queue (round 4) -------------------------------------------------------------------------------------------------
@@ -1094,69 +1102,190 @@ CIMG_DEV_OUTLINE int encode_account(kernarg_ptr<EncodeArgs> ap_in, int item_in, 
 // from the scratch slots, stored planes of split blocks from the source (REC_RAW_SRC).  A chunk that is not laid out yet is waited for
 // (s_sleep + one atomic load per try; every chain that still encodes keeps its own SIMD slot, so waiting waves hold nobody up) --
 // with a hard bound, after which the batch FAILS.
-CIMG_DEV_OUTLINE void encode_emit_own(kernarg_ptr<EncodeArgs> ap_in, int last_in)
+//
+// HELPING (round 7; EncodeArgs::helpers).  A wave with nothing of its own left to place in a ready chunk looks for blocks whose stored
+// planes are not marked as placed (EncodeArgs::placed) and places them, whoever encoded them: the planes are byte-selects of the
+// launch's read-only input, so any wave on any XCD writes the same bytes, and nothing is claimed (EmitBlock::placed) -- a stale mark
+// costs a plane written twice.  An owner that finds its block marked skips those planes.  A helper looks at a window of up to 64
+// chunks that starts at a chunk of its own (wave w: chunk w mod nchunks) and, inside a chunk, takes the first unmarked block at or
+// behind a rotation of its own, marks it and places it: ONE block per look at the marks, so that waves rarely take the same block.
+// It keeps out of chunks that are not assembled in the launch, that start off a 4-byte boundary (the fence path) and -- once they
+// are laid out -- of memcpyed, special and failed chunks.  It is done when every chunk of its window that it may help is laid out and
+// has no unmarked block left; like an owner it waits for nothing but ready[].
+CIMG_DEV_OUTLINE void encode_emit_own(kernarg_ptr<EncodeArgs> ap_in, int last_in, int w_in)
 {
     const kernarg_ptr<EncodeArgs> ap = CIMG_OWN_KERNARGS(EncodeArgs, ap_in);
-    const int last = uni(last_in);
-    const AssembleArgs aa = assemble_args(ap);
+    const int last = uni(last_in), w = uni(w_in);
+    const ChunkDesc* descs;
     uint32_t* ready;
+    uint32_t* placed;
+    const ChunkLayout* layout;
     int32_t* next_item;
     uint32_t gen;
-    int items, want_split, ts_arg;
+    int items, want_split, ts_arg, nchunks, unb, total_blocks;
+    bool helping, marks;
+    uintptr_t comp;
     {
         const auto a = fresh(ap);
+        descs = a->descs; nchunks = a->nchunks; unb = a->uniform_nblocks; total_blocks = a->total_blocks; layout = a->layout;
         ready = a->ready; next_item = a->next_item; gen = a->gen; want_split = a->want_split; ts_arg = a->p.typesize;
         items = encode_items(a->total_blocks, a->p.streams_per_block, a->want_split != 0, a->block_items);
+        placed = a->placed; comp = (uintptr_t)a->comp;
+        marks = a->helpers && a->placed;
+        helping = a->helpers > 0 && w % a->helpers == 0 && a->placed && a->want_split && nchunks > 0 && plane_from_source_ok(a->p.typesize, a->p.filter);
     }
     // Pass after pass over the wave's own items: an item whose chunk is laid out is copied into place and marked; the others are
     // looked at again in the next pass (a nap in between).  Most of a wave's items belong to chunks that were finished long
     // before it ran out of work; only the chunks that close at the very end of the launch are waited for.
     enum : int { PASS_LIMIT = 1 << 20, ITEM_DONE = 1 << 30 };   // x (s_sleep + the polls of a pass) is seconds: only a lost chunk gets there
     int known_ready = -1, known_not = -1;                    // per pass: the chunks last seen ready / not ready (a wave's items share chunks)
-    bool pending = true;
-    for (int pass = 0; pass < PASS_LIMIT && pending; ++pass) {
+    bool pending = last >= 0;
+    uint64_t clean = 0;                                      // helper: the chunks of its window it is done with
+    int helped = 0;                                          // helper: blocks whose stored planes it placed (diagnostics)
+    const int nwin = helping ? imin(nchunks, 64) : 0, c0 = helping ? w % nchunks : 0;
+    const int share = helping ? imax((fresh(ap)->nwaves + nchunks - 1) / nchunks, 1) : 1;   // waves that start at the same chunk
+    const uint64_t window = nwin == 64 ? ~0ull : (1ull << nwin) - 1;
+    for (int pass = 0; pass < PASS_LIMIT && (pending || helping); ++pass) {
+        bool worked = false;
+        const bool walk = pending;
         pending = false;
         known_not = -1;
-        int it = last;
-        for (int n = 0; n <= items && it >= 0; ++n) {        // bounded: a wave cannot own more than every item
-            LV<int32_t> nx;
-            FOR_LANES(l) { nx[l] = next_item[it]; }
-            const int link = uni(readlane(nx, 0));
-            const bool marked = link >= 0 && (link & ITEM_DONE) != 0;                   // (the end of the list, -1, is not a mark: marks are non-negative)
-            const int next = marked ? (link & ~ITEM_DONE) - 1 : link;                   // a marked link holds (next + 1) | ITEM_DONE
-            if (!marked) {
-                int b, s;
-                encode_item_place(fresh(ap), it, b, s);
-                const int chunk = find_chunk(aa.descs, aa.nchunks, b, aa.uniform_nblocks);
-                bool is_ready = chunk == known_ready;
-                if (!is_ready && chunk != known_not) {
-                    LV<uint32_t> got;
-                    FOR_LANES(l) { got[l] = 0; }
-                    FOR_LANES_W(l) { if (l == 0) got[l] = atomic_load_agent(ready + chunk); }
-                    is_ready = uni(readlane(got, 0)) == gen;
-                    if (is_ready) known_ready = chunk;               // (what the closer and other waves wrote is read past the L2: EmitBlock::run_streams)
-                    else known_not = chunk;
+        int it = walk ? last : -1, walked = 0;
+        bool looked = false;                                 // helper: the window was looked at in this pass
+        uint64_t todo = 0;
+        // One block is placed per step, by ONE copy of the placing code (EmitBlock) for owner and helper alike: the step first
+        // moves on through the wave's own items to the next one whose chunk is laid out; with none left, through the helper's
+        // window to the next chunk with an unmarked block.
+        for (int step = 0; step <= items + 64; ++step) {     // bounded: every own item, every chunk of the window
+            int job_b = -1, job_s0 = 0, job_s1 = 0, job_item = -1, job_next = -1;
+            bool job_src = false, owner_skipped = false;
+            for (; walked <= items && it >= 0 && job_b < 0; ++walked) {        // bounded: a wave cannot own more than every item
+                LV<int32_t> nx;
+                FOR_LANES(l) { nx[l] = next_item[it]; }
+                const int link = uni(readlane(nx, 0));
+                const bool marked = link >= 0 && (link & ITEM_DONE) != 0;                   // (the end of the list, -1, is not a mark: marks are non-negative)
+                const int next = marked ? (link & ~ITEM_DONE) - 1 : link;                   // a marked link holds (next + 1) | ITEM_DONE
+                if (!marked) {
+                    int b, s;
+                    encode_item_place(fresh(ap), it, b, s);
+                    const int chunk = find_chunk(descs, nchunks, b, unb);
+                    bool is_ready = chunk == known_ready;
+                    if (!is_ready && chunk != known_not) {
+                        LV<uint32_t> got;
+                        FOR_LANES(l) { got[l] = 0; }
+                        FOR_LANES_W(l) { if (l == 0) got[l] = atomic_load_agent(ready + chunk); }
+                        is_ready = uni(readlane(got, 0)) == gen;
+                        if (is_ready) known_ready = chunk;               // (what the closer and other waves wrote is read past the L2: EmitBlock::run_streams)
+                        else known_not = chunk;
+                    }
+                    if (is_ready) {
+                        const ChunkDesc d = uniform_desc(descs + chunk);
+                        const int j = b - d.blk0;
+                        const bool leftover_blk = (j == d.nblocks - 1 && d.leftover);
+                        const int ns = (d.split && !leftover_blk) ? ts_arg : 1;
+                        const bool whole = ns > 1 && want_split && it < fresh(ap)->block_items;
+                        const bool all = whole || ns == 1;
+                        job_b = b; job_s0 = all ? 0 : s; job_s1 = all ? ns : s + 1; job_item = it; job_next = next;
+                    } else {
+                        pending = true;
+                    }
                 }
-                if (is_ready) {
-                    const ChunkDesc d = uniform_desc(aa.descs + chunk);
-                    const int j = b - d.blk0;
-                    const bool leftover_blk = (j == d.nblocks - 1 && d.leftover);
-                    const int ns = (d.split && !leftover_blk) ? ts_arg : 1;
-                    const bool whole = ns > 1 && want_split && it < fresh(ap)->block_items;
-                    EmitBlock eb(aa, b);
-                    if (whole || ns == 1) eb.run_streams(0, ns);
-                    else eb.run_streams(s, s + 1);
-                    FOR_LANES_W(l) { if (l == 0) next_item[it] = (next + 1) | ITEM_DONE; }
-                    CIMG_ITEM_STAMP(fresh(ap)->dbg, it, 2);                 // diagnostics: the item's streams are in place
-                } else {
-                    pending = true;
+                it = next;
+            }
+            if (job_b < 0 && helping) {
+                if (!looked) {
+                    // the window in one round trip: which chunks a helper may touch, which are laid out, which somebody saw fully marked
+                    looked = true;
+                    LV<bool> may, isready, isclean;
+                    FOR_LANES(l) {
+                        const int c = (c0 + l) % nchunks;
+                        bool m = false, r = false, k = false;
+                        if (l < nwin) {
+                            const ChunkDesc& d = descs[c];
+                            m = d.assemble && !d.memcpyed && d.split && !d.leftover && ((comp + (uintptr_t)d.comp_off) & 3) == 0;
+                            if (m) { r = atomic_load_agent(ready + c) == gen; k = atomic_load_agent(placed + total_blocks + c) == gen; }
+                        }
+                        may[l] = m; isready[l] = r; isclean[l] = k;
+                    }
+                    clean |= (~ballot(may) & window) | (ballot(isclean) & ballot(isready));
+                    todo = ballot(isready) & ~clean;
+                }
+                for (int n = 0; n < 64 && todo && job_b < 0; ++n) {                // bounded: a window has at most 64 chunks
+                    const int k = ctz64(todo);
+                    todo &= todo - 1;
+                    const int c = (c0 + k) % nchunks;
+                    const ChunkDesc d = uniform_desc(descs + c);
+                    // the chunk's mode and its blocks' marks, two tiles of 64 marks a round trip
+                    const int ntiles = (d.nblocks + 63) >> 6;
+                    // (the waves that start at the same chunk share its blocks out evenly among themselves)
+                    const int rot = (int)(((int64_t)(w / nchunks) * d.nblocks / share) % imax(d.nblocks, 1));
+                    int take_behind = -1, take_any = -1;
+                    bool keep_out = false;
+                    for (int t0 = 0; t0 < ntiles && take_behind < 0 && !keep_out; t0 += 2) {
+                        LV<uint32_t> mk[2], md;
+                        FOR_LANES(l) { md[l] = 0; }
+                        FOR_LANES_W(l) { if (l == 0) md[l] = atomic_load_agent(reinterpret_cast<const uint32_t*>(&layout[c].mode)); }
+                        CIMG_UNROLL
+                        for (int q = 0; q < 2; q++) {
+                            FOR_LANES(l) {
+                                const int jb = 64 * (t0 + q) + l;
+                                mk[q][l] = jb < d.nblocks ? atomic_load_agent(placed + d.blk0 + jb) : gen;
+                            }
+                        }
+                        keep_out = uni(readlane(md, 0)) != 0;           // memcpyed, special-zero, does not fit: the owners' business
+                        CIMG_UNROLL
+                        for (int q = 0; q < 2; q++) {
+                            LV<bool> open;
+                            FOR_LANES(l) { open[l] = mk[q][l] != gen; }
+                            const uint64_t m = ballot(open);
+                            const int t = t0 + q;
+                            if (m && take_any < 0) take_any = 64 * t + ctz64(m);
+                            if (m && take_behind < 0 && t >= (rot >> 6)) {
+                                const int r6 = t == (rot >> 6) ? (rot & 63) : 0;
+                                const uint64_t behind = m >> r6 << r6;
+                                if (behind) take_behind = 64 * t + ctz64(behind);
+                            }
+                        }
+                    }
+                    const int take = take_behind >= 0 ? take_behind : take_any;
+                    if (keep_out || take < 0) {
+                        clean |= 1ull << k;
+                        FOR_LANES_W(l) { if (l == 0) atomic_store_agent(placed + total_blocks + c, gen); }
+                    } else {
+                        job_b = d.blk0 + take; job_s0 = 0; job_s1 = MAX_STREAMS; job_src = true;
+                        todo = 0;                                        // ONE block per look: the next pass starts from fresh marks
+                    }
                 }
             }
-            it = next;
+            if (job_b < 0) break;
+            {
+                const AssembleArgs aa = assemble_args(ap);
+                EmitBlock eb(aa, job_b);
+                if (marks) { eb.placed = placed; eb.placed_streams = placed + total_blocks + nchunks; eb.gen = gen; }
+                eb.run_streams(job_s0, job_s1, job_src);     // (reads the block's mark with its metadata; sets it)
+                if (job_src && eb.src_placed) ++helped;
+                owner_skipped = !job_src && eb.src_skipped;
+            }
+            if (job_item >= 0) {
+                FOR_LANES_W(l) { if (l == 0) next_item[job_item] = (job_next + 1) | ITEM_DONE; }
+                CIMG_ITEM_STAMP(fresh(ap)->dbg, job_item, 2);                 // diagnostics: the item's streams are in place
+#ifndef CIMG_EMULATE
+                // (... and, in bit 8 of the stamp's last word, whether a helper had placed its stored planes: this wave's own slot)
+                if (owner_skipped) { uint64_t* const dbg = fresh(ap)->dbg; if (dbg && __lane_id() == 0) dbg[16 * (size_t)job_item + 11] += 256; }
+#endif
+            }
+            worked = true;
         }
-        if (pending) wave_nap();
+        if (helping && looked && (clean & window) == window) helping = false;
+        if ((pending || helping) && !worked) wave_nap();
     }
-    if (pending) { FOR_LANES_W(l) { if (l == 0 && aa.layout_host) aa.layout_host[aa.nchunks].cbytes = -1; } }
+#ifndef CIMG_EMULATE
+    // diagnostics: the blocks this wave placed as a helper, from bit 16 on of the same word of its newest item's slot
+    if (helped > 0 && last >= 0) { uint64_t* const dbg = fresh(ap)->dbg; if (dbg && __lane_id() == 0) dbg[16 * (size_t)last + 11] += (uint64_t)helped << 16; }
+#else
+    (void)helped;
+#endif
+    if (pending || helping) { FOR_LANES_W(l) { if (l == 0) { ChunkLayout* const lh = fresh(ap)->layout_host; if (lh) lh[nchunks].cbytes = -1; } } }
 }
 
 // the next item of the launch for wave w, or -1 when every sub-queue is dry ("the work queue" at the top of this file).  Out of line:
@@ -1204,6 +1333,8 @@ struct EncodeStream {
     kernarg_ptr<EncodeArgs> ap;     // wave.h: fields are loaded where they are used, not held in SGPRs across the codec loop
     uint8_t* lds;
     int w;
+
+    int last = -1;                  // the items this wave encoded, newest first (next_item[])
 
     CIMG_DEV EncodeStream(kernarg_ptr<EncodeArgs> a_, uint8_t* lds_, int w_) : ap(a_), lds(lds_), w(w_) {}
 
@@ -1417,8 +1548,12 @@ struct EncodeStream {
     }
 
     // persistent workgroup: pull items until the queue is dry, then -- when the batch is assembled in place -- copy this wave's own
-    // streams into place as their chunks close
-    CIMG_DEV void run()
+    // streams into place as their chunks close, and help with the stored planes of waves that still encode (encode_emit_own).
+    // (The two phases are calls of their own, and the codec phase takes a budget of items, for the emulator's sake: it runs the waves
+    // of a launch one after the other, and only a test that stops a wave between the two sees a helper at work.)
+    CIMG_DEV void run() { run_codec(0x7fffffff); run_place(); }
+
+    CIMG_DEV void run_codec(int budget)
     {
         int items, assemble;
         uint32_t* queue;
@@ -1433,15 +1568,18 @@ struct EncodeStream {
             }
         }
         // bounded: a wave can never pop more than every item plus its final empty-queue pop
-        int last = -1;                                           // the items this wave encoded, newest first (next_item[])
-        for (int pops = 0; pops <= items + 1; ++pops) {
+        for (int pops = 0; pops <= items + 1 && pops < budget; ++pops) {
             const int item = uni(encode_pop_item(queue, items, w));
             if (item < 0) break;
             int chunk = 0;
             const int finished = run_item(item, chunk);
             if (assemble && finished > 0) last = encode_account(ap, item, last, chunk, finished);
         }
-        if (assemble && last >= 0) encode_emit_own(ap, last);
+    }
+
+    CIMG_DEV void run_place()
+    {
+        if (fresh(ap)->assemble) encode_emit_own(ap, last, w);
     }
 
     // run check + codec on the stream that sits in LDS; leaves payload in the scratch slot and the record in recs

@@ -364,10 +364,11 @@ struct cimg_engine {
     // `sync` holds (behind 16 unused words): per chunk the count of finished streams, then per chunk the generation at which the
     // chunk was last laid out inside a launch.  Both are zeroed when (re)allocated, when the generation wraps and after any
     // failed batch (sync_dirty).
-    DevBuf sync, next_item, qheads, zstd_seq, zstd_tables;   // (zstd encoder: per-wave sequence records, FSE tables of the predefined distributions)
+    DevBuf sync, next_item, qheads, placed, zstd_seq, zstd_tables;   // (zstd encoder: per-wave sequence records, FSE tables of the predefined distributions)
     uint32_t qpar[2] = {0, 0}, fold_gen = 0;   // qpar: which of its two sets of queue heads the next split / unsplit launch pops
     bool sync_dirty = true;
     size_t sync_chunks = 0;             // chunks the current layout of `sync` was made for
+    int enc_helpers = (getenv("CIMG_ENC_NO_HELPERS") && atoi(getenv("CIMG_ENC_NO_HELPERS")) != 0) ? 0 : getenv("CIMG_ENC_HELPERS") ? atoi(getenv("CIMG_ENC_HELPERS")) : 0;   // CIMG_ENC_HELPERS=n: idle waves of an encode launch place stored planes of busy ones (encode_kernel.h: encode_emit_own), every n-th wave helps (-1: the marks are kept, nobody helps).  OFF by default: measured slower (LABNOTES round 7).  CIMG_ENC_NO_HELPERS=1 forces it off.
     bool no_fold = getenv("CIMG_NO_ASSEMBLE_IN_LAUNCH") != nullptr;   // diagnostic: cimg_layout_chunks / cimg_emit_blocks behind every encode launch
     int64_t fold_batches = 0;
     // decode: the lean kernel (decode_lean_kernel.h) runs in front of the general one while it pays off
@@ -690,7 +691,7 @@ void cimg_engine_destroy(cimg_engine* e)
     (void)hipStreamSynchronize(e->stream);
     e->drain_timing();
     for (EventPair& ev : e->free_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-    for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->zstd_seq, &e->zstd_tables, &e->zplan,
+    for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->placed, &e->zstd_seq, &e->zstd_tables, &e->zplan,
                     &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots,
                     &e->upd_patch, &e->upd_units, &e->upd_stage, &e->upd_items, &e->upd_descs, &e->upd_chunks, &e->upd_blocks, &e->upd_layout,
                     &e->upd_src, &e->upd_new, &e->pack_tab, &e->trunc_tab, &e->trunc_src})
@@ -972,7 +973,17 @@ static int encode_launch(cimg_engine* e, EncodePlan& plan, int32_t nchunks, cons
     const size_t sync_words = 16 + 2 * (size_t)nchunks;
     if (sync_words * 4 > e->sync.cap || (size_t)nchunks > e->sync_chunks) e->sync_dirty = true;
     if ((rc = e->reserve(e->sync, sync_words * 4))) return rc;
-    if (++e->fold_gen == 0) { e->fold_gen = 1; e->sync_dirty = true; }
+    bool marks_stale = false;                       // the per-block marks (EncodeArgs::placed) could match this batch's generation
+    if (++e->fold_gen == 0) { e->fold_gen = 1; e->sync_dirty = true; marks_stale = true; }
+    // one mark per block, one per chunk and one per stream; compared with the generation like ready[], so zeroed once, when allocated
+    const size_t placed_bytes = 4 * ((size_t)plan.total_blocks * (size_t)(plan.cp.streams_per_block + 1) + (size_t)nchunks);
+    if (fold && e->enc_helpers) {
+        if (placed_bytes > e->placed.cap) marks_stale = true;
+        if ((rc = e->reserve(e->placed, placed_bytes))) return rc;
+        if (marks_stale && (rc = e->hip(hipMemsetAsync(e->placed.p, 0, e->placed.cap, e->stream), "marks memset"))) return rc;
+    } else if (marks_stale && e->placed.p) {
+        if ((rc = e->hip(hipMemsetAsync(e->placed.p, 0, e->placed.cap, e->stream), "marks memset"))) return rc;
+    }
     // the encode launches' work-queue heads (encode_kernel.h, "the work queue"): per kind of launch (split / unsplit) two sets of
     // ENC_NQ heads; a launch pops one set and zeroes the other for the next launch of its kind
     const size_t qset_bytes = (size_t)ENC_NQ * ENC_QSTRIDE * 4;
@@ -1053,7 +1064,8 @@ static int encode_launch(cimg_engine* e, EncodePlan& plan, int32_t nchunks, cons
                       (StreamRec*)e->recs.p, lds_bytes, plan.total_blocks, split, dbg, head, plan.uniform_nblocks, whole_blocks,
                       nullptr, 0, nullptr,
                       head_next, 0, fold ? 1 : 0, (uint8_t*)d_comp, (ChunkLayout*)e->layout.p, lay_host,
-                      sync + 16, sync + 16 + nslots, next_item, e->fold_gen};
+                      sync + 16, sync + 16 + nslots, next_item, e->fold_gen,
+                      (fold && e->enc_helpers) ? (uint32_t*)e->placed.p : nullptr, (fold && e->enc_helpers) ? e->enc_helpers : 0};
         const bool blz = plan.cp.compcode == CODEC_BLOSCLZ, zst = plan.cp.compcode == CODEC_ZSTD;
         void (*const enc_kernel)(EncodeArgs) = blz ? cimg_encode_streams_blosclz : zst ? cimg_encode_streams_zstd : rt ? cimg_encode_streams_rt : cimg_encode_streams;
         const int lds_slot = blz ? 3 : zst ? 4 : rt ? 11 : 0;

@@ -1,5 +1,8 @@
 """Encode launch with in-launch assembly: per work item, when it was taken (stamp 0), when its codec work ended (3), when its wave
-finished laying a chunk out -- only the 32 items whose wave closed a chunk -- (1), and when its streams were copied into place (2)."""
+finished laying a chunk out -- only the 32 items whose wave closed a chunk -- (1), and when its streams were copied into place (2).
+With helpers (CIMG_ENC_HELPERS=n) the last word of stamp 2 also says whether the item's owner found its stored planes placed by
+another wave (bit 8) and, in the slot of a wave's newest item, how many blocks that wave placed as a helper (from bit 16 on):
+"placed by non-owner" counts the former; what the helpers placed beyond that was placed twice ("duplicates")."""
 import sys, os
 sys.path[:0] = [os.path.join(os.getcwd(), "compressed-image_amd"), os.path.join(os.getcwd(), "tests")]
 import numpy as np, faulthandler; faulthandler.dump_traceback_later(90, exit=True)
@@ -41,3 +44,8 @@ late = last_end > np.percentile(last_end, 85)
 print("  the waves that run out of work last (%d): time from their last codec end to their last item in place: mean %.1f max %.1f us; the others: mean %.1f" % (late.sum(), own[late].mean(), own[late].max(), own[~late].mean()))
 order = np.argsort(np.nan_to_num(placed))[::-1][:8]
 print("  the 8 items in place last: " + ", ".join("item %d (wave %d): codec end %.0f, in place %.0f" % (i, wave[i], end[i], placed[i]) for i in order))
+# helpers: items whose owner skipped its stored planes because another wave had placed them; blocks placed by helpers in all
+flags = st[:, 11].astype(np.int64)
+skipped, helped = int(((flags >> 8) & 1).sum()), int((flags >> 16).sum())
+print("  tail: last codec end %.1f, last layout %.1f, last stream in place %.1f us; placed by non-owner: %d items; blocks placed by helpers: %d; duplicates: %d"
+      % (np.nanmax(end), c.max() if c.size else float("nan"), np.nanmax(placed), skipped, helped, max(helped - skipped, 0)))
