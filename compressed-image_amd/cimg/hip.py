@@ -21,6 +21,7 @@ K_PACK, K_INTERLEAVE = 20, 21                  # packed device storage (csrc/pac
 K_DECODE_WINDOW_STRIDED = 22                   # strided windows: the blocks that hold a sampled element (csrc/window_kernel.h)
 K_TRUNC_PREC = 23                              # trunc-prec: the masked copy in front of a compress batch (csrc/trunc_kernel.h)
 K_DECODE_WINDOW_GROUPED = 24                   # grouped windows: every block staged once for all its windows (csrc/window_kernel.h)
+K_ENCODE_WIDE_BLOSCLZ = 25                     # BloscLZ streams beyond 65 535 bytes: the wide encoder's BloscLZ instance (csrc/wide_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -28,7 +29,7 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
-           "cimg_trunc_prec", "cimg_decode_window_grouped")
+           "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)

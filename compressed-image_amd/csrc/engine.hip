@@ -266,6 +266,15 @@ extern "C" __global__ __launch_bounds__(64) void cimg_encode_wide_zstd(WideZstdE
     ww.run();
 }
 
+// BloscLZ streams beyond the normal encoder's uint16 table: cimg_encode_wide's waves with blosclz_wide_encode (32-bit positions in the
+// same 16 KiB of LDS, the stream read from device memory).
+extern "C" __global__ __launch_bounds__(64) void cimg_encode_wide_blosclz(WideEncodeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    WideEncodeWaveT<CODEC_BLOSCLZ> ww(a, reinterpret_cast<uint32_t*>(lds), (int)blockIdx.x);
+    ww.run();
+}
+
 extern "C" __global__ __launch_bounds__(64) void cimg_zstd_replay_wide(WideDecodeArgs a)
 {
     uint8_t* const slot = a.slots + (size_t)blockIdx.x * (size_t)a.d.lds_bytes;
@@ -603,6 +612,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_ENCODE_WIDE: return "cimg_encode_wide";
     case CIMG_K_DECODE_WIDE: return "cimg_decode_wide";
     case CIMG_K_ENCODE_WIDE_ZSTD: return "cimg_encode_wide_zstd";
+    case CIMG_K_ENCODE_WIDE_BLOSCLZ: return "cimg_encode_wide_blosclz";
     case CIMG_K_ZSTD_REPLAY_WIDE: return "cimg_zstd_replay_wide";
     case CIMG_K_DEINTERLEAVE: return "cimg_deinterleave";
     case CIMG_K_DECODE_ZSTD: return "cimg_decode_zstd";
@@ -870,6 +880,8 @@ static int compress_launch_wide(cimg_engine* e, EncodePlan& plan, int32_t nchunk
         }
         WideZstdEncodeArgs za{wa, (uint64_t*)e->wide_zseq.p, WIDE_ZSTD_SEQ_STRIDE, (const ZstdEncTables*)e->zstd_tables.p};
         if ((rc = e->launch(CIMG_K_ENCODE_WIDE_ZSTD, cimg_encode_wide_zstd, za, grid, 64, WIDE_ZSTD_LDS + 64))) return rc;
+    } else if (plan.cp.compcode == CODEC_BLOSCLZ) {
+        if ((rc = e->launch(CIMG_K_ENCODE_WIDE_BLOSCLZ, cimg_encode_wide_blosclz, wa, grid, 64, LZ4_HASH_BYTES + 64))) return rc;
     } else if ((rc = e->launch(CIMG_K_ENCODE_WIDE, cimg_encode_wide, wa, grid, 64, LZ4_HASH_BYTES + 64))) return rc;
     AssembleArgs aa{(const ChunkDesc*)e->descs_enc.p, nchunks, plan.cp, (const uint8_t*)d_raw, (const uint8_t*)e->scratch.p,
                     (const StreamRec*)e->recs.p, (uint8_t*)d_comp, (ChunkLayout*)e->layout.p, plan.uniform_nblocks, lay_host, 1};
@@ -934,7 +946,7 @@ static int compress_launch(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     const int64_t* const plan_off = copy_off.empty() ? raw_off : copy_off.data();
     EncodePlan plan;
     int rc = plan_encode_batch(hp, nchunks, plan_off, nbytes, comp_off, destsize, &plan, trunc != 0);
-    const bool wide = rc == ERR_CODEC_SUPPORT && plan_encode_wide(hp, nchunks, plan_off, nbytes, comp_off, destsize, &plan, trunc != 0) == 0;
+    const bool wide = rc == ERR_CODEC_SUPPORT && plan_encode_wide(hp, nchunks, plan_off, nbytes, comp_off, destsize, &plan, trunc != 0, true) == 0;
     if (rc < 0 && !wide) return e->fail(rc, "compress batch rejected by the planner (code %d): codec %d / filter pipeline / block size %d not available on the GPU path",
                                         rc, p->compcode, p->blocksize);
     if (trunc) {

@@ -1,6 +1,6 @@
 // wide_kernel.h -- blocks whose streams or staging do not fit the LDS of the normal kernels (blocks up to 256 KiB, LZ4 / LZ4HC /
-// zstd write, LZ4 / LZ4HC / BloscLZ read; zstd read: zstd_walk_kernel.h's replay out of a device-memory slot).  wide_plan.h decides
-// which batches come here; engine.hip launches the kernels.
+// zstd / BloscLZ write, LZ4 / LZ4HC / BloscLZ read; zstd read: zstd_walk_kernel.h's replay out of a device-memory slot).  wide_plan.h
+// decides which batches come here; engine.hip launches the kernels.
 //
 //   cimg_encode_wide   persistent single-wave workgroups pull streams from one atomic counter.  A stream that needs the byte
 //                      shuffle is staged into the wave's own plane in device memory (a stream that is a plain slice of the
@@ -21,6 +21,9 @@
 //                      the replay with its planes in a device-memory slot per workgroup (zstd_walk_kernel.h).
 //   cimg_encode_wide_zstd  the same persistent waves and staging as cimg_encode_wide; each stream becomes one zstd frame of
 //                      ceil(n / 128 KiB) blocks (zstd_wide_encode below, the frame writer of zstd_encode.h).
+//   cimg_encode_wide_blosclz  the same persistent waves and staging; each stream goes through blosclz_wide_encode below: the windowed
+//                      scan of blosclz_kernel.h over a stream in device memory, with a table of 32-bit positions in the same
+//                      16 KiB of LDS.  Bytes are those of BloscLZ 2.3.0 at every length up to 256 KiB.
 #pragma once
 #include "encode_kernel.h"
 
@@ -191,6 +194,215 @@ last_literals:
     return op;
 }
 
+// ---- BloscLZ on the wide route ----------------------------------------------------------------------------------------------------
+// blosclz_wide_encode is blosclz_encode_body (blosclz_kernel.h) restated for a stream in device memory: the same windows of 64
+// positions, collision rule, commit bound, 12-byte look-ahead, parked sequences and counting probe passes, with three differences.
+//   * The table holds 4096 x uint32 positions (16 KiB of LDS, the table of the other wide encoders), so a stream may be 256 KiB long.
+//   * A candidate MAX_FARDISTANCE (65 535 + 8191 - 1) or more bytes back is no hit; its slot is overwritten all the same.  (Below
+//     64 KiB no candidate is that far, which is why the normal-path encoder has no such check.)
+//   * The stream is read where it lies, and NO load touches a byte outside [in, in + n): a stream that is a plain slice of the
+//     caller's pixels may end with the caller's allocation.  Every dword load whose index is not provably at most n - 4 goes through
+//     blzw_ld32, which CLAMPS the index to n - 4 and shifts the bytes down; the bytes it makes up beyond the stream's end lie where
+//     the codec's own bound (ip_bound = n - 1) has already cut the comparison.  Byte loads are guarded by their counts.
+enum : int { BLZ_MAX_FARDISTANCE = 65535 + BLZ_MAX_DISTANCE - 1 };
+
+// the four bytes in[idx .. idx + 4) of a stream of n >= 4 bytes, idx >= 0; bytes at n and beyond read as zero
+CIMG_DEV uint32_t blzw_ld32(const uint8_t* in, int idx, int n)
+{
+    const int c = imin(idx, n - 4);
+    const int over = idx - c;
+    return over >= 4 ? 0u : wide_rd32(in + c) >> (8 * over);
+}
+
+// blz_count on device memory: equal bytes in[a + k] == in[b + k], k = 0 .. maxc - 1, b < a, a + maxc <= n
+CIMG_DEV int blzw_count(const uint8_t* in, int a, int b, int maxc, int n)
+{
+    int cnt = 0;
+    for (int it = 0; it <= n / 256 + 1; ++it) {
+        LV<int> len;
+        LV<bool> stop;
+        FOR_LANES(l) {
+            const int k = cnt + 4 * l;
+            const uint32_t x = blzw_ld32(in, a + k, n) ^ blzw_ld32(in, b + k, n);
+            const int ln = imin(x ? (int)(__builtin_ctz(x) >> 3) : 4, imax(maxc - k, 0));
+            len[l] = ln;
+            stop[l] = ln < 4;
+        }
+        const uint64_t sm = ballot(stop);
+        if (sm) { const int f = ctz64(sm); return cnt + 4 * f + readlane(len, f); }
+        cnt += 256;
+    }
+    return imin(cnt, maxc);
+}
+
+// Bit-exact blosclz_compress(clevel, in, n, out, cap) by one wave for 0 <= n <= WIDE_MAX_BLOCK.  in: device memory, exactly n
+// readable bytes; tab: 16 KiB of LDS.  Returns bytes written, 0 if the codec gives up / the result does not fit, < 0 if a loop
+// guard tripped.  need_out = smallest cap that still succeeds (max(66, size + 1): blosclz_kernel.h says why).
+CIMG_DEV int blosclz_wide_encode(const uint8_t* in, uint32_t* tab, int n, uint8_t* out_generic, int cap, int clevel, int& need_out)
+{
+    cimg_global_u8p out = CIMG_AS_GLOBAL(out_generic);
+    cimg_lds_vu32p tab32 = CIMG_AS_LDS_VU32(tab);
+    need_out = 0;
+    if (n < 16 || cap < 66 || clevel < 1 || clevel > 9) return 0;
+    const int hashlog = clevel == 1 ? BLZ_HASH_LOG - 2 : (clevel == 2 ? BLZ_HASH_LOG - 1 : BLZ_HASH_LOG);
+    const int minlen_tab = clevel <= 2 ? 12 : 14 - clevel;
+    const int maxlen = n >> 3;
+    int pass = clevel == 9 ? 0 : 1;                                   // level 9 probes with ipshift 3 and 4, the others with 4; then the real scan
+    int csize3 = 0, csize4 = 0, ipshift = 4;
+
+    LV<int> P_anchor, P_lit, P_dist, P_len;
+    FOR_LANES(l) { P_anchor[l] = 0; P_lit[l] = 0; P_dist[l] = 0; P_len[l] = 0; }
+    int np = 0, op = 0;
+    int anchor = 0;
+    int ending = 1;                                                   // 1: go on; 0: give up (stored raw); < 0: a loop guard tripped
+    bool saw_hit = false;
+    for (; pass < 3; ++pass) {
+        const bool probe = pass < 2;
+        if (pass == 2) {
+            const int cs = clevel == 9 ? imin(csize3, csize4) : csize4;
+            ipshift = (clevel == 9 && csize3 < csize4) ? 3 : 4;
+            const double cratio = (double)maxlen / (double)cs;
+            const double thr = clevel <= 4 ? 2.0 : (clevel == 5 ? 1.8 : (clevel == 6 ? 1.6 : (clevel == 7 ? 1.4 : (clevel == 8 ? 1.2 : 1.1))));
+            if (cratio < thr) { ending = 0; break; }
+        }
+        const int shift = probe ? 32 - BLZ_HASH_LOG : 32 - hashlog;
+        const int ips = probe ? (pass == 0 ? 3 : 4) : ipshift;
+        const int minlen = probe ? 3 : (clevel == 9 ? ipshift : minlen_tab);
+        const int nlim = probe ? maxlen : n;
+        const int ip_bound = nlim - 1, ip_limit = nlim - 12;
+        for (int k = 0; k < 4096; k += 64) { FOR_LANES(l) { tab32[k + l] = 0; } }
+        int ip = probe ? 0 : 4;
+        anchor = 0;
+        int oc = 5, copyc = 4;                                        // the probe's counters ("4 literals already copied")
+        int guard = 0;
+        while (ip < ip_limit) {
+            if (++guard > n + 2) { ending = -1; break; }              // a window consumes at least one position
+            const int nv = imin(64, ip_limit - ip);
+            LV<int> pos;
+            LV<bool> valid;
+            LV<uint32_t> v, h;
+            FOR_LANES(l) {
+                pos[l] = ip + l;
+                valid[l] = l < nv;
+                v[l] = wide_rd32(in + (l < nv ? ip + l : 0));          // (ip + l < nlim - 12)
+                h[l] = blz_hash(v[l], shift);
+            }
+            LV<uint32_t> ph, pv;
+            lane_prev(h, ph);
+            lane_prev(v, pv);
+            LV<bool> head, cont;
+            LV<uint32_t> old;
+            FOR_LANES(l) {
+                cont[l] = valid[l] && l > 0 && h[l] == ph[l];
+                head[l] = valid[l] && !cont[l];
+                old[l] = tab32[h[l]];
+            }
+            FOR_LANES_W(l) { if (head[l]) tab32[h[l]] = (uint32_t)pos[l]; }
+            LV<bool> loser, hit;
+            LV<int> cand;
+            FOR_LANES(l) {
+                const uint32_t rb = tab32[h[l]];
+                const uint32_t mvh = wide_rd32(in + old[l]);           // (a table entry is a position below an ip_limit, or 0)
+                const uint32_t mv = head[l] ? mvh : pv[l];
+                loser[l] = head[l] && rb != (uint32_t)pos[l];
+                cand[l] = head[l] ? (int)old[l] : pos[l] - 1;
+                // distance 0: position 0 against the empty table; MAX_FARDISTANCE and beyond: not a hit, the slot is written all the same
+                hit[l] = valid[l] && mv == v[l] && cand[l] != pos[l] && pos[l] - cand[l] < BLZ_MAX_FARDISTANCE;
+            }
+            uint64_t involved = ballot(loser);
+            if (involved) {
+                FOR_LANES_W(l) { if (loser[l]) tab32[h[l]] = (uint32_t)pos[l]; }
+                LV<bool> inv;
+                FOR_LANES(l) { inv[l] = head[l] && (loser[l] || tab32[h[l]] != (uint32_t)pos[l]); }
+                involved = ballot(inv);
+            }
+            const int k1 = ctz64(involved);
+            const int limit = imin(nv - 1, k1);
+            const uint64_t below = limit >= 63 ? ~0ull : ((1ull << (limit + 1)) - 1);
+            const uint64_t hits = ballot(hit) & below;
+            int m = -1;
+            if (hits) {
+                saw_hit = true;
+                // a 4-byte hit is a match only if it is long enough: the next 12 bytes decide every rule
+                LV<bool> acc;
+                FOR_LANES(l) {
+                    const int a = hit[l] ? pos[l] + 4 : 0, b = hit[l] ? cand[l] + 4 : 0;
+                    const uint32_t x0 = blzw_ld32(in, a, n) ^ blzw_ld32(in, b, n);
+                    const uint32_t x1 = blzw_ld32(in, a + 4, n) ^ blzw_ld32(in, b + 4, n);
+                    const uint32_t x2 = blzw_ld32(in, a + 8, n) ^ blzw_ld32(in, b + 8, n);
+                    const int kk = x0 ? (int)(__builtin_ctz(x0) >> 3) : (x1 ? 4 + (int)(__builtin_ctz(x1) >> 3) : (x2 ? 8 + (int)(__builtin_ctz(x2) >> 3) : 12));
+                    const int room = ip_bound - (pos[l] + 4);
+                    const int lenlb = 4 + imin(kk + 1, room) - ips;            // exact below 13, a lower bound from there
+                    const bool far = pos[l] - cand[l] - 1 >= BLZ_MAX_DISTANCE;
+                    const bool ok = probe ? lenlb >= (far ? 4 : 3) : (lenlb >= minlen && !(lenlb <= 5 && far));
+                    acc[l] = hit[l] && ok;
+                }
+                const uint64_t am = ballot(acc) & below;
+                if (am) m = ctz64(am);
+            }
+            const int B = m >= 0 ? m : limit;
+            const uint64_t headmask = ballot(head), contmask = ballot(cont);
+            const uint64_t above = B >= 63 ? 0ull : (~0ull << (B + 1));
+            if (headmask & above) {
+                FOR_LANES_W(l) { if (head[l] && l > B) tab32[h[l]] = old[l]; }
+                FOR_LANES_W(l) { if (head[l] && l == B) tab32[h[l]] = (uint32_t)pos[l]; }
+            }
+            if (contmask & ~above) {
+                FOR_LANES_W(l) {
+                    if (cont[l] && l <= B && (l == B || !((contmask >> ((l + 1) & 63)) & 1) || l == 63)) tab32[h[l]] = (uint32_t)pos[l];
+                }
+            }
+            if (m < 0) { ip += B + 1; continue; }
+            // ---- a match at lane m ------------------------------------------------------------------------------
+            const int mpos = readlane(pos, m), mref = readlane(cand, m);
+            const int room = ip_bound - (mpos + 4);
+            const int k = blzw_count(in, mpos + 4, mref + 4, room, n);
+            const int nip = mpos + 4 + (k < room ? k + 1 : room) - ips;
+            const int len = nip - mpos, dist = mpos - mref - 1, L = mpos - anchor;
+            if (probe) {
+                const int t = copyc + L;
+                oc += L + (t >> 5);
+                if ((t & 31) == 0) oc--;
+                copyc = 0;
+                oc += (len >= 7 ? blz_div255(len - 7) + 1 : 0) + (dist >= BLZ_MAX_DISTANCE ? 4 : 2) + 1;
+            } else {
+                const int slot = np;
+                FOR_LANES(l) { if (l == slot) { P_anchor[l] = anchor; P_lit[l] = L; P_dist[l] = dist; P_len[l] = len; } }
+                if (++np == 64) {
+                    if (!blz_emit_pending(in, out, cap, op, np, P_anchor, P_lit, P_dist, P_len)) { ending = 0; break; }
+                    np = 0;
+                }
+            }
+            {   // "update the hash at match boundary": positions nip and nip + 1 (nip <= nlim - 1 - ips: four bytes are there)
+                LV<uint32_t> s2;
+                FOR_LANES(l) { s2[l] = wide_rd32(in + nip); }
+                FOR_LANES_W(l) { tab32[blz_hash(s2[l], shift)] = (uint32_t)nip; }
+                FOR_LANES_W(l) { tab32[blz_hash(s2[l] >> 8, shift)] = (uint32_t)(nip + 1); }
+            }
+            ip = nip + 2;
+            anchor = ip;
+        }
+        if (ending <= 0) break;
+        if (probe) {
+            const int Lc = imax(ip_limit - anchor, 0);
+            const int t = copyc + Lc;
+            oc += Lc + (t >> 5);
+            if ((t & 31) == 0) oc--;
+            if (pass == 0) csize3 = oc; else csize4 = oc;
+            // (a first probe that never met four equal bytes is the second one too: blosclz_kernel.h)
+            if (pass == 0 && !saw_hit) { csize4 = csize3; pass = 1; }
+        }
+    }
+    if (ending <= 0) return ending;
+    if (np && !blz_emit_pending(in, out, cap, op, np, P_anchor, P_lit, P_dist, P_len)) return 0;
+    const int Lf = n - anchor;
+    const int size = op + blz_lit_bytes(Lf);
+    if (size + 1 > cap) return 0;
+    blz_emit_literals(in, anchor, out, op, Lf);
+    need_out = imax(66, size + 1);
+    return size;
+}
+
 // true if all n bytes equal the first (any alignment)
 CIMG_DEV bool wide_is_run(const uint8_t* in, int n, uint32_t& value)
 {
@@ -300,7 +512,7 @@ CIMG_DEV int zstd_wide_encode(const uint8_t* in, uint32_t* tab, const ZstdEncTab
 }
 
 // one wave: pulls streams until the counter passes the last one (CODEC_LZ4: cimg_encode_wide, every LZ4 / LZ4HC batch;
-// CODEC_ZSTD: cimg_encode_wide_zstd, with z)
+// CODEC_ZSTD: cimg_encode_wide_zstd, with z; CODEC_BLOSCLZ: cimg_encode_wide_blosclz)
 template <int CODEC>
 struct WideEncodeWaveT {
     const WideEncodeArgs& a;
@@ -376,7 +588,8 @@ struct WideEncodeWaveT {
                 cb = zstd_wide_encode(in, tab, reinterpret_cast<const ZstdEncTables*>(tab + LZ4_HASH_BYTES / 4), n, out, n,
                                       z->seq + (int64_t)w * z->seq_stride);
                 need = cb;                                // (a frame fits a budget iff the budget holds its bytes)
-            } else cb = lz4_wide_encode(in, tab, n, out, n, a.p.accel, need);
+            } else if constexpr (CODEC == CODEC_BLOSCLZ) cb = blosclz_wide_encode(in, tab, n, out, n, a.p.clevel, need);
+            else cb = lz4_wide_encode(in, tab, n, out, n, a.p.accel, need);
             if (cb > 0 && cb < n) { r.kind = REC_LZ4; r.csize = cb; r.need = need; }
             else wide_copy(in, out, n);
         }

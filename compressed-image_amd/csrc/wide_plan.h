@@ -1,7 +1,8 @@
 // wide_plan.h -- the planner of the wide-block kernels (wide_kernel.h).  It is asked only after plan_encode_batch /
 // plan_decode_batch (plan.h) refused a batch with ERR_CODEC_SUPPORT, and it takes exactly what those refuse for size alone:
-// LZ4 / LZ4HC streams longer than the byU16 encoder's 65 546 bytes, zstd streams longer than ZSTD_ENC_MAX_INPUT, or shuffled
-// blocks whose staging exceeds LDS (write), and blocks whose staging exceeds LDS (read; zstd blocks among them go on to the zstd
+// LZ4 / LZ4HC streams longer than the byU16 encoder's 65 546 bytes, zstd streams longer than ZSTD_ENC_MAX_INPUT, BloscLZ streams
+// longer than BLZ_MAX_INPUT (for a caller that has the BloscLZ instance of the wide encoder: `blosclz`), or shuffled blocks whose
+// staging exceeds LDS (write), and blocks whose staging exceeds LDS (read; zstd blocks among them go on to the zstd
 // read path's walk and cimg_zstd_replay_wide) -- in both cases for blocks up to WIDE_MAX_BLOCK.  Everything else keeps the normal
 // planner's answer.  Pure C++, shared by the engine and the emulator tests.
 #pragma once
@@ -11,8 +12,10 @@
 namespace cimg {
 
 // Write side: the whole batch goes through cimg_encode_wide (every stream, whatever its length) and the two assembly kernels.
+// blosclz: the caller launches cimg_encode_wide_blosclz for a BloscLZ plan (the engine does; a caller with the LZ4 instance alone
+// leaves it false and BloscLZ stays refused).  Such a batch is planned like an lz4 one: cp.clevel is what the kernel reads.
 inline int plan_encode_wide(const HostCParams& p_in, int nchunks, const int64_t* raw_off, const int32_t* nbytes,
-                            const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan, bool truncated = false)
+                            const int64_t* comp_off, const int32_t* destsize, EncodePlan* plan, bool truncated = false, bool blosclz = false)
 {
     plan->descs.resize((size_t)nchunks);
     HostCParams p;
@@ -21,7 +24,7 @@ inline int plan_encode_wide(const HostCParams& p_in, int nchunks, const int64_t*
     if (rc < 0) return rc;
     rc = single_filter(p, &filter);
     if (rc < 0) return rc;
-    if (p.compcode != CODEC_LZ4 && p.compcode != CODEC_LZ4HC && p.compcode != CODEC_ZSTD) return ERR_CODEC_SUPPORT;   // BloscLZ / zlib: not built
+    if (p.compcode != CODEC_LZ4 && p.compcode != CODEC_LZ4HC && p.compcode != CODEC_ZSTD && !(blosclz && p.compcode == CODEC_BLOSCLZ)) return ERR_CODEC_SUPPORT;   // zlib: not built
     if (filter == FILTER_BITSHUFFLE) return ERR_CODEC_SUPPORT;
     if (p.blocksize <= 0 || p.blocksize > WIDE_MAX_BLOCK) return ERR_CODEC_SUPPORT;      // (automatic block size stays with plan.h)
     CodecParams& cp = plan->cp;

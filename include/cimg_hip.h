@@ -353,7 +353,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* trunc-prec (filters[4] == 4): the masked copy in front of a compress batch */
        CIMG_K_TRUNC_PREC = 23,
        /* the window launch of cimg_decompress_windows_grouped_device / _host */
-       CIMG_K_DECODE_WINDOW_GROUPED = 24, CIMG_K_COUNT = 25 };
+       CIMG_K_DECODE_WINDOW_GROUPED = 24,
+       /* BloscLZ streams beyond 65 535 bytes (blocks up to 256 KiB): the wide encoder's BloscLZ instance */
+       CIMG_K_ENCODE_WIDE_BLOSCLZ = 25, CIMG_K_COUNT = 26 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);
