@@ -22,6 +22,7 @@ K_DECODE_WINDOW_STRIDED = 22                   # strided windows: the blocks tha
 K_TRUNC_PREC = 23                              # trunc-prec: the masked copy in front of a compress batch (csrc/trunc_kernel.h)
 K_DECODE_WINDOW_GROUPED = 24                   # grouped windows: every block staged once for all its windows (csrc/window_kernel.h)
 K_ENCODE_WIDE_BLOSCLZ = 25                     # BloscLZ streams beyond 65 535 bytes: the wide encoder's BloscLZ instance (csrc/wide_kernel.h)
+K_UPDATE_PATCH_STRIDED = 26                    # strided window writes: the patch launch of cimg_update_windows_strided_* (csrc/update_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -29,7 +30,7 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
-           "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz")
+           "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz", "cimg_update_patch_strided")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -54,6 +55,7 @@ EXPORTS = (
     "cimg_decompress_windows_strided_device", "cimg_decompress_windows_strided_host",
     "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
+    "cimg_update_windows_strided_device", "cimg_update_windows_strided_host",
     "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
     "cimg_interleave_device", "cimg_engine_wait_stream", "cimg_device_range_check",
     # include/blosc2.h
@@ -198,6 +200,8 @@ def load():
     L.cimg_update_windows_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_update_windows_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
     L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
+    L.cimg_update_windows_strided_device.argtypes = L.cimg_update_windows_device.argtypes
+    L.cimg_update_windows_strided_host.argtypes = L.cimg_update_windows_host.argtypes
     L.cimg_compress_batch_device_packed_begin.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp]
     L.cimg_compress_batch_device_packed_fetch.argtypes = [vp, C.c_int32, vp, vp]
     L.cimg_pack_chunks_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
@@ -517,31 +521,41 @@ class Engine:
         return status if check else (rc, status)
 
     # ---- window writes (include/cimg_hip.h: cimg_update_windows_*) ----
+    def update_windows_strided_device(self, p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size=None,
+                                      check=True):
+        """update_windows_device over cimg_window_strided specs (with col_pitch): cimg_update_windows_strided_device"""
+        return self.update_windows_device(p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size, check,
+                                          strided=True)
+
+    def update_windows_strided_host(self, p, chunks, destsize, specs, src, check=True):
+        """update_windows_host over cimg_window_strided specs: cimg_update_windows_strided_host"""
+        return self.update_windows_host(p, chunks, destsize, specs, src, check, strided=True)
+
     def update_windows_device(self, p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size=None,
-                              check=True):
+                              check=True, strided=False):
         """windows of d_src written into device-resident chunks; the touched chunks' new forms go to d_new + new_off[i].
         Returns (new_cbytes, status) (with check=False: (rc, new_cbytes, status))."""
         comp_off, nbytes, blocksize, destsize, new_off = _i64(comp_off), _i32(nbytes), _i32(blocksize), _i32(destsize), _i64(new_off)
         cs = _i32(comp_size) if comp_size is not None else None
-        w = windows(specs)
+        w = strided_windows(specs) if strided else windows(specs)
         status = np.zeros(nbytes.size, np.int32)
         ncb = np.zeros(nbytes.size, np.int32)
-        rc = load().cimg_update_windows_device(self.handle, C.byref(p), nbytes.size, d_comp, _ptr(comp_off),
-                                               _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), _ptr(destsize),
-                                               len(specs), w, d_src, d_new, _ptr(new_off), _ptr(ncb), _ptr(status))
+        fn = load().cimg_update_windows_strided_device if strided else load().cimg_update_windows_device
+        rc = fn(self.handle, C.byref(p), nbytes.size, d_comp, _ptr(comp_off), _ptr(cs) if cs is not None else None, _ptr(nbytes),
+                _ptr(blocksize), _ptr(destsize), len(specs), w, d_src, d_new, _ptr(new_off), _ptr(ncb), _ptr(status))
         if check:
             self._check(rc)
             return ncb, status
         return rc, ncb, status
 
-    def update_windows_host(self, p, chunks, destsize, specs, src, check=True):
+    def update_windows_host(self, p, chunks, destsize, specs, src, check=True, strided=False):
         """chunks: list of bytes; src: a uint8 numpy array the windows' out_off / out_pitch point into.  Returns (list of new chunk
         bytes, None where untouched, status) (with check=False: (rc, new chunks, status))."""
         sizes = [len(c) for c in chunks]
         comp_off = _i64(np.concatenate([[0], np.cumsum(sizes[:-1], dtype=np.int64)]))
         comp = np.frombuffer(b"".join(chunks) + bytes(16), np.uint8)
         held, destsize = _i32(sizes), _i32(destsize)
-        w = windows(specs)
+        w = strided_windows(specs) if strided else windows(specs)
         n = len(chunks)
         status = np.zeros(n, np.int32)
         ncb = np.zeros(n, np.int32)
@@ -554,8 +568,9 @@ class Engine:
             return C.addressof(b)
         cb = _ALLOC_FN(alloc)
         src = np.ascontiguousarray(src).view(np.uint8)
-        rc = load().cimg_update_windows_host(self.handle, C.byref(p), n, _ptr(comp), _ptr(comp_off), _ptr(held), _ptr(destsize), len(specs),
-                                             w, _ptr(src), cb, None, ptrs, _ptr(ncb), _ptr(status))
+        fn = load().cimg_update_windows_strided_host if strided else load().cimg_update_windows_host
+        rc = fn(self.handle, C.byref(p), n, _ptr(comp), _ptr(comp_off), _ptr(held), _ptr(destsize), len(specs), w, _ptr(src), cb, None, ptrs,
+                _ptr(ncb), _ptr(status))
         new = [C.string_at(ptrs[i], int(ncb[i])) if ptrs[i] else None for i in range(n)]
         if check:
             self._check(rc)

@@ -300,6 +300,31 @@ extern "C" __global__ __launch_bounds__(256) void cimg_update_patch(PatchArgs a)
     }
 }
 
+// Strided window writes: the same staging, then the overlays of StridedPatchBlock in the schedule the host chose for the unit -- one
+// item by all 256 threads; an ordered unit item after item with a barrier between; a disjoint unit's items dealt over the four
+// waves with no barrier (no two of them write a common byte).
+extern "C" __global__ __launch_bounds__(256) void cimg_update_patch_strided(StridedPatchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    StridedPatchBlock sb(a, lds, (int)blockIdx.x);
+    sb.pb.phase_a(wave);
+    __syncthreads();
+    sb.pb.phase_base(wave);
+    __syncthreads();
+    const int n = sb.pb.u.nitems;
+    if (n == 1) {
+        sb.overlay(0, wave * 64, 256);
+    } else if (sb.disjoint) {
+        for (int k = wave; k < n; k += 4) sb.overlay(k, 0, 64);
+    } else {
+        for (int k = 0; k < n; k++) {
+            if (k) __syncthreads();                                  // (a later window wins where two overlap)
+            sb.overlay(k, wave * 64, 256);
+        }
+    }
+}
+
 // Splice: one wave lays out each spliced chunk (old streams of untouched blocks, new streams of re-encoded ones); then one workgroup
 // per block copies the streams into place.
 extern "C" __global__ __launch_bounds__(64) void cimg_update_layout(SpliceArgs a)
@@ -421,7 +446,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15)
+    int max_dyn_lds[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -626,6 +651,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_DECODE_WINDOW_STRIDED: return "cimg_decode_window_strided";
     case CIMG_K_DECODE_WINDOW_GROUPED: return "cimg_decode_window_grouped";
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
+    case CIMG_K_UPDATE_PATCH_STRIDED: return "cimg_update_patch_strided";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
     case CIMG_K_PACK: return "cimg_pack_chunks";
@@ -2450,13 +2476,27 @@ struct EngineUpdateEnv : EngineChunks {
     int patch(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<WindowItem>& stage,
               const std::vector<WindowItem>& items, int to_whole, int64_t patch_bytes, int32_t* status)
     {
+        return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
+    }
+    int patch_strided(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<StridedPatchUnit>& units,
+                      const std::vector<WindowItem>& stage, const std::vector<StridedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                      int32_t* status)
+    {
+        return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
+    }
+
+    // cimg_update_patch over PatchUnit / WindowItem, or cimg_update_patch_strided over StridedPatchUnit / StridedWindowItem
+    template <class Unit, class Item>
+    int patch_launch(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<Unit>& units, const std::vector<WindowItem>& stage,
+                     const std::vector<Item>& items, int to_whole, int64_t patch_bytes, int32_t* status)
+    {
         int rc;
         const int nchunks = (int)descs.size();
         if (!to_whole && (rc = e->reserve(e->upd_patch, (size_t)patch_bytes + 64))) return rc;
         if ((rc = upload(e->upd_descs, descs.data(), descs.size() * sizeof(ChunkDesc), "update descs H2D"))) return rc;
-        if ((rc = upload(e->upd_units, units.data(), units.size() * sizeof(PatchUnit), "update units H2D"))) return rc;
+        if ((rc = upload(e->upd_units, units.data(), units.size() * sizeof(Unit), "update units H2D"))) return rc;
         if ((rc = upload(e->upd_stage, stage.data(), stage.size() * sizeof(WindowItem), "update items H2D"))) return rc;
-        if ((rc = upload(e->upd_items, items.data(), items.size() * sizeof(WindowItem), "update items H2D"))) return rc;
+        if ((rc = upload(e->upd_items, items.data(), items.size() * sizeof(Item), "update items H2D"))) return rc;
         if ((rc = e->reserve(e->h_upd_st, (size_t)nchunks * 4))) return rc;
         memset(e->h_upd_st.p, 0, (size_t)nchunks * 4);
         int32_t* d_st = nullptr;
@@ -2465,13 +2505,19 @@ struct EngineUpdateEnv : EngineChunks {
         pa.w.d = DecodeArgs{(const ChunkDesc*)e->upd_descs.p, nchunks, d_comp, nullptr, d_st, lds_bytes, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1, 0};
         pa.w.items = (const WindowItem*)e->upd_stage.p;
         pa.w.nitems = (int32_t)stage.size();
-        pa.units = (const PatchUnit*)e->upd_units.p;
-        pa.items = (const WindowItem*)e->upd_items.p;
         pa.src = d_src;
         pa.dst = (uint8_t*)(to_whole ? e->win_whole.p : e->upd_patch.p);
         pa.nunits = (int32_t)units.size();
-        if ((rc = e->allow_lds(cimg_update_patch, 13, lds_bytes))) return rc;
-        rc = e->launch(CIMG_K_UPDATE_PATCH, cimg_update_patch, pa, (int)units.size(), 256, lds_bytes);
+        if constexpr (std::is_same_v<Item, StridedWindowItem>) {
+            const StridedPatchArgs sa{pa, (const StridedPatchUnit*)e->upd_units.p, (const StridedWindowItem*)e->upd_items.p};
+            if ((rc = e->allow_lds(cimg_update_patch_strided, 16, lds_bytes))) return rc;
+            rc = e->launch(CIMG_K_UPDATE_PATCH_STRIDED, cimg_update_patch_strided, sa, (int)units.size(), 256, lds_bytes);
+        } else {
+            pa.units = (const PatchUnit*)e->upd_units.p;
+            pa.items = (const WindowItem*)e->upd_items.p;
+            if ((rc = e->allow_lds(cimg_update_patch, 13, lds_bytes))) return rc;
+            rc = e->launch(CIMG_K_UPDATE_PATCH, cimg_update_patch, pa, (int)units.size(), 256, lds_bytes);
+        }
         const int src = cimg_engine_synchronize(e);
         if (rc || src) return rc ? rc : src;
         const int32_t* hs = (const int32_t*)e->h_upd_st.p;
@@ -2530,14 +2576,11 @@ int update_result(cimg_engine* e, int rc, int32_t nchunks, const int32_t* status
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
-                               const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
-                               int32_t nwindows, const cimg_window* w, const void* d_src, void* d_new, const int64_t* new_off,
-                               int32_t* new_cbytes, int32_t* status)
+template <class Spec>
+int update_device_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                       const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                       int32_t nwindows, const Spec* w, const void* d_src, void* d_new, const int64_t* new_off,
+                       int32_t* new_cbytes, int32_t* status)
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
@@ -2550,15 +2593,15 @@ int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nc
     e->cflight_chunks = -1;
     EngineUpdateEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, p, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr};
     UpdateStats st;
-    rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
-                    reinterpret_cast<const WindowSpec*>(w), new_off, new_cbytes, status, &st);
+    rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, w, new_off, new_cbytes, status, &st);
     e->upd_stats = st;
     return update_result(e, rc, nchunks, status);
 }
 
-int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
-                             const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
-                             const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
+template <class Spec>
+int update_host_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                     const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const Spec* w,
+                     const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
 {
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
@@ -2573,7 +2616,8 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
     e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
     const uint8_t* hc = (const uint8_t*)h_comp;
     UpdateHostPlan hp;
-    if ((rc = plan_update_host(p->typesize, nchunks, hc, comp_off, comp_size, destsize, nwindows, reinterpret_cast<const WindowSpec*>(w), status, &hp)) < 0)
+    std::vector<Spec> dw;                                  // the windows with their rows packed
+    if ((rc = plan_update_host(p->typesize, nchunks, hc, comp_off, comp_size, destsize, nwindows, w, status, &hp, &dw)) < 0)
         return hp.bad_window >= 0 || hp.short_chunk >= 0 ? named_fail(e, rc, hp, nchunks, w, comp_size) : update_result(e, rc, nchunks, status);
     // only the touched chunks go up, and the windows' rows go up packed
     if ((rc = e->reserve(e->stage_comp, (size_t)hp.comp_total + 64))) return rc;
@@ -2586,7 +2630,7 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
         HostPin pin_in(e, h_comp, comp_off, hp.up.data(), nchunks, false);
         if ((rc = copy_in(e, e->stream, sc, hp.d_comp_off.data(), hc, comp_off, hp.up.data(), 0, nchunks, "chunk H2D"))) return rc;
         for (int k = 0; k < nwindows; k++) {
-            const WindowSpec& d = hp.dw[(size_t)k];
+            const Spec& d = dw[(size_t)k];
             if (!hp.wbytes[(size_t)k]) continue;
             rc = copy_rows(e, ss + d.out_off, d.out_pitch, hs + w[k].out_off, w[k].out_pitch, d.out_pitch, w[k].height, hipMemcpyHostToDevice, "window H2D");
             if (rc) { (void)cimg_engine_synchronize(e); return rc; }
@@ -2594,7 +2638,7 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
         EngineUpdateEnv env{{e, sc, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data()}, p, ss, (uint8_t*)e->upd_new.p, hc, comp_off};
         UpdateStats st;
         rc = run_update(env, to_host(p), nchunks, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data(), destsize, nwindows,
-                        hp.dw.data(), hp.new_off.data(), new_cbytes, status, &st);
+                        dw.data(), hp.new_off.data(), new_cbytes, status, &st);
         e->upd_stats = st;
     }
     e->upd_stats.bytes_uploaded += hp.bytes_uploaded;
@@ -2613,6 +2657,45 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
     if ((src = cimg_engine_synchronize(e))) return src;
     if (rc) { e->err = chunk_error; return update_result(e, rc, nchunks, status); }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cimg_update_windows_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                               const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                               int32_t nwindows, const cimg_window* w, const void* d_src, void* d_new, const int64_t* new_off,
+                               int32_t* new_cbytes, int32_t* status)
+{
+    return update_device_call(e, p, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
+                              reinterpret_cast<const WindowSpec*>(w), d_src, d_new, new_off, new_cbytes, status);
+}
+
+int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                             const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
+                             const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
+{
+    return update_host_call(e, p, nchunks, h_comp, comp_off, comp_size, destsize, nwindows, reinterpret_cast<const WindowSpec*>(w), h_src,
+                            alloc, user, new_chunks, new_cbytes, status);
+}
+
+int cimg_update_windows_strided_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                       const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                                       int32_t nwindows, const cimg_window_strided* w, const void* d_src, void* d_new,
+                                       const int64_t* new_off, int32_t* new_cbytes, int32_t* status)
+{
+    return update_device_call(e, p, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, destsize, nwindows,
+                              reinterpret_cast<const StridedWindowSpec*>(w), d_src, d_new, new_off, new_cbytes, status);
+}
+
+int cimg_update_windows_strided_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                     const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_strided* w,
+                                     const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
+                                     int32_t* status)
+{
+    return update_host_call(e, p, nchunks, h_comp, comp_off, comp_size, destsize, nwindows, reinterpret_cast<const StridedWindowSpec*>(w),
+                            h_src, alloc, user, new_chunks, new_cbytes, status);
 }
 
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole, int64_t* bytes_uploaded)

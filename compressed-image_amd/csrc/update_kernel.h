@@ -6,6 +6,8 @@
 //                       slot of the patch buffer -- or one chunk the batch path decoded whole.  Then the window rows that meet the
 //                       unit are copied over it from the source, one window after the other in call order (a later window wins).  A
 //                       block the windows cover completely is not staged: only the source bytes are copied.
+//   cimg_update_patch_strided
+//                       the same for windows with a col_pitch (StridedPatchBlock, below): same staging, its own overlay and schedule.
 //   cimg_update_layout  one wave per spliced chunk.  Lane j takes block j: a touched block's size comes from the stream records the
 //                       encode launch left for it; an untouched block's streams are harvested from the old chunk (a negative csize
 //                       word is a run, csize == neblock raw, anything else a coded stream whose payload stays where it is).  A wave
@@ -59,6 +61,8 @@ struct PatchBlock {
     }
 
     CIMG_DEV PatchBlock(const PatchArgs& a_, uint8_t* lds, int k) : a(a_), u(uniform_unit(a_.units + k)), wb(a_.w, lds, k) {}
+    // (the unit handed in, already wave-uniform: the strided kernel keeps its units in a table of its own)
+    CIMG_DEV PatchBlock(const PatchArgs& a_, uint8_t* lds, int k, const PatchUnit& t) : a(a_), u(t), wb(a_.w, lds, k) {}
 
     CIMG_DEV void phase_a(int wave) { if (u.stage) wb.phase_a(wave); }
 
@@ -85,6 +89,7 @@ struct PatchBlock {
     }
 
     // overlay k of the unit: the rows of one window that meet it
+    // (StridedPatchBlock::overlay below keeps a copy of this row loop with tid0 and the stride as parameters: change them together)
     CIMG_DEV void overlay(int wave, int k)
     {
         const WindowItem it = WindowBlock::uniform_item(a.items + u.item0 + k);
@@ -113,6 +118,115 @@ struct PatchBlock {
                                 const int64_t q = q0 + i;
                                 if (q >= 0 && q < n) dst[q] = src[q];
                             }
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// ---- strided patch: cimg_update_patch_strided -------------------------------------------------------------------------------------
+// The patch kernel of the strided write calls.  Units are staged exactly as above (PatchBlock::phase_a and phase_base, every
+// staging mode theirs); only the overlay differs: element c of window row r goes to plane byte row0 + r * rpitch + c * cpitch.  For
+// every row that meets the unit only the elements with a byte inside it are visited (c_lo .. c_hi, from the unit's place in the
+// plane), one lane an element, so the work follows the samples in the unit and not the row's width.  An element that straddles the
+// unit's end is written byte by byte by the units that hold its bytes.  Items with cpitch == typesize are dense rows and are copied in
+// dword units as PatchBlock::overlay copies them.  The host decides each unit's schedule (update_plan.h: items_disjoint): ordered,
+// item after item with a barrier between (a later window wins); or disjoint, the items dealt round-robin over the four waves, each
+// writing its item alone with 64 lanes and no barrier, as cimg_decode_window_grouped reads.
+struct StridedPatchUnit {
+    PatchUnit u;
+    int32_t disjoint;     // 1: no two items of the unit write a common byte
+    int32_t pad_;
+};
+
+struct StridedPatchArgs {
+    PatchArgs p;                      // (p.units and p.items unused)
+    const StridedPatchUnit* units;
+    const StridedWindowItem* items;   // overlays, in call order inside a unit
+};
+
+struct StridedPatchBlock {
+    const StridedPatchArgs& a;
+    PatchBlock pb;
+    int disjoint;
+
+    CIMG_DEV StridedPatchBlock(const StridedPatchArgs& a_, uint8_t* lds, int k)
+        : a(a_), pb(a_.p, lds, k, PatchBlock::uniform_unit(&a_.units[k].u)), disjoint(uni(a_.units[k].disjoint)) {}
+
+    // overlay k of the unit by threads tid0 + lane, + stride, ...
+    CIMG_DEV void overlay(int k, int tid0, int stride)
+    {
+        const StridedWindowItem* ip = a.items + pb.u.item0 + k;
+        const WindowItem it = WindowBlock::uniform_item(ip);
+        const int64_t cpitch = uni64(ip->cpitch);
+        const int ts = uni(ip->ts);
+        const int64_t len = pb.u.len;
+        uint8_t* const unit = a.p.dst + pb.u.dst_off;
+        // dense rows: a copy of PatchBlock::overlay's row loop with tid0 and the stride as parameters (that kernel must not change
+        // here; keep the two in step by hand until both can share one helper)
+        if (cpitch == ts) {
+            for (int r = it.r0; r < it.r1; r++) {
+                const int64_t rs = it.row0 + (int64_t)r * it.rpitch, re = rs + it.wbytes;
+                const int64_t s = rs > it.p0 ? rs : it.p0;
+                const int64_t e = re < it.p0 + len ? re : it.p0 + len;
+                if (s >= e) continue;
+                const uint8_t* src = a.p.src + it.out_off + (int64_t)r * it.out_pitch + (s - rs);
+                uint8_t* dst = unit + (s - it.p0);
+                const int64_t n = e - s;
+                const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+                const int64_t units = (mis + n + 3) >> 2;
+                for (int64_t u0 = tid0; u0 < units; u0 += stride) {
+                    FOR_LANES(l) {
+                        const int64_t q0 = 4 * (u0 + l) - mis;
+                        if (u0 + l < units) {
+                            if (q0 >= 0 && q0 + 4 <= n) {
+                                const uint32_t v = (uint32_t)src[q0] | ((uint32_t)src[q0 + 1] << 8) | ((uint32_t)src[q0 + 2] << 16) |
+                                                   ((uint32_t)src[q0 + 3] << 24);
+                                *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                            } else {
+                                for (int i = 0; i < 4; i++) {
+                                    const int64_t q = q0 + i;
+                                    if (q >= 0 && q < n) dst[q] = src[q];
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            return;
+        }
+        const int64_t width = it.wbytes / ts;
+        const bool dwords = ts == 4 || ts == 8;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the unit
+            // elements c_lo .. c_hi of the row have a byte in [0, len)
+            const int64_t lo = -rel - (ts - 1), hi = len - 1 - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = lo <= 0 ? 0 : (lo + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            const int64_t base = rel + c_lo * cpitch;                          // unit offset of element c_lo (>= -(ts - 1))
+            const uint8_t* src = a.p.src + it.out_off + (int64_t)r * it.out_pitch + c_lo * ts;
+            const int64_t ne = c_hi + 1 - c_lo;
+            for (int64_t e0 = tid0; e0 < ne; e0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t e = e0 + l;
+                    if (e < ne) {
+                        const int64_t at = base + e * cpitch;                  // the element's bytes: [at, at + ts) of the unit
+                        const uint8_t* s = src + e * ts;
+                        uint8_t* d = unit + at;
+                        if (dwords && at >= 0 && at + ts <= len && ((uintptr_t)d & 3) == 0) {
+                            for (int i = 0; i < ts; i += 4) {
+                                const uint32_t v = (uint32_t)s[i] | ((uint32_t)s[i + 1] << 8) | ((uint32_t)s[i + 2] << 16) |
+                                                   ((uint32_t)s[i + 3] << 24);
+                                *reinterpret_cast<uint32_t*>(d + i) = v;
+                            }
+                        } else {
+                            for (int i = 0; i < ts; i++)
+                                if (at + i >= 0 && at + i < len) d[i] = s[i];
                         }
                     }
                 }

@@ -1,7 +1,8 @@
 // update_plan.h -- window writes: validation, routing and the order in which an update call runs.  Pure C++, shared by the engine
 // (engine.hip) and the emulator tests (tests/emu/window_write_emu.cpp, tests/emu/mock_window_write.cpp), like window_plan.h.
 //
-// Windows are cimg_window / WindowSpec, with out_off / out_pitch locating the SOURCE rows.  Every touched chunk's new bytes are what a
+// Windows are cimg_window / WindowSpec -- or, for the strided calls, cimg_window_strided / StridedWindowSpec: run_update and
+// plan_update_host are templates over the window type, as run_windows and plan_windows_host are -- with out_off / out_pitch locating the SOURCE rows.  Every touched chunk's new bytes are what a
 // from-scratch compress of its decoded pixels with the windows written in gives.  Two routes:
 //   splice  regular lz4 / lz4hc / blosclz chunks whose blocks the window kernel can stage and the batch encoder can take: the touched
 //           blocks are staged and patched (cimg_update_patch), re-encoded as one-block pseudo-chunks (the batch encode launch, no
@@ -64,6 +65,9 @@ inline bool items_cover(const std::vector<WindowItem>& items, size_t first, size
 //   int compress(p, list, raw_off, nbytes, destsize, new_off, cbytes)
 //                                                          -- the batch compress of chunks lying in the whole buffer (with trunc-prec
 //                                                             in p: the pass over those chunks, then the compress)
+//   int patch_strided(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
+//                                                          -- the same for a call over StridedWindowSpec: cimg_update_patch_strided over
+//                                                             StridedPatchUnit and StridedWindowItem (only such calls need it)
 //   int trunc(typesize, mask64, off, len)    [optional]    -- trunc-prec in place over pieces of the patch buffer, in front of encode().
 //                                                             An env without it cannot truncate: parameters that name the filter are
 //                                                             ERR_INVALID_PARAM there, as they were before the filter was built.
@@ -72,11 +76,83 @@ template <class Env>
 struct env_has_trunc<Env, std::void_t<decltype(std::declval<Env&>().trunc(0, uint64_t(0), std::declval<const std::vector<int64_t>&>(),
                                                                           std::declval<const std::vector<int32_t>&>()))>> : std::true_type {};
 
+// ---- strided windows (StridedWindowSpec: cimg_update_windows_strided_*) -----------------------------------------------------------
+// Coverage: a unit needs no staging only if its DENSE items (cpitch == typesize: col_pitch 1, or one element a row) cover it --
+// items_cover over those; strided items never prove coverage.
+inline bool items_cover(const std::vector<StridedWindowItem>& items, size_t first, size_t count, int64_t len)
+{
+    int64_t written = 0;                                             // (most units are not covered: no table for them)
+    for (size_t k = first; k < first + count; k++) if (items[k].cpitch == items[k].ts) written += (int64_t)(items[k].r1 - items[k].r0) * items[k].wbytes;
+    if (written < len) return false;
+    std::vector<WindowItem> dense;
+    for (size_t k = first; k < first + count; k++) if (items[k].cpitch == items[k].ts) dense.push_back(items[k]);
+    return items_cover(dense, 0, dense.size(), len);
+}
+
+// Schedule: true when no two items of the unit write a common byte, so that the kernel may hand them to its four waves with no
+// barrier between them.  Conservative: every row of every item gives one byte interval inside the unit, from the first to the last
+// sampled byte it holds there (the bytes between samples count as written); the intervals are sorted and ANY intersection makes
+// the unit ordered.  (Rows of one item never intersect: row_pitch >= span.)  Above UPDATE_DISJOINT_MAX_ROWS intervals a unit the
+// proof gives up and says "ordered": 4096 keeps the sort of a unit in the tens of microseconds, and a unit with more rows than
+// that has work enough for 256 threads an item.
+enum : int { UPDATE_DISJOINT_MAX_ROWS = 4096 };
+inline bool items_disjoint(const std::vector<WindowItem>&, size_t, size_t, int64_t, std::vector<std::pair<int64_t, int64_t>>*) { return false; }
+// (ivp: the caller's table, so that the units of a call share one allocation)
+inline bool items_disjoint(const std::vector<StridedWindowItem>& items, size_t first, size_t count, int64_t len,
+                           std::vector<std::pair<int64_t, int64_t>>* ivp)
+{
+    if (count < 2) return false;                                 // (one item: the schedule does not matter)
+    int64_t rows = 0;
+    for (size_t k = first; k < first + count; k++) rows += items[k].r1 - items[k].r0;
+    if (rows > UPDATE_DISJOINT_MAX_ROWS) return false;
+    std::vector<std::pair<int64_t, int64_t>>& iv = *ivp;
+    iv.clear();
+    for (size_t k = first; k < first + count; k++) {
+        const StridedWindowItem& t = items[k];
+        const int64_t width = t.wbytes / t.ts;
+        for (int r = t.r0; r < t.r1; r++) {
+            const int64_t rel = t.row0 + (int64_t)r * t.rpitch - t.p0;
+            const int64_t lo = -rel - (t.ts - 1), hi = len - 1 - rel;
+            if (hi < 0) continue;
+            if (width == 1) {                                    // (a pixel: no division)
+                if (lo <= 0) iv.push_back({std::max<int64_t>(rel, 0), std::min(rel + t.ts, len)});
+                continue;
+            }
+            const int64_t c_lo = lo <= 0 ? 0 : (lo + t.cpitch - 1) / t.cpitch;
+            const int64_t c_hi = std::min(hi / t.cpitch, width - 1);
+            if (c_lo > c_hi) continue;
+            iv.push_back({std::max<int64_t>(rel + c_lo * t.cpitch, 0), std::min(rel + c_hi * t.cpitch + t.ts, len)});
+        }
+    }
+    std::sort(iv.begin(), iv.end());
+    for (size_t k = 1; k < iv.size(); k++) if (iv[k].first < iv[k - 1].second) return false;
+    return true;
+}
+
+// the patch launch of a call: cimg_update_patch for plain windows, cimg_update_patch_strided (units with their schedule) for strided
 template <class Env>
+int patch_units(Env& env, const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<uint8_t>&,
+                const std::vector<WindowItem>& stage, const std::vector<WindowItem>& items, int to_whole, int64_t patch_bytes, int32_t* status)
+{
+    return env.patch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
+}
+template <class Env>
+int patch_units(Env& env, const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<uint8_t>& disjoint,
+                const std::vector<WindowItem>& stage, const std::vector<StridedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                int32_t* status)
+{
+    std::vector<StridedPatchUnit> su(units.size());
+    for (size_t k = 0; k < units.size(); k++) su[k] = StridedPatchUnit{units[k], disjoint[k], 0};
+    return env.patch_strided(descs, lds_bytes, su, stage, items, to_whole, patch_bytes, status);
+}
+
+template <class Env, class Spec>
 int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
-               const int32_t* blocksize, const int32_t* destsize, int nwindows, const WindowSpec* w, const int64_t* new_off,
+               const int32_t* blocksize, const int32_t* destsize, int nwindows, const Spec* w, const int64_t* new_off,
                int32_t* new_cbytes, int32_t* status, UpdateStats* stats)
 {
+    using Plan = typename PlanOf<Spec>::type;
+    using Item = typename decltype(Plan::items)::value_type;
     *stats = UpdateStats{};
     if (nchunks < 0 || nwindows < 0) return ERR_INVALID_PARAM;
     for (int i = 0; i < nchunks; i++) { status[i] = 0; new_cbytes[i] = 0; }
@@ -96,8 +172,11 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
     const int ts = p.typesize > 255 ? 1 : p.typesize;
     for (int i = 0; i < nchunks; i++) if (destsize[i] < HEADER_LEN) return ERR_INVALID_PARAM;
     const std::vector<int32_t> tsv((size_t)nchunks, ts);
-    WindowPlan plan;
+    Plan plan;
     if (plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, nullptr, &plan) < 0) return ERR_INVALID_PARAM;
+    // (the tables index items and units with int32.  The limit is theoretical: 2^31 items of ~100 bytes are listed before it is
+    // looked at, so a call that large runs out of memory first; it is here so that no count is ever narrowed silently)
+    if (plan.items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
 
     // the touched chunks' headers: damage is the chunk's status, disagreement with p the call's error
     std::vector<uint8_t> route((size_t)nchunks, ROUTE_NONE);
@@ -142,22 +221,40 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
     // ---- splice route ----
     std::vector<uint8_t> hint((size_t)nchunks, 0);
     for (int i = 0; i < nchunks; i++) hint[(size_t)i] = route[(size_t)i] != ROUTE_SPLICE;
-    if (plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, hint.data(), &plan) < 0) return ERR_INVALID_PARAM;
+    // (the plan above is this one already unless some touched chunk leaves the splice route.  The hint would change plan.whole[] for
+    // chunks no window meets only, and those have no items; lds_bytes, descs and items depend on touched chunks alone.  This holds
+    // only because NOTHING READS plan.whole[] PAST THIS POINT: code that starts to must re-plan here whenever the hint is not all zero
+    // over the chunks it looks at, or the plain calls change without a sign.)
+    bool replan = false;
+    for (const int i : tl) replan = replan || route[(size_t)i] != ROUTE_SPLICE;
+    if (replan && plan_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w, hint.data(), &plan) < 0) return ERR_INVALID_PARAM;
     for (int i = 0; i < nchunks; i++) {
         plan.descs[(size_t)i].comp_off = plan.touched[(size_t)i] ? comp_off[i] : 0;
         plan.descs[(size_t)i].destsize = comp_size ? comp_size[i] : 0x7fffffff;
     }
-    std::vector<WindowItem> blk_items;
-    for (const WindowItem& t : plan.items) if (t.b >= 0 && route[(size_t)t.chunk] == ROUTE_SPLICE) blk_items.push_back(t);
-    std::stable_sort(blk_items.begin(), blk_items.end(), [](const WindowItem& x, const WindowItem& y) { return x.b < y.b; });
+    // the spliced chunks' items by block, call order kept inside a block: (block, index) keys are sorted and the items moved once
+    std::vector<Item> blk_items;
+    {
+        std::vector<uint64_t> keys;
+        keys.reserve(plan.items.size());
+        for (size_t k = 0; k < plan.items.size(); k++) {
+            const Item& t = plan.items[k];
+            if (t.b >= 0 && route[(size_t)t.chunk] == ROUTE_SPLICE) keys.push_back(((uint64_t)(uint32_t)t.b << 32) | (uint64_t)k);
+        }
+        std::sort(keys.begin(), keys.end());
+        blk_items.reserve(keys.size());
+        for (const uint64_t key : keys) blk_items.push_back(plan.items[(size_t)(key & 0xffffffffu)]);
+    }
+    std::vector<std::pair<int64_t, int64_t>> iv;     // items_disjoint's table, one for the call
     std::vector<PatchUnit> units;
+    std::vector<uint8_t> disjoint;                   // per unit: no two of its items write a common byte (strided calls)
     std::vector<WindowItem> stage;
     std::vector<int32_t> unit_b;
     int64_t patch_bytes = 0;
     for (size_t k = 0; k < blk_items.size();) {
         size_t e = k;
         while (e < blk_items.size() && blk_items[e].b == blk_items[k].b) e++;
-        const WindowItem& t = blk_items[k];
+        const Item& t = blk_items[k];
         const ChunkDesc& d = plan.descs[(size_t)t.chunk];
         const int j = t.b - d.blk0;
         const int64_t blen = (j == d.nblocks - 1 && d.leftover) ? d.leftover : d.blocksize;
@@ -170,10 +267,11 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
         WindowItem s{};
         s.chunk = t.chunk; s.b = u.stage ? t.b : -1;
         units.push_back(u); stage.push_back(s); unit_b.push_back(t.b);
+        disjoint.push_back(items_disjoint(blk_items, k, e - k, blen, &iv) ? 1 : 0);
         k = e;
     }
     if (!units.empty()) {
-        int rc = env.patch(plan.descs, plan.lds_bytes, units, stage, blk_items, 0, patch_bytes, status);
+        int rc = patch_units(env, plan.descs, plan.lds_bytes, units, disjoint, stage, blk_items, 0, patch_bytes, status);
         if (rc < 0) return rc;
         for (int i = 0; i < nchunks; i++) if (route[(size_t)i] == ROUTE_SPLICE && status[i] != 0) route[(size_t)i] = ROUTE_FAILED;
         // one-block pseudo-chunks with the parent's geometry (a short last block stays unsplit), no assembly
@@ -272,21 +370,23 @@ int run_update(Env& env, const HostCParams& p, int nchunks, const int64_t* comp_
             at[(size_t)wl[k]] = woff[k];
             ok.push_back(wl[k]); okoff.push_back(woff[k]);
         }
-        std::vector<WindowItem> items;
+        std::vector<Item> items;
         std::vector<PatchUnit> wunits;
+        std::vector<uint8_t> wdisjoint;
         std::vector<WindowItem> wstage;
         for (int i : ok) {
             PatchUnit u{};
             u.chunk = i; u.stage = 0; u.item0 = (int32_t)items.size();
             u.len = nbytes[i]; u.dst_off = at[(size_t)i];
-            for (const WindowItem& t : plan.items) if (t.b < 0 && t.chunk == i) items.push_back(t);
+            for (const Item& t : plan.items) if (t.b < 0 && t.chunk == i) items.push_back(t);
             u.nitems = (int32_t)items.size() - u.item0;
+            wdisjoint.push_back(items_disjoint(items, (size_t)u.item0, (size_t)u.nitems, u.len, &iv) ? 1 : 0);
             WindowItem s{};
             s.chunk = i; s.b = -1;
             wunits.push_back(u); wstage.push_back(s);
         }
         if (!ok.empty()) {
-            if ((rc = env.patch(plan.descs, 0, wunits, wstage, items, 1, wtotal, status)) < 0) return rc;
+            if ((rc = patch_units(env, plan.descs, 0, wunits, wdisjoint, wstage, items, 1, wtotal, status)) < 0) return rc;
             std::vector<int32_t> nb, ds, cb(ok.size(), 0);
             std::vector<int64_t> no;
             for (int i : ok) { nb.push_back(nbytes[i]); ds.push_back(destsize[i]); no.push_back(new_off[i]); }
@@ -320,16 +420,19 @@ struct UpdateHostPlan : HostCallPlan {
 // cimg_update_windows_host: only the touched chunks go up, and a header that claims more than the buffer holds is the chunk's
 // own error, found by run_update (hence `up`: what is there to copy, a header at least).  ERR_INVALID_PARAM with bad_window < 0:
 // the typesize or a window was refused.
+// (dw: the packed windows -- hp->dw, or the strided call's list)
+template <class Spec>
 inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size,
-                            const int32_t* destsize, int nwindows, const WindowSpec* w, int32_t* status, UpdateHostPlan* hp)
+                            const int32_t* destsize, int nwindows, const Spec* w, int32_t* status, UpdateHostPlan* hp, std::vector<Spec>* dw)
 {
     const int rc = read_named_headers(nchunks, comp, comp_off, comp_size, nwindows, w, hp);
     if (hp->short_chunk >= 0) status[hp->short_chunk] = rc;
     if (rc < 0) return rc;
     if (typesize <= 0) return ERR_INVALID_PARAM;
     const std::vector<int32_t> tsv((size_t)nchunks, typesize > 255 ? 1 : typesize);
-    WindowPlan plan;
+    typename PlanOf<Spec>::type plan;
     if (plan_windows(nchunks, hp->nbytes.data(), hp->blocksize.data(), tsv.data(), nwindows, w, nullptr, &plan) < 0) return ERR_INVALID_PARAM;
+    if (plan.items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
     hp->held.assign((size_t)nchunks, 0);
     hp->new_off.assign((size_t)nchunks, 0);
     for (int i = 0; i < nchunks; i++) {
@@ -341,10 +444,15 @@ inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, cons
         hp->new_used = hp->new_total + std::max(destsize[i], 0);
         hp->new_total += ((int64_t)std::max(destsize[i], 0) + 63) & ~63ll;
     }
-    pack_rows(nwindows, w, tsv.data(), hp);
+    pack_rows(nwindows, w, tsv.data(), hp, dw);
     hp->bytes_uploaded = hp->comp_bytes_uploaded;
     for (const int64_t b : hp->wbytes) hp->bytes_uploaded += b;
     return 0;
+}
+inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size,
+                            const int32_t* destsize, int nwindows, const WindowSpec* w, int32_t* status, UpdateHostPlan* hp)
+{
+    return plan_update_host(typesize, nchunks, comp, comp_off, comp_size, destsize, nwindows, w, status, hp, &hp->dw);
 }
 
 }  // namespace cimg

@@ -248,6 +248,7 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
                     t.cpitch = cpitch; t.ts = ts;
                     plan->items.push_back(t);
                 }
+                if (c + 1 >= s.width) break;                                         // (the row's last sample: nothing to skip to)
                 // the first sample with a byte at or past the end of what was just listed
                 int64_t edge = whole ? ce : cs + (int64_t)(jl + 1) * d.blocksize;
                 if (edge > ce) edge = ce;

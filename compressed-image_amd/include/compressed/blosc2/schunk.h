@@ -346,6 +346,90 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					}
 				}
 
+				/// One subsampled rectangle of set_regions: nx x ny samples, sx / sy apart, from (x, y); its data (nx elements a row) starts
+				/// at element src_off of the call's source.
+				struct strided_rect { size_t x, y, nx, ny, sx, sy, src_off; };
+
+				/// Batch building block of set_regions: the rectangles, in order, written into this table seen as rows of `row_len`
+				/// elements.  Every run of compressed chunks that holds a sample becomes a plane of `job` with strided windows in region
+				/// order (a later region wins); a lazy chunk that holds a sample is filled with its value and patched on the host, with
+				/// stride and in region order.  (Template over the job so that only callers refer to the strided entry point's types.)
+				template <typename Job>
+				void plan_regions_write(const T* src, const std::vector<strided_rect>& rects, size_t row_len, Job& job, region_write& rw) const
+				{
+					rw.job_first = job.chunks.size();
+					size_t cs = 0;
+					for (size_t i = 0; i < m_Chunks.size();)
+					{
+						const bool lazy = m_Chunks[i].is_lazy();
+						size_t j = i, ce = cs;
+						while (j < m_Chunks.size() && m_Chunks[j].is_lazy() == lazy) { ce += m_Chunks[j].num_elements; ++j; if (lazy) break; }
+						const int32_t first = static_cast<int32_t>(job.chunks.size());
+						std::vector<T> px;
+						bool met = false;
+						std::vector<cimg_window_strided> wins;
+						std::vector<const std::byte*> srcs;
+						for (const strided_rect& q : rects)
+						{
+							if (q.nx == 0 || q.ny == 0 || ce == cs) continue;
+							const size_t base = q.y * row_len + q.x, stride = q.sy * row_len, reach = (q.nx - 1) * q.sx;   // a row's samples: [rs, rs + reach]
+							const size_t r_lo = cs <= base + reach ? 0 : (cs - base - reach + stride - 1) / stride;
+							const size_t r_hi = base >= ce ? 0 : std::min(q.ny, (ce - 1 - base) / stride + 1);
+							// rows r_lo .. r_hi - 1 may hold samples of the run; only the first and the last of them can be cut by its ends
+							auto cols = [&](size_t r, size_t& c_lo, size_t& c_hi) {
+								const size_t rs = base + r * stride;
+								c_lo = rs >= cs ? 0 : (cs - rs + q.sx - 1) / q.sx;
+								c_hi = std::min(q.nx - 1, (ce - 1 - rs) / q.sx);
+								return c_lo <= c_hi && c_lo < q.nx;
+							};
+							auto emit = [&](size_t ra, size_t rb, size_t c_lo, size_t c_hi) {
+								met = true;
+								if (lazy)
+								{
+									if (px.empty()) px.assign(m_Chunks[i].num_elements, std::get<T>(m_Chunks[i].value));
+									for (size_t r = ra; r < rb; ++r)
+										for (size_t c = c_lo; c <= c_hi; ++c) px[base + r * stride + c * q.sx - cs] = src[q.src_off + r * q.nx + c];
+									return;
+								}
+								cimg_window_strided win{};
+								win.chunk_first = first;
+								win.chunk_count = static_cast<int32_t>(j - i);
+								win.origin = static_cast<int64_t>(base + ra * stride + c_lo * q.sx - cs);
+								win.row_pitch = static_cast<int64_t>(stride);
+								win.col_pitch = static_cast<int64_t>(q.sx);
+								win.width = static_cast<int32_t>(c_hi - c_lo + 1);
+								win.height = static_cast<int32_t>(rb - ra);
+								win.out_pitch = static_cast<int64_t>(q.nx * sizeof(T));
+								wins.push_back(win);
+								srcs.push_back(reinterpret_cast<const std::byte*>(src + q.src_off + ra * q.nx + c_lo));
+							};
+							size_t ra = r_lo, rb = r_hi, c_lo = 0, c_hi = 0;
+							if (ra < rb) { if (cols(ra, c_lo, c_hi)) { if (c_lo > 0 || c_hi < q.nx - 1 || rb - ra == 1) { emit(ra, ra + 1, c_lo, c_hi); ++ra; } } else ++ra; }
+							if (ra < rb) { if (cols(rb - 1, c_lo, c_hi)) { if (c_lo > 0 || c_hi < q.nx - 1) { emit(rb - 1, rb, c_lo, c_hi); --rb; } } else --rb; }
+							if (ra < rb) emit(ra, rb, 0, q.nx - 1);
+						}
+						if (met && lazy)
+						{
+							rw.lazy.push_back(i);
+							rw.lazy_pixels.push_back(std::move(px));
+						}
+						else if (met)
+						{
+							for (size_t k = i; k < j; ++k)
+							{
+								job.chunks.push_back(m_Chunks[k].bytes().data());
+								job.held.push_back(m_Chunks[k].bytes().size());
+								job.destsize.push_back(static_cast<int32_t>(min_compressed_size(m_ChunkSize)));
+								rw.compressed.push_back(k);
+							}
+							job.windows.insert(job.windows.end(), wins.begin(), wins.end());
+							job.srcs.insert(job.srcs.end(), srcs.begin(), srcs.end());
+						}
+						cs = ce;
+						i = j;
+					}
+				}
+
 				/// After the engine call succeeded: take this table's new chunks out of the call's results and compress the patched lazy
 				/// chunks (one batch call).  May throw; nothing of the table has changed yet.
 				void prepare_region_write(context_raw_ptr cctx, region_write& rw, std::vector<std::vector<std::byte>>& made) const

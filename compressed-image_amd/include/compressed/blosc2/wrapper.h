@@ -500,6 +500,56 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				return out;
 			}
 
+			// The same over cimg_window_strided (cimg_update_windows_strided_host): set_region with steps, set_regions.  A template, so
+			// that only code that instantiates it refers to the strided entry point.
+			struct update_job_strided
+			{
+				std::vector<const std::byte*> chunks;
+				std::vector<size_t> held;
+				std::vector<int32_t> destsize;
+				std::vector<cimg_window_strided> windows;
+				std::vector<const std::byte*> srcs;
+				cimg_cparams cparams{};
+			};
+
+			template <typename Job = update_job_strided>
+			inline std::vector<std::vector<std::byte>> update_windows_strided(Job& job)
+			{
+				const size_t n = job.chunks.size();
+				std::vector<std::vector<std::byte>> out(n);
+				if (job.windows.empty()) return out;
+				if (job.windows.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("set_regions: too many windows for one call");
+				const std::byte* cbase = job.chunks[0];
+				for (const auto* c : job.chunks) if (c < cbase) cbase = c;
+				const std::byte* sbase = job.srcs[0];
+				for (const auto* s : job.srcs) if (s < sbase) sbase = s;
+				std::vector<int64_t> comp_off(n);
+				std::vector<int32_t> held(n), status(n), ncb(n);
+				std::vector<void*> made(n, nullptr);
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (job.held[i] > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+						throw std::out_of_range(detail::text("Blosc2 chunk size may not exceed numeric limit of int32_t, got ", job.held[i]));
+					comp_off[i] = job.chunks[i] - cbase;
+					held[i] = static_cast<int32_t>(job.held[i]);
+				}
+				for (size_t k = 0; k < job.windows.size(); ++k) job.windows[k].out_off = job.srcs[k] - sbase;
+				const auto alloc = [](void*, size_t bytes) -> void* { return std::malloc(bytes ? bytes : 1); };
+				const int rc = cimg_update_windows_strided_host(engine(), &job.cparams, static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+					job.destsize.data(), static_cast<int32_t>(job.windows.size()), job.windows.data(), sbase, alloc, nullptr, made.data(),
+					ncb.data(), status.data());
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (!made[i]) continue;
+					const auto* b = static_cast<const std::byte*>(made[i]);
+					out[i].assign(b, b + ncb[i]);
+					std::free(made[i]);
+				}
+				if (rc < 0)
+					throw std::runtime_error(detail::text("Error code ", rc, " while writing regions into blosc2 chunks (", cimg_last_error(engine()), ")"));
+				return out;
+			}
+
 			// one chunk -> its pixels; chunk_bytes = what the chunk buffer really holds (0: unknown, trust the header)
 			struct target { const std::byte* chunk; std::byte* out; size_t capacity; size_t chunk_bytes = 0; };
 

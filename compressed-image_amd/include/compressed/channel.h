@@ -250,6 +250,51 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				s.commit_region_write(rw);
 			}, *m_Schunk);
 		}
+		/// Write `data` over every step_y-th row and every step_x-th element of the rectangle: data holds ceil(height / step_y) rows of
+		/// ceil(width / step_x) elements, what get_region with the same steps returns.  Only the blocks that hold a written element are
+		/// decoded and re-encoded.  A step of 0 throws std::invalid_argument.
+		void set_region(std::span<const T> data, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), data);
+		}
+		/// Many rectangles in ONE engine call.  The data lies back to back in region order, each region row-major in its subsampled
+		/// shape -- the layout get_regions returns.  Later regions win where two overlap.  Every region is checked before anything
+		/// runs; an empty list does nothing; lazy chunks a region meets become real; nothing changes unless the whole call succeeds.
+		void set_regions(std::span<const region> regions, std::span<const T> data)
+		{
+			const size_t total = check_regions(regions);
+			if (data.size() != total)
+				throw std::invalid_argument(detail::text("set_regions: span holds ", data.size(), " elements, the regions have ", total));
+			if (total == 0) return;
+			require();
+			require_encoder();
+			blosc2::batch::update_job_strided job;
+			region_cparams(job.cparams);
+			std::visit([&](auto& s) {
+				using table_t = std::decay_t<decltype(s)>;
+				typename table_t::region_write rw;
+				s.plan_regions_write(data.data(), region_rects<table_t>(regions, 0, 1), m_Width, job, rw);
+				auto made = blosc2::batch::update_windows_strided(job);
+				s.prepare_region_write(m_CompressionContext.get(), rw, made);
+				s.commit_region_write(rw);
+			}, *m_Schunk);
+		}
+		/// The regions as the chunk table takes them; region k's data starts where `channels` channels of the regions before it end,
+		/// plus `channel` pieces of its own (an image's data is region-major, channel-minor).
+		template <typename Table>
+		static std::vector<typename Table::strided_rect> region_rects(std::span<const region> regions, size_t channel, size_t channels)
+		{
+			std::vector<typename Table::strided_rect> out;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				const size_t n = r.out_elems();
+				if (n) out.push_back({ r.x, r.y, (r.width + r.step_x - 1) / r.step_x, (r.height + r.step_y - 1) / r.step_y, r.step_x, r.step_y, at + channel * n });
+				at += channels * n;
+			}
+			return out;
+		}
 		/// The codec parameters of this channel's compression context (what set_region hands the engine).
 		void region_cparams(cimg_cparams& out) const
 		{

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <memory>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "channel.h"
@@ -407,7 +408,36 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			if (width == 0 || height == 0) return;
 			detail::device_range(m_Store->engine, d_src, width * height * sizeof(T), "set_region");
 			const cimg_window w = region_window(x, y, width, height, 0);
-			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, { w }, d_src);
+			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, std::vector<cimg_window>{ w }, d_src);
+		}
+
+		/// Write `d_src` over every step_y-th row and every step_x-th element of the rectangle: d_src holds ceil(height / step_y) rows of
+		/// ceil(width / step_x) elements, the layout get_region with the same steps returns.  Only the blocks that hold a written
+		/// element are decoded and re-encoded.  A step of 0 throws std::invalid_argument.
+		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src);
+		}
+		/// Many rectangles in ONE engine call and one repack of the store.  The data lies back to back in region order, each region
+		/// row-major in its subsampled shape -- the layout get_regions returns.  Later regions win where two overlap.  Every region is
+		/// checked before anything runs; an empty list does nothing; nothing changes unless the whole call succeeds.
+		void set_regions(std::span<const region> regions, const T* d_src)
+		{
+			if (m_ReadOnly) throw std::runtime_error("set_regions: this device_channel shares the store of a device_image and is read-only; use device_image::set_regions");
+			const size_t total = check_regions(regions);
+			require();
+			std::vector<cimg_window_strided> w;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				if (r.width && r.height) w.push_back(region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, at * sizeof(T)));
+				at += r.out_elems();
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("set_regions: too many regions for one call");
+			detail::device_range(m_Store->engine, d_src, total * sizeof(T), "set_regions");
+			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, w, d_src);
 		}
 
 		void check_region(size_t x, size_t y, size_t width, size_t height) const
@@ -462,9 +492,13 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 
 		/// Apply window writes to a store: the update's output goes to a scratch allocation, then ONE pack launch gathers the new
 		/// store -- untouched chunks from the old one, touched ones from the scratch.  The old store is left as it was.
+		/// (Window: cimg_window through cimg_update_windows_device, cimg_window_strided through cimg_update_windows_strided_device --
+		/// only the strided instantiation refers to the strided entry point)
+		template <typename Window>
 		static std::shared_ptr<detail::device_store> updated_store(const detail::device_store& old, const cimg_cparams& cp, size_t nominal_chunk_bytes,
-			const std::vector<cimg_window>& windows, const void* d_src)
+			const std::vector<Window>& windows, const void* d_src)
 		{
+			constexpr bool strided = std::is_same_v<Window, cimg_window_strided>;
 			cimg_engine* e = old.engine;
 			const size_t n = old.num_chunks();
 			const int32_t dest = static_cast<int32_t>(blosc2::min_compressed_size(nominal_chunk_bytes));
@@ -476,7 +510,9 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			{
 				if (w.width <= 0 || w.height <= 0) continue;
 				const int64_t lo = w.origin * static_cast<int64_t>(sizeof(T));
-				const int64_t hi = (w.origin + (w.height - 1) * w.row_pitch + w.width) * static_cast<int64_t>(sizeof(T));
+				int64_t span = w.width;
+				if constexpr (strided) span = static_cast<int64_t>(w.width - 1) * w.col_pitch + 1;
+				const int64_t hi = (w.origin + (w.height - 1) * w.row_pitch + span) * static_cast<int64_t>(sizeof(T));
 				int64_t at = 0;
 				for (int32_t k = w.chunk_first; k < w.chunk_first + w.chunk_count; ++k)
 				{
@@ -490,9 +526,14 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			detail::device_store scratch;
 			scratch.allocate(e, scratch_bytes + 64);
 			detail::engine_lock lock(e);
-			detail::engine_call(e, cimg_update_windows_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(), old.nbytes.data(),
-				old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base, new_off.data(),
-				new_cbytes.data(), status.data()), "Writing the region");
+			if constexpr (strided)
+				detail::engine_call(e, cimg_update_windows_strided_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(),
+					old.nbytes.data(), old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base,
+					new_off.data(), new_cbytes.data(), status.data()), "Writing the regions");
+			else
+				detail::engine_call(e, cimg_update_windows_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(), old.nbytes.data(),
+					old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base, new_off.data(),
+					new_cbytes.data(), status.data()), "Writing the region");
 			auto fresh = std::make_shared<detail::device_store>();
 			fresh->nbytes = old.nbytes;
 			fresh->blocksize = old.blocksize;

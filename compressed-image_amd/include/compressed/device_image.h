@@ -242,6 +242,41 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
 		}
 
+		/// Write every step_y-th row and every step_x-th element of the rectangle of every channel: d_src holds num_channels planes of
+		/// ceil(height / step_y) x ceil(width / step_x) elements, channel-major.  A step of 0 throws std::invalid_argument.
+		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src);
+		}
+		/// Many rectangles of every channel in ONE engine call and one repack of the store.  The data is region-major, channel-minor,
+		/// each piece row-major in its subsampled shape -- the layout get_regions returns.  Later regions win where two overlap.  Every
+		/// region is checked before anything runs; an empty list does nothing; nothing changes unless the whole call succeeds.
+		void set_regions(std::span<const region> regions, const T* d_src)
+		{
+			const size_t per_channel = prototype().check_regions(regions);
+			if (m_NumChannels == 0) return;
+			std::vector<device_channel<T>> per_ch;                    // one prototype a channel, made once
+			for (size_t c = 0; c < m_NumChannels; ++c)
+			{
+				per_ch.push_back(prototype());
+				per_ch.back().m_First = c * chunks_per_channel();
+				per_ch.back().m_Count = chunks_per_channel();
+			}
+			std::vector<cimg_window_strided> w;
+			size_t at = 0;
+			for (const region& r : regions)
+				for (size_t c = 0; c < m_NumChannels; ++c)
+				{
+					if (r.width && r.height) w.push_back(per_ch[c].region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, at * sizeof(T)));
+					at += r.out_elems();
+				}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("set_regions: too many regions for one call");
+			detail::device_range(m_Store->engine, d_src, per_channel * m_NumChannels * sizeof(T), "set_regions");
+			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
+		}
+
 		size_t width() const noexcept { return m_Width; }
 		size_t height() const noexcept { return m_Height; }
 		size_t num_channels() const noexcept { return m_NumChannels; }

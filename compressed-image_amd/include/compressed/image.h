@@ -302,6 +302,69 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				}, m_Channels[ch].chunks());
 		}
 
+		/// Write one span per channel over every step_y-th row and step_x-th element of the rectangle of every channel; each span holds
+		/// ceil(height / step_y) x ceil(width / step_x) elements.  A step of 0 throws std::invalid_argument.
+		void set_region(const std::vector<std::span<const T>>& data, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y)
+		{
+			if (data.size() != m_Channels.size())
+				throw std::invalid_argument(detail::text("set_region: got ", data.size(), " spans for ", m_Channels.size(), " channels"));
+			const region r{ x, y, width, height, step_x, step_y };
+			for (const auto& ch : m_Channels) ch.check_regions(std::span<const region>(&r, 1));
+			std::vector<T> all;
+			all.reserve(data.size() * r.out_elems());
+			for (size_t ch = 0; ch < data.size(); ++ch)
+			{
+				if (data[ch].size() != r.out_elems())
+					throw std::invalid_argument(detail::text("set_region: span ", ch, " holds ", data[ch].size(), " elements, the subsampled region has ", r.out_elems()));
+				all.insert(all.end(), data[ch].begin(), data[ch].end());
+			}
+			set_regions(std::span<const region>(&r, 1), std::span<const T>(all));
+		}
+		/// Many rectangles of every channel: the data is region-major, channel-minor, each piece row-major in its subsampled shape --
+		/// the layout get_regions returns.  One engine call for all channels that share their codec parameters; later regions win;
+		/// every region is checked before anything runs; an empty list does nothing; nothing changes unless the whole call succeeds.
+		void set_regions(std::span<const region> regions, std::span<const T> data)
+		{
+			size_t total = 0;
+			for (const auto& ch : m_Channels) total += ch.check_regions(regions);
+			if (data.size() != total)
+				throw std::invalid_argument(detail::text("set_regions: span holds ", data.size(), " elements, the regions have ", total));
+			if (total == 0) return;
+			std::vector<blosc2::batch::update_job_strided> jobs;
+			std::vector<size_t> job_of(m_Channels.size());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				cimg_cparams c{};
+				m_Channels[ch].region_cparams(c);
+				size_t k = 0;
+				while (k < jobs.size() && std::memcmp(&jobs[k].cparams, &c, sizeof c) != 0) ++k;
+				if (k == jobs.size()) { jobs.emplace_back(); jobs.back().cparams = c; }
+				job_of[ch] = k;
+			}
+			using table_var = std::variant<typename blosc2::schunk<T>::region_write, typename blosc2::lazy_schunk<T>::region_write>;
+			std::vector<table_var> rws;
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using table_t = std::decay_t<decltype(table)>;
+					typename table_t::region_write rw;
+					table.plan_regions_write(data.data(), compressed::channel<T>::template region_rects<table_t>(regions, ch, m_Channels.size()), m_Channels[ch].width(),
+						jobs[job_of[ch]], rw);
+					rws.emplace_back(std::move(rw));
+				}, m_Channels[ch].chunks());
+			std::vector<std::vector<std::vector<std::byte>>> made;
+			for (auto& job : jobs) made.push_back(blosc2::batch::update_windows_strided(job));
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.prepare_region_write(m_Channels[ch].compression_context(), std::get<rw_t>(rws[ch]), made[job_of[ch]]);
+				}, m_Channels[ch].chunks());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.commit_region_write(std::get<rw_t>(rws[ch]));
+				}, m_Channels[ch].chunks());
+		}
+
 		/// All channels into caller-owned memory (num_channels * height * width elements, channel-major): no
 		/// intermediate vectors, no zero fill -- what the Python binding uses to decode straight into a numpy array.
 		void decompress_into(std::span<T> out) const

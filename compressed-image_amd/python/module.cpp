@@ -96,6 +96,8 @@ namespace
 		if (step_x < 1 || step_y < 1) throw py::value_error("step_x and step_y must be >= 1");
 	}
 	inline py::ssize_t ceil_div(py::ssize_t a, py::ssize_t b) { return (a + b - 1) / b; }
+	// the rectangle side that n samples `step` apart cover: (n - 1) * step + 1 (0 for none)
+	inline size_t covered(py::ssize_t n, py::ssize_t step) { return n > 0 ? static_cast<size_t>((n - 1) * step + 1) : 0; }
 
 	// one axis of a key: `count` elements from `start`, `step` apart; an integer drops its axis
 	struct axis_pick { py::ssize_t start = 0, count = 0, step = 1; bool drop = false; };
@@ -313,14 +315,56 @@ namespace
 		}
 
 		// the (height, width) array over the rectangle at (x, y): only the blocks it meets are decoded and re-encoded
-		void set_region(py::ssize_t x, py::ssize_t y, const py::array& array)
+		// array: (h', w'), written over every step_y-th row and step_x-th element from (x, y)
+		void set_region(py::ssize_t x, py::ssize_t y, const py::array& array, py::ssize_t step_x, py::ssize_t step_y)
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			check_steps(step_x, step_y);
 			visit([&]<typename T>(compressed::channel<T>& ch) {
-				const auto [h, w] = region_shape<T>(array);
+				const auto [hs, ws] = region_shape<T>(array);
+				const size_t w = covered(static_cast<py::ssize_t>(ws), step_x), h = covered(static_cast<py::ssize_t>(hs), step_y);
 				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
 				auto [keep, px] = elements<T>(array);
-				ch.set_region(px, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				if (step_x == 1 && step_y == 1) ch.set_region(px, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				else ch.set_region(px, static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x), static_cast<size_t>(step_y));
+				return 0;
+			});
+		}
+		// arrays: (N, h', w') (pixels: (N,)), region k from (xs[k], ys[k]); later regions win
+		void set_regions(const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t step_x, py::ssize_t step_y, bool pixels)
+		{
+			const std::string what = pixels ? "set_pixels" : "set_regions";
+			check_steps(step_x, step_y);
+			if (arrays.ndim() != (pixels ? 1 : 3)) throw py::value_error(what + (pixels ? ": values must have the shape (N,)" : ": arrays must have the shape (N, height, width)"));
+			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(arrays.shape(2), step_x)),
+				pixels ? 1 : static_cast<py::ssize_t>(covered(arrays.shape(1), step_y)), step_x, step_y);
+			if (regions.size() != static_cast<size_t>(arrays.shape(0)))
+				throw py::value_error(what + ": got " + std::to_string(arrays.shape(0)) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(compressed::channel<T>& ch) {
+				if (!arrays.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				ch.check_regions(regions);
+				auto [keep, px] = elements<T>(arrays);
+				ch.set_regions(regions, px);
+				return 0;
+			});
+		}
+		// a[key] = value for the keys of __getitem__: anything numpy.broadcast_to(numpy.asarray(value), selection shape) accepts;
+		// scalars and sequences are converted to the channel's dtype, an ARRAY of another dtype is refused
+		void setitem(const py::object& key, const py::object& value)
+		{
+			visit([&]<typename T>(compressed::channel<T>& ch) {
+				const region_pick p = pick_region(key, static_cast<py::ssize_t>(ch.height()), static_cast<py::ssize_t>(ch.width()));
+				const py::module_ np = py::module_::import("numpy");
+				py::object a = value;
+				if (py::isinstance<py::array>(value))
+				{
+					if (!py::array(value).dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				}
+				else a = np.attr("asarray")(value, py::arg("dtype") = np_dtype<T>());
+				const py::array b = np.attr("ascontiguousarray")(np.attr("broadcast_to")(a, py::cast(p.shape)));
+				if (p.w > 0 && p.h > 0)
+					ch.set_region(std::span<const T>(static_cast<const T*>(b.data()), static_cast<size_t>(b.size())), static_cast<size_t>(p.x),
+						static_cast<size_t>(p.y), static_cast<size_t>(p.w), static_cast<size_t>(p.h), static_cast<size_t>(p.sx), static_cast<size_t>(p.sy));
 				return 0;
 			});
 		}
@@ -460,9 +504,10 @@ namespace
 			});
 		}
 		// one (height, width) array per channel over the rectangle at (x, y): one engine call
-		void set_region(py::ssize_t x, py::ssize_t y, const std::vector<py::array>& arrays)
+		void set_region(py::ssize_t x, py::ssize_t y, const std::vector<py::array>& arrays, py::ssize_t step_x, py::ssize_t step_y)
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			check_steps(step_x, step_y);
 			visit([&]<typename T>(const img_ptr<T>& img) {
 				if (arrays.size() != img->num_channels())
 					throw py::value_error("got " + std::to_string(arrays.size()) + " arrays for " + std::to_string(img->num_channels()) + " channels");
@@ -478,8 +523,29 @@ namespace
 					keep.push_back(k);
 					spans.push_back(px);
 				}
-				for (const auto& ch : img->channels()) ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
-				img->set_region(spans, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				const size_t cw = covered(static_cast<py::ssize_t>(w), step_x), chh = covered(static_cast<py::ssize_t>(h), step_y);
+				for (const auto& ch : img->channels()) ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), cw, chh);
+				if (step_x == 1 && step_y == 1) img->set_region(spans, static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				else img->set_region(spans, static_cast<size_t>(x), static_cast<size_t>(y), cw, chh, static_cast<size_t>(step_x), static_cast<size_t>(step_y));
+				return 0;
+			});
+		}
+		// arrays: (N, C, h', w') (pixels: (N, C)), region k from (xs[k], ys[k]) of every channel; later regions win
+		void set_regions(const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t step_x, py::ssize_t step_y, bool pixels)
+		{
+			const std::string what = pixels ? "set_pixels" : "set_regions";
+			check_steps(step_x, step_y);
+			if (arrays.ndim() != (pixels ? 2 : 4)) throw py::value_error(what + (pixels ? ": values must have the shape (N, channels)" : ": arrays must have the shape (N, channels, height, width)"));
+			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(arrays.shape(3), step_x)),
+				pixels ? 1 : static_cast<py::ssize_t>(covered(arrays.shape(2), step_y)), step_x, step_y);
+			if (regions.size() != static_cast<size_t>(arrays.shape(0)))
+				throw py::value_error(what + ": got " + std::to_string(arrays.shape(0)) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(const img_ptr<T>& img) {
+				if (!arrays.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
+				if (static_cast<size_t>(arrays.shape(1)) != img->num_channels()) throw py::value_error(what + ": the arrays' channel count does not match the image");
+				img->check_regions(regions);
+				auto [keep, px] = elements<T>(arrays);
+				img->set_regions(regions, px);
 				return 0;
 			});
 		}
@@ -695,16 +761,58 @@ namespace
 				return ret;
 			});
 		}
-		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream)
+		// array: (h', w') in device memory, written over every step_y-th row and step_x-th element from (x, y)
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y)
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			check_steps(step_x, step_y);
 			const device_view v = view_of(array, "set_region");
 			visit([&]<typename T>(compressed::device_channel<T>& ch) {
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
 				if (v.shape.size() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(v.shape.size()) + " dimensions");
-				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]));
+				const size_t w = covered(v.shape[1], step_x), h = covered(v.shape[0], step_y);
+				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
 				wait_for(stream);
-				ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[1]), static_cast<size_t>(v.shape[0]));
+				if (step_x == 1 && step_y == 1)
+					ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				else
+					ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x),
+						static_cast<size_t>(step_y));
+				return 0;
+			});
+		}
+		// arrays: (N, h', w') in device memory (pixels: (N,)), region k from (xs[k], ys[k]); later regions win
+		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
+			py::ssize_t step_y, bool pixels)
+		{
+			const char* what = pixels ? "set_pixels" : "set_regions";
+			check_steps(step_x, step_y);
+			const device_view v = view_of(arrays, what);
+			if (v.shape.size() != (pixels ? 1u : 3u)) throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N,)" : ": arrays must have the shape (N, height, width)"));
+			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[2], step_x)),
+				pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[1], step_y)), step_x, step_y);
+			if (regions.size() != static_cast<size_t>(v.shape[0]))
+				throw py::value_error(std::string(what) + ": got " + std::to_string(v.shape[0]) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				ch.check_regions(regions);
+				if (regions.empty() || v.count() == 0) return 0;
+				wait_for(stream);
+				ch.set_regions(regions, static_cast<const T*>(v.ptr));
+				return 0;
+			});
+		}
+		// a[key] = value for the keys of __getitem__: value is a device array of exactly the selection's shape and dtype
+		void setitem(const py::object& key, const py::object& value)
+		{
+			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				const region_pick p = pick_region(key, static_cast<py::ssize_t>(ch.height()), static_cast<py::ssize_t>(ch.width()));
+				const device_view v = view_of(value, "__setitem__");
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				if (v.shape != p.shape) throw py::value_error("__setitem__: the value's shape does not match the selection's shape");
+				if (p.w > 0 && p.h > 0)
+					ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(p.x), static_cast<size_t>(p.y), static_cast<size_t>(p.w),
+						static_cast<size_t>(p.h), static_cast<size_t>(p.sx), static_cast<size_t>(p.sy));
 				return 0;
 			});
 		}
@@ -824,18 +932,46 @@ namespace
 				return ret;
 			});
 		}
-		// one (C, h, w) device array over the rectangle at (x, y) of every channel
-		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream)
+		// one (C, h', w') device array over every step_y-th row and step_x-th element from (x, y) of every channel
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y)
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+			check_steps(step_x, step_y);
 			const device_view v = view_of(array, "set_region");
 			visit([&]<typename T>(const dimg_ptr<T>& img) {
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
 				if (v.shape.size() != 3 || static_cast<size_t>(v.shape[0]) != img->num_channels())
 					throw py::value_error("region arrays must have the shape (channels, height, width)");
-				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[2]), static_cast<size_t>(v.shape[1]));
+				const size_t w = covered(v.shape[2], step_x), h = covered(v.shape[1], step_y);
+				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
 				wait_for(stream);
-				img->set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(v.shape[2]), static_cast<size_t>(v.shape[1]));
+				if (step_x == 1 && step_y == 1)
+					img->set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+				else
+					img->set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x),
+						static_cast<size_t>(step_y));
+				return 0;
+			});
+		}
+		// arrays: (N, C, h', w') in device memory (pixels: (N, C)), region k from (xs[k], ys[k]) of every channel; later regions win
+		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
+			py::ssize_t step_y, bool pixels)
+		{
+			const char* what = pixels ? "set_pixels" : "set_regions";
+			check_steps(step_x, step_y);
+			const device_view v = view_of(arrays, what);
+			if (v.shape.size() != (pixels ? 2u : 4u)) throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N, channels)" : ": arrays must have the shape (N, channels, height, width)"));
+			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[3], step_x)),
+				pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[2], step_y)), step_x, step_y);
+			if (regions.size() != static_cast<size_t>(v.shape[0]))
+				throw py::value_error(std::string(what) + ": got " + std::to_string(v.shape[0]) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
+				if (static_cast<size_t>(v.shape[1]) != img->num_channels()) throw py::value_error(std::string(what) + ": the arrays' channel count does not match the image");
+				if (img->num_channels()) img->channel(0).check_regions(regions);
+				if (regions.empty() || v.count() == 0) return 0;
+				wait_for(stream);
+				img->set_regions(regions, static_cast<const T*>(v.ptr));
 				return 0;
 			});
 		}
@@ -895,7 +1031,13 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_pixels", [](const Channel& c, const py::object& xs, const py::object& ys) { return c.get_regions(xs, ys, 1, 1, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"))
 		.def("__getitem__", &Channel::getitem, py::arg("key"))
-		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"));
+		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_regions", [](Channel& c, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy) {
+				c.set_regions(xs, ys, arrays, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_pixels", [](Channel& c, const py::object& xs, const py::object& ys, const py::array& values) { c.set_regions(xs, ys, values, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"))
+		.def("__setitem__", &Channel::setitem, py::arg("key"), py::arg("value"));
 
 	py::class_<Image>(m, "Image", py::module_local())
 		.def(py::init<const py::object&, const std::vector<py::array>&, size_t, size_t, std::vector<std::string>, codec, size_t, size_t, size_t, std::optional<int>>(),
@@ -919,7 +1061,12 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1, py::arg("step_y") = 1)
 		.def("get_pixels", [](const Image& i, const py::object& xs, const py::object& ys) { return i.get_regions(xs, ys, 1, 1, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"))
-		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"))
+		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_regions", [](Image& i, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy) {
+				i.set_regions(xs, ys, arrays, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_pixels", [](Image& i, const py::object& xs, const py::object& ys, const py::array& values) { i.set_regions(xs, ys, values, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("print_statistics", [](const Image& i) { i.visit([](auto& img) { img->print_statistics(); return 0; }); })
 		.def("compression_ratio", [](const Image& i) { return i.visit([](auto& img) { return img->compression_ratio(); }); })
@@ -987,7 +1134,15 @@ PYBIND11_MODULE(compressed_image, m)
 				return c.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
-		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt);
+		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
+			py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_regions", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
+				py::ssize_t sx, py::ssize_t sy) { c.set_regions(xs, ys, arrays, stream, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_pixels", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream) {
+				c.set_regions(xs, ys, values, stream, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt)
+		.def("__setitem__", &DeviceChannel::setitem, py::arg("key"), py::arg("value"));
 
 	py::class_<DeviceImage>(m, "DeviceImage", py::module_local())
 		.def(py::init(&DeviceImage::from_arrays), py::arg("dtype"), py::arg("channels"), py::arg("width"), py::arg("height"),
@@ -1012,7 +1167,14 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_pixels", [](const DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream) {
 				return i.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
-		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt)
+		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
+			py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_regions", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
+				py::ssize_t sx, py::ssize_t sy) { i.set_regions(xs, ys, arrays, stream, sx, sy, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_pixels", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream) {
+				i.set_regions(xs, ys, values, stream, 1, 1, true); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt)
 		.def("get_channel_index", [](const DeviceImage& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("get_channel_names", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->channelnames(); }); })
 		.def("set_channel_names", [](DeviceImage& i, std::vector<std::string> names) { i.visit([&](auto& img) { img->channelnames(std::move(names)); return 0; }); }, py::arg("channel_names"))

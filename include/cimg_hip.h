@@ -272,6 +272,25 @@ int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
                              const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
                              const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
                              int32_t* status);
+/* Strided window writes: the two calls above over cimg_window_strided.  Element c of window row r is written to plane element
+ * origin + r * row_pitch + c * col_pitch; the source rows are dense (width * typesize bytes at src + out_off + r * out_pitch).  The
+ * window checks are those of the strided reads (col_pitch >= 1, row_pitch >= span for height > 1, every sampled element inside the
+ * plane), the other checks, the order (a later window wins on every byte two windows share), new bytes, status and return values
+ * those of the calls above.  A block is staged and re-encoded only if it holds a byte of a written element: blocks and chunks
+ * between samples are copied as they are or not named at all (new_cbytes[i] = 0; the host call does not upload them).  A block counts
+ * as covered -- not staged -- only through windows with col_pitch 1.  With col_pitch 1 everywhere a call gives the new chunks,
+ * new_cbytes, status, return value and cimg_engine_update_stats of the plain call with the same windows.  The patch launch is
+ * cimg_update_patch_strided (CIMG_K_UPDATE_PATCH_STRIDED); a call whose work items do not fit the tables' int32 fields is
+ * BLOSC2_ERROR_INVALID_PARAM before anything runs (a theoretical limit: more than 2^31 (window, block) pairs). */
+int cimg_update_windows_strided_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp,
+                                       const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
+                                       const int32_t* blocksize, const int32_t* destsize, int32_t nwindows,
+                                       const cimg_window_strided* w, const void* d_src, void* d_new, const int64_t* new_off,
+                                       int32_t* new_cbytes, int32_t* status);
+int cimg_update_windows_strided_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                     const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_strided* w,
+                                     const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
+                                     int32_t* status);
 /* The last update call on this engine: blocks staged from their old streams, blocks re-encoded on the splice route, chunks decoded
  * and compressed whole, bytes uploaded (host call only: touched chunks and window bytes).  Any pointer may be NULL. */
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole,
@@ -355,7 +374,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* the window launch of cimg_decompress_windows_grouped_device / _host */
        CIMG_K_DECODE_WINDOW_GROUPED = 24,
        /* BloscLZ streams beyond 65 535 bytes (blocks up to 256 KiB): the wide encoder's BloscLZ instance */
-       CIMG_K_ENCODE_WIDE_BLOSCLZ = 25, CIMG_K_COUNT = 26 };
+       CIMG_K_ENCODE_WIDE_BLOSCLZ = 25,
+       /* the patch launch of cimg_update_windows_strided_device / _host */
+       CIMG_K_UPDATE_PATCH_STRIDED = 26, CIMG_K_COUNT = 27 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

@@ -23,6 +23,12 @@ first) that can also be run on its own -- `python tools/diag_windows.py --groupe
       block, each through cimg_decompress_windows_grouped_device against the strided multi-window call over the same windows
       (kernel time, wall time with its spread over the REPS runs, both block counts), against the whole decode followed by torch
       indexing (its kernel time: K_DECODE plus torch's indexing between two events), and against N single get_region calls through DeviceChannel (and DeviceChannel.get_regions / get_pixels itself).
+Strided write leg, in a child process (`--write-strided-leg`, torch first) that can also be run on its own:
+  (7) the 1024^2 window of (3) through cimg_update_windows_strided_device with col_pitch 1 against cimg_update_windows_device,
+      alternating (wall medians, the plain call's max - min, each patch kernel's time); 4096 distinct seeded random pixels written
+      into a device-resident 4096^2 float16 plane (lz4 + shuffle, 32 KiB blocks) through the strided call against the same 4096
+      1 x 1 windows through the plain call; every 4th pixel in x and y of a 2048^2 region of that plane through
+      DeviceChannel.set_region(..., step_x=4, step_y=4) against get_region of the rectangle + a torch scatter + set_region.
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -34,7 +40,8 @@ import time
 
 STRIDED_LEG = "--strided-leg" in sys.argv
 GROUPED_LEG = "--grouped-leg" in sys.argv
-if STRIDED_LEG or GROUPED_LEG:
+WRITE_STRIDED_LEG = "--write-strided-leg" in sys.argv
+if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG:
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,6 +82,102 @@ def timed(fn, kernels):
         kus.append(sum(eng.kernel_time(k)[0] for k in kernels) * 1e3)
     eng.enable_timing(0)
     return float(np.median(kus)), float(np.median(walls))
+
+
+def write_strided_leg():
+    """(7), in the child process: strided and batched writes against the routes they replace"""
+    out = {}
+    rng = np.random.default_rng(7)
+
+    def alternating(fa, fb, ka, kb):
+        """fa and fb in turn, REPS times after a warm-up of each -> per call: wall median, wall max - min, kernel median (us)"""
+        fa(); fb()
+        eng.enable_timing(1)
+        wa, wb, qa, qb = [], [], [], []
+        for _ in range(REPS):
+            for f, ws, ks, kid in ((fa, wa, qa, ka), (fb, wb, qb, kb)):
+                eng.reset_timing()
+                t = time.perf_counter()
+                f()
+                ws.append((time.perf_counter() - t) * 1e6)
+                ks.append(eng.kernel_time(kid)[0] * 1e3)
+        eng.enable_timing(0)
+        return [dict(wall_us=round(float(np.median(x)), 1), wall_spread_us=round(float(max(x) - min(x)), 1), patch_kernel_us=round(float(np.median(k)), 1))
+                for x, k in ((wa, qa), (wb, qb))]
+
+    # the 1024^2 window of (3), col_pitch 1 against the plain call
+    win = rng.integers(0, 1 << 20, (w, w)).astype(np.float32)
+    d_src, d_new = eng.alloc(win.nbytes), eng.alloc(nch * dest)
+    d_src.upload(win.view(np.uint8).ravel())
+    args = (hip.cparams(4), d_comp.ptr, comp_off, [chunk] * nch, [32768] * nch, [chunk + 32] * nch)
+    plain, strd = alternating(lambda: eng.update_windows_device(*args, [spec], d_src.ptr, d_new.ptr, comp_off, comp_size=cb),
+                              lambda: eng.update_windows_strided_device(*args, [dict(spec, col_pitch=1)], d_src.ptr, d_new.ptr, comp_off, comp_size=cb),
+                              hip.K_UPDATE_PATCH, hip.K_UPDATE_PATCH_STRIDED)
+    out["window_1024_plain"], out["window_1024_col_pitch_1"] = plain, strd
+    d_src.free(); d_new.free()
+    # 4096 distinct pixels into a 4096^2 float16 plane
+    m = 4096
+    plane = np.ascontiguousarray(synth.tiled_channel(np.float16, m, m)).view(np.uint8).ravel()
+    k16 = plane.size // chunk
+    off16 = np.arange(k16, dtype=np.int64) * dest
+    d_p, d_c, d_n = eng.alloc(plane.size), eng.alloc(k16 * dest), eng.alloc(k16 * dest)
+    d_p.upload(plane)
+    cb16 = eng.compress_device(hip.cparams(2), d_p.ptr, np.arange(k16, dtype=np.int64) * chunk, [chunk] * k16, d_c.ptr, off16, [dest] * k16)
+    at = rng.choice(m * m, 4096, replace=False)
+    px = [dict(chunk_first=0, chunk_count=k16, origin=int(a), row_pitch=1, width=1, height=1, out_off=2 * i, out_pitch=2) for i, a in enumerate(at)]
+    d_v = eng.alloc(2 * 4096)
+    d_v.upload(rng.integers(0, 255, 2 * 4096, dtype=np.uint8))
+    # (the C entry points called directly over window tables built once: 4096 dicts to ctypes cost more than the call itself)
+    import ctypes as C
+    lib, p2 = hip.load(), hip.cparams(2)
+    i32, i64, ptr = hip._i32, hip._i64, hip._ptr
+    nb16, bs16, ds16, cs16, o16 = i32([chunk] * k16), i32([32768] * k16), i32([chunk + 32] * k16), i32(cb16), i64(off16)
+    ncb, st = np.zeros(k16, np.int32), np.zeros(k16, np.int32)
+    wp, wstr = hip.windows(px), hip.strided_windows([dict(q, col_pitch=1) for q in px])
+
+    def direct(fn, wt):
+        def f():
+            rc = fn(eng.handle, C.byref(p2), k16, d_c.ptr, ptr(o16), ptr(cs16), ptr(nb16), ptr(bs16), ptr(ds16), len(px), wt, d_v.ptr, d_n.ptr,
+                    ptr(o16), ptr(ncb), ptr(st))
+            assert rc == 0, rc
+        return f
+
+    plain, strd = alternating(direct(lib.cimg_update_windows_device, wp), direct(lib.cimg_update_windows_strided_device, wstr),
+                              hip.K_UPDATE_PATCH, hip.K_UPDATE_PATCH_STRIDED)
+    out["pixels4096_plain"], out["pixels4096_strided"] = plain, strd
+    out["pixels4096_blocks_encoded"] = eng.update_stats()["blocks_encoded"]
+    for b in (d_p, d_c, d_n, d_v):
+        b.free()
+    # every 4th pixel of a 2048^2 region through the module, against get_region + scatter + set_region
+    path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
+    spec_m = importlib.util.spec_from_file_location("compressed_image", path)
+    ci = importlib.util.module_from_spec(spec_m)
+    spec_m.loader.exec_module(ci)
+    dch = ci.DeviceChannel(torch.from_numpy(plane.view(np.float16).reshape(m, m)).cuda(), m, m, block_size=32768, chunk_size=chunk)
+    sub = torch.from_numpy(rng.integers(0, 1000, (512, 512)).astype(np.float16)).cuda()
+
+    def new_route():
+        dch.set_region(1024, 1024, sub, step_x=4, step_y=4)
+
+    def old_route():
+        r = torch.as_tensor(dch.get_region(1024, 1024, 2048, 2048), device="cuda")
+        r[::4, ::4] = sub
+        dch.set_region(1024, 1024, r)
+
+    for name, fn in (("subsample_set_region_steps", new_route), ("subsample_get_scatter_set", old_route)):
+        fn()
+        ts = []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t) * 1e6)
+        out[name] = dict(wall_us=round(float(np.median(ts)), 1), wall_spread_us=round(float(max(ts) - min(ts)), 1))
+    want = plane.view(np.float16).reshape(m, m).copy()
+    want[1024:3072:4, 1024:3072:4] = sub.cpu().numpy()
+    assert np.array_equal(torch.as_tensor(dch.get_decompressed(), device="cuda").cpu().numpy(), want)
+    return out
 
 
 def strided_leg():
@@ -221,6 +324,15 @@ if GROUPED_LEG:
     eng.close()
     sys.exit(0)
 
+if WRITE_STRIDED_LEG:
+    line = json.dumps(write_strided_leg())
+    print("WSTRIDED " + line)
+    if "--out" in sys.argv:
+        open(sys.argv[sys.argv.index("--out") + 1], "w").write(line + "\n")
+    d_raw.free(); d_comp.free(); d_win.free()
+    eng.close()
+    sys.exit(0)
+
 if STRIDED_LEG:
     print("STRIDED " + json.dumps(strided_leg()))
     d_raw.free(); d_comp.free(); d_win.free()
@@ -331,6 +443,11 @@ child = subprocess.run([sys.executable, os.path.abspath(__file__), "--grouped-le
 got = [ln for ln in child.stdout.splitlines() if ln.startswith("GROUPED ")]
 assert child.returncode == 0 and got, child.stdout[-2000:] + child.stderr[-4000:]
 res["grouped"] = json.loads(got[0][len("GROUPED "):])
+# (7): in a process of its own
+child = subprocess.run([sys.executable, os.path.abspath(__file__), "--write-strided-leg"], capture_output=True, text=True, timeout=1800)
+got = [ln for ln in child.stdout.splitlines() if ln.startswith("WSTRIDED ")]
+assert child.returncode == 0 and got, child.stdout[-2000:] + child.stderr[-4000:]
+res["write_strided"] = json.loads(got[0][len("WSTRIDED "):])
 line = json.dumps(res)
 print(line)
 if len(sys.argv) > 2 and sys.argv[1] == "--out":
