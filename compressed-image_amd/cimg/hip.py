@@ -23,6 +23,7 @@ K_TRUNC_PREC = 23                              # trunc-prec: the masked copy in 
 K_DECODE_WINDOW_GROUPED = 24                   # grouped windows: every block staged once for all its windows (csrc/window_kernel.h)
 K_ENCODE_WIDE_BLOSCLZ = 25                     # BloscLZ streams beyond 65 535 bytes: the wide encoder's BloscLZ instance (csrc/wide_kernel.h)
 K_UPDATE_PATCH_STRIDED = 26                    # strided window writes: the patch launch of cimg_update_windows_strided_* (csrc/update_kernel.h)
+K_DECODE_WINDOW_TYPED = 27                     # typed windows: convert, scale and place each element in the launch (csrc/window_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -30,7 +31,8 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_decode_zstd", "cimg_encode_streams_zstd", "cimg_zstd_walk", "cimg_zstd_replay", "cimg_decode_zstd_fused", "cimg_zstd_seq", "cimg_zstd_lit",
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
-           "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz", "cimg_update_patch_strided")
+           "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz", "cimg_update_patch_strided",
+           "cimg_decode_window_typed")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -53,7 +55,7 @@ EXPORTS = (
     "cimg_engine_debug_stamps", "cimg_engine_read_stamps", "cimg_shared_engine", "cimg_context_cparams",
     "cimg_decompress_windows_device", "cimg_decompress_windows_host", "cimg_engine_window_stats",
     "cimg_decompress_windows_strided_device", "cimg_decompress_windows_strided_host",
-    "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host",
+    "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host", "cimg_decompress_windows_typed_device",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
     "cimg_update_windows_strided_device", "cimg_update_windows_strided_host",
     "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
@@ -109,6 +111,32 @@ def strided_windows(specs):
         arr[i].col_pitch = 1
         for k, v in (s.items() if isinstance(s, dict) else ((f, getattr(s, f)) for f, _ in StridedWindow._fields_)):
             setattr(arr[i], k, int(v))
+    return arr
+
+
+T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F16, T_F32, T_F64 = range(9)     # CIMG_T_* (include/cimg_hip.h)
+_T_OF_DTYPE = {"uint8": T_U8, "int8": T_I8, "uint16": T_U16, "int16": T_I16, "uint32": T_U32, "int32": T_I32, "float16": T_F16,
+               "float32": T_F32, "float64": T_F64}
+
+
+def type_of(dtype):
+    """the CIMG_T_* code of a numpy dtype"""
+    return _T_OF_DTYPE[np.dtype(dtype).name]
+
+
+class TypedWindow(C.Structure):
+    """cimg_window_typed (include/cimg_hip.h)"""
+    _fields_ = StridedWindow._fields_ + [("elem_pitch", C.c_int64), ("src_type", C.c_int32), ("out_type", C.c_int32),
+                                         ("scale", C.c_float), ("offset", C.c_float)]
+
+
+def typed_windows(specs):
+    """dicts (or TypedWindow) with the fields of cimg_window_typed -> a ctypes array (col_pitch and scale default to 1)"""
+    arr = (TypedWindow * max(len(specs), 1))()
+    for i, s in enumerate(specs):
+        arr[i].col_pitch, arr[i].scale = 1, 1.0
+        for k, v in (s.items() if isinstance(s, dict) else ((f, getattr(s, f)) for f, _ in TypedWindow._fields_)):
+            setattr(arr[i], k, float(v) if k in ("scale", "offset") else int(v))
     return arr
 
 
@@ -197,6 +225,8 @@ def load():
     L.cimg_decompress_windows_strided_host.argtypes = L.cimg_decompress_windows_host.argtypes
     L.cimg_decompress_windows_grouped_device.argtypes = L.cimg_decompress_windows_device.argtypes
     L.cimg_decompress_windows_grouped_host.argtypes = L.cimg_decompress_windows_host.argtypes
+    if hasattr(L, "cimg_decompress_windows_typed_device"):      # (a CIMG_LIB build from before it)
+        L.cimg_decompress_windows_typed_device.argtypes = L.cimg_decompress_windows_device.argtypes
     L.cimg_update_windows_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_update_windows_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
     L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
@@ -497,6 +527,19 @@ class Engine:
             fn = load().cimg_decompress_windows_grouped_device
         rc = fn(self.handle, nbytes.size, d_comp, _ptr(comp_off), _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), typesize,
                 len(specs), w, d_out, _ptr(status))
+        if check:
+            self._check(rc)
+        return status if check else (rc, status)
+
+    def decompress_windows_typed_device(self, d_comp, comp_off, nbytes, blocksize, typesize, specs, d_out, comp_size=None, check=True):
+        """typed windows (cimg_window_typed specs: elem_pitch, src_type, out_type, scale, offset) of device-resident chunks into
+        device memory at d_out through cimg_decompress_windows_typed_device; returns the per-chunk status"""
+        comp_off, nbytes, blocksize = _i64(comp_off), _i32(nbytes), _i32(blocksize)
+        cs = _i32(comp_size) if comp_size is not None else None
+        status = np.zeros(nbytes.size, np.int32)
+        rc = load().cimg_decompress_windows_typed_device(self.handle, nbytes.size, d_comp, _ptr(comp_off), _ptr(cs) if cs is not None else None,
+                                                         _ptr(nbytes), _ptr(blocksize), typesize, len(specs), typed_windows(specs), d_out,
+                                                         _ptr(status))
         if check:
             self._check(rc)
         return status if check else (rc, status)

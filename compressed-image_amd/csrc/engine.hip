@@ -256,6 +256,17 @@ extern "C" __global__ __launch_bounds__(256) void cimg_decode_window_grouped(Gro
     gb.phase_w(wave);
 }
 
+// Typed windows: the grouped launch whose write phase converts each element and stores it at its own pitch (TypedWindowBlock).
+extern "C" __global__ __launch_bounds__(256) void cimg_decode_window_typed(TypedWindowArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    TypedWindowBlock tb(a, lds, (int)blockIdx.x);
+    tb.phase_a(wave);
+    __syncthreads();
+    tb.phase_w(wave);
+}
+
 // zstd blocks beyond the normal kernels' LDS.  Encode: cimg_encode_wide's waves with zstd_wide_encode (hash table and FSE tables in
 // LDS, sequences in a device-memory area per wave).  Decode, behind cimg_zstd_walk: the replay with its planes in a device-memory
 // slot per single-wave workgroup, which walks blocks blk_first + k, k + G, ... of the group.
@@ -446,7 +457,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16)
+    int max_dyn_lds[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16) / typed window decode (17)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -650,6 +661,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_DECODE_WINDOW: return "cimg_decode_window";
     case CIMG_K_DECODE_WINDOW_STRIDED: return "cimg_decode_window_strided";
     case CIMG_K_DECODE_WINDOW_GROUPED: return "cimg_decode_window_grouped";
+    case CIMG_K_DECODE_WINDOW_TYPED: return "cimg_decode_window_typed";
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_PATCH_STRIDED: return "cimg_update_patch_strided";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
@@ -2191,6 +2203,12 @@ struct EngineWindowEnv : EngineChunks {
     {
         return run(plan, items, status, &units, &order);
     }
+    // (TypedEnv: the same, over typed items)
+    int run_typed_units(const TypedWindowPlan& plan, const std::vector<TypedWindowItem>& items, const std::vector<int32_t>& order,
+                        const std::vector<WindowUnit>& units, int32_t* status)
+    {
+        return run(plan, items, status, &units, &order);
+    }
 
     // the launch over a table of items: cimg_decode_window, or its strided form over StridedWindowItem; units: the grouped form,
     // whose items go into the table in `order` and whose unit table rides behind them in the same upload
@@ -2229,7 +2247,13 @@ struct EngineWindowEnv : EngineChunks {
         wa.out = d_out;
         wa.typesize = typesize;
         wa.nitems = (int32_t)items.size();
-        if constexpr (std::is_same_v<Item, StridedWindowItem>) {
+        if constexpr (std::is_same_v<Item, TypedWindowItem>) {
+            const TypedWindowArgs ta{wa, (const TypedWindowItem*)e->win_items.p, (const WindowUnit*)((const uint8_t*)e->win_items.p + tb),
+                                     (int32_t)units->size()};
+            if ((rc = e->allow_lds(cimg_decode_window_typed, 17, plan.lds_bytes))) return rc;
+            e->begin_batch(1);
+            rc = e->launch(CIMG_K_DECODE_WINDOW_TYPED, cimg_decode_window_typed, ta, (int)units->size(), 256, plan.lds_bytes);
+        } else if constexpr (std::is_same_v<Item, StridedWindowItem>) {
             if (units) {
                 const GroupedWindowArgs ga{wa, (const StridedWindowItem*)e->win_items.p, (const WindowUnit*)((const uint8_t*)e->win_items.p + tb),
                                            (int32_t)units->size()};
@@ -2268,6 +2292,13 @@ int invalid_window(cimg_engine* e, const StridedWindowSpec*)
                                       "out_pitch >= width * typesize and one typesize per plane");
 }
 int invalid_window(cimg_engine* e, const WindowSpec*) { return invalid_window(e); }
+int invalid_window(cimg_engine* e, const TypedWindowSpec*)
+{
+    return e->fail(ERR_INVALID_PARAM, "invalid typed window: the checks of a strided window but out_pitch >= (width - 1) * elem_pitch + the output "
+                                      "size (height > 1); src_type of the call's typesize; out_type float32 or float16, or src_type with "
+                                      "scale 1 and offset 0; elem_pitch >= the output size; out_off, out_pitch, elem_pitch and the output "
+                                      "address multiples of the output size; every blocksize of the plane a multiple of the typesize");
+}
 
 // the text of a call refused at its opening (open_window_call, open_update_call) or by read_named_headers
 int open_fail(cimg_engine* e, int32_t nchunks, int32_t nwindows)
@@ -2290,7 +2321,7 @@ int copy_rows(cimg_engine* e, void* dst, int64_t dst_pitch, const void* src, int
     return e->hip(hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)row, (size_t)height, kind, e->stream), what);
 }
 
-// (Grouped: a strided call whose launches are grouped, run_windows_grouped)
+// (Grouped: a strided call whose launches are grouped, run_windows_grouped; typed windows: run_windows_typed)
 template <bool Grouped = false, class Spec>
 int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off, const int32_t* comp_size,
                 const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int32_t check_ts, const std::vector<uint8_t>& hint,
@@ -2299,7 +2330,8 @@ int windows_run(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64
     EngineWindowEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, (uint8_t*)d_out, check_ts};
     WindowStats st;
     int rc;
-    if constexpr (Grouped) rc = run_windows_grouped(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
+    if constexpr (std::is_same_v<Spec, TypedWindowSpec>) rc = run_windows_typed(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
+    else if constexpr (Grouped) rc = run_windows_grouped(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
     else rc = run_windows(env, nchunks, nbytes, blocksize, typesize, nwindows, w, hint, status, &st);
     e->win_stats = st;
     if (rc == ERR_INVALID_PARAM) return invalid_window(e, w);
@@ -2321,6 +2353,11 @@ int windows_device_call(cimg_engine* e, int32_t nchunks, const void* d_comp, con
     if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
     if (!w || !comp_off || !nbytes || !blocksize || !status || !d_comp || !d_out) return e->fail(ERR_INVALID_PARAM, "null argument");
     if (typesize <= 0 || typesize > 255) return e->fail(ERR_INVALID_PARAM, "typesize %d", typesize);
+    if constexpr (std::is_same_v<Spec, TypedWindowSpec>) {
+        // every output element naturally aligned: the planner checks the offsets and pitches, the base is checked here
+        for (int k = 0; k < nwindows; k++)
+            if (type_size(w[k].out_type) && (uintptr_t)d_out % (uintptr_t)type_size(w[k].out_type)) return invalid_window(e, w);
+    }
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     std::vector<int32_t> ts((size_t)nchunks, typesize);
@@ -2423,6 +2460,20 @@ int cimg_decompress_windows_grouped_host(cimg_engine* e, int32_t nchunks, const 
 {
     return windows_host_call<true>(e, nchunks, h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const StridedWindowSpec*>(w), h_out,
                                    status);
+}
+
+static_assert(sizeof(cimg_window_typed) == sizeof(TypedWindowSpec) && offsetof(cimg_window_typed, out_pitch) == offsetof(TypedWindowSpec, out_pitch) &&
+              offsetof(cimg_window_typed, elem_pitch) == offsetof(TypedWindowSpec, elem_pitch) &&
+              offsetof(cimg_window_typed, offset) == offsetof(TypedWindowSpec, offset), "cimg_window_typed != TypedWindowSpec");
+static_assert(CIMG_T_U8 == T_U8 && CIMG_T_I8 == T_I8 && CIMG_T_U16 == T_U16 && CIMG_T_I16 == T_I16 && CIMG_T_U32 == T_U32 && CIMG_T_I32 == T_I32 &&
+              CIMG_T_F16 == T_F16 && CIMG_T_F32 == T_F32 && CIMG_T_F64 == T_F64, "CIMG_T_* != T_*");
+
+int cimg_decompress_windows_typed_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, int32_t typesize,
+                                         int32_t nwindows, const cimg_window_typed* w, void* d_out, int32_t* status)
+{
+    return windows_device_call(e, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, typesize, nwindows,
+                               reinterpret_cast<const TypedWindowSpec*>(w), d_out, status);
 }
 
 void cimg_engine_window_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* chunks_whole, int64_t* comp_bytes_uploaded)

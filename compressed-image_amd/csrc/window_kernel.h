@@ -7,7 +7,8 @@
 // nothing) without staging; items of chunks that were decoded whole beforehand
 // (zstd, blocks beyond LDS: the batch path into engine scratch) are cut from that copy (`b < 0`).
 // cimg_decode_window_strided (below) stages the same way and writes only every col_pitch-th element of each window row.
-// cimg_decode_window_grouped (at the end) runs one workgroup per distinct block and writes every window that meets it.
+// cimg_decode_window_grouped runs one workgroup per distinct block and writes every window that meets it.
+// cimg_decode_window_typed (at the end) groups the same way and converts each element on its way out of LDS.
 #pragma once
 #include "decode_kernel.h"
 
@@ -340,6 +341,158 @@ struct GroupedWindowBlock {
                             for (int i = 0; i < 4; i++)
                                 if (at[i] >= 0) dst[q0 + i] = wb.byte_at(at[i]);
                         }
+                    }
+                }
+            }
+        }
+    }
+
+    CIMG_DEV void phase_w(int wave)
+    {
+        if (wb.mode == 3) return;                                              // (the block failed to stage: nothing for any item)
+        if (u.nitems == 1) { write_item(u.item0, wave * 64, 256); return; }
+        for (int k = wave; k < u.nitems; k += 4) write_item(u.item0 + k, 0, 64);
+    }
+};
+
+// ---- typed windows: cimg_decode_window_typed ----------------------------------------------------------------------------------
+// The grouped launch with a write phase of its own: the work unit is one output ELEMENT.  A thread gathers the ts bytes of a
+// sampled element (WindowBlock::byte_at, every mode), converts the value -- x = (float)v, y = fl32(fl32(x * scale) + offset), two
+// roundings and never an FMA, then y itself or y rounded once to float16 -- and stores it with one store of the output's size at
+// out + out_off + r * out_pitch + c * epitch.  Bytes between the elements of a row are not written, so the windows of C planes can
+// fill the channel slots of pixel-major rows (epitch = C * size of the output type).  An item whose output type is its stored type
+// with scale 1 and offset 0 copies the element's bytes unchanged.  The planner (window_plan.h: plan_windows over TypedWindowSpec)
+// admits only planes whose blocks hold whole elements, and only naturally aligned outputs.
+enum : int { T_U8 = 0, T_I8 = 1, T_U16 = 2, T_I16 = 3, T_U32 = 4, T_I32 = 5, T_F16 = 6, T_F32 = 7, T_F64 = 8, T_COUNT = 9 };   // = CIMG_T_*
+
+CIMG_HD int type_size(int t) { return t < 0 || t >= T_COUNT ? 0 : t < T_U16 ? 1 : t < T_U32 || t == T_F16 ? 2 : t == T_F64 ? 8 : 4; }
+
+struct TypedWindowItem : StridedWindowItem {
+    int64_t epitch;       // output bytes between consecutive elements of a row
+    int32_t src_type, out_type;     // T_*
+    float scale, offset;
+};
+
+struct TypedWindowArgs {
+    WindowArgs w;              // (w.items unused; w.nitems: items of the table)
+    const TypedWindowItem* items;
+    const WindowUnit* units;
+    int32_t nunits;
+};
+
+CIMG_HD uint32_t f32_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+CIMG_HD float bits_f32(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
+
+#ifdef CIMG_EMULATE
+// float16 <-> float32 in integer arithmetic (the host compiler need not know a half type): exact one way, round to nearest even
+// the other, subnormals kept, overflow to inf
+inline float half_to_f32(uint16_t h)
+{
+    const uint32_t s = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u;
+    uint32_t m = h & 0x3FFu;
+    if (e == 31) return bits_f32(s | 0x7F800000u | (m << 13));
+    if (e) return bits_f32(s | ((e + 112) << 23) | (m << 13));
+    if (!m) return bits_f32(s);
+    const int sh = __builtin_clz(m) - 21;                     // the top bit of m goes to bit 10
+    m = (m << sh) & 0x3FFu;
+    return bits_f32(s | ((uint32_t)(113 - sh) << 23) | (m << 13));
+}
+inline uint16_t f32_to_half(float f)
+{
+    const uint32_t u = f32_bits(f), s = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return (uint16_t)(s | 0x7E00u);      // NaN
+    if (a >= 0x477FF000u) return (uint16_t)(s | 0x7C00u);     // >= 65520: inf
+    if (a >= 0x38800000u) {                                   // a normal half
+        const uint32_t m = a - 0x38000000u, rem = m & 0x1FFFu;
+        uint32_t r = m >> 13;
+        if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) r++;
+        return (uint16_t)(s | r);
+    }
+    if (a <= 0x33000000u) return (uint16_t)s;                 // <= 2^-25: zero (the tie goes to even)
+    const int shift = 126 - (int)(a >> 23);                   // 14 .. 24: units of 2^-24
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
+    uint32_t r = m >> shift;
+    if (rem > half || (rem == half && (r & 1))) r++;
+    return (uint16_t)(s | r);
+}
+#else
+CIMG_DEV float half_to_f32(uint16_t h) { _Float16 x; __builtin_memcpy(&x, &h, 2); return (float)x; }
+CIMG_DEV uint16_t f32_to_half(float f) { const _Float16 x = (_Float16)f; uint16_t h; __builtin_memcpy(&h, &x, 2); return h; }
+#endif
+
+// the stored element `bits` (its ts low bytes) as float32: exact for 8 / 16-bit integers and float16, one rounding for the rest
+CIMG_DEV float typed_load(uint64_t bits, int src_type)
+{
+    switch (src_type) {
+    case T_U8: case T_U16: case T_U32: return (float)(uint32_t)bits;
+    case T_I8: return (float)(int8_t)bits;
+    case T_I16: return (float)(int16_t)bits;
+    case T_I32: return (float)(int32_t)bits;
+    case T_F16: return half_to_f32((uint16_t)bits);
+    case T_F32: return bits_f32((uint32_t)bits);
+    default: { double d; __builtin_memcpy(&d, &bits, 8); return (float)d; }
+    }
+}
+
+// fl32(fl32(x * scale) + offset): the product is rounded before the sum -- no contraction to an FMA here, whatever the build's
+// default says (the emulator's translation unit is built with -ffp-contract=off)
+CIMG_DEV float typed_scale(float x, float scale, float offset)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float p = x * scale;
+    return p + offset;
+}
+
+struct TypedWindowBlock {
+    const TypedWindowArgs& a;
+    WindowUnit u;
+    WindowBlock wb;            // the staged block, through the unit's first item
+
+    CIMG_DEV TypedWindowBlock(const TypedWindowArgs& a_, uint8_t* lds, int k)
+        : a(a_), u(GroupedWindowBlock::uniform_unit(a_.units + k)), wb(a_.w, lds, WindowBlock::uniform_item(a_.items + u.item0)) {}
+
+    CIMG_DEV void phase_a(int wave) { wb.phase_a(wave); }
+
+    // item k of the table over the staged block, by threads tid0 + lane, + stride, ...: one element a thread
+    CIMG_DEV void write_item(int k, int tid0, int stride)
+    {
+        const WindowItem it = WindowBlock::uniform_item(a.items + k);
+        const int64_t cpitch = uni64(a.items[k].cpitch), epitch = uni64(a.items[k].epitch);
+        const int ts = uni(a.items[k].ts), src_type = uni(a.items[k].src_type), out_type = uni(a.items[k].out_type);
+        const float scale = bits_f32(uni(f32_bits(a.items[k].scale))), offset = bits_f32(uni(f32_bits(a.items[k].offset)));
+        const bool identity = out_type == src_type && scale == 1.0f && offset == 0.0f;
+        const int osz = identity ? ts : type_size(out_type);
+        const int64_t blen = wb.blen, width = it.wbytes / ts;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the block
+            // elements c_lo .. c_hi of the row lie inside [0, blen) (whole: the planner admits no element over a block's edge)
+            const int64_t hi = blen - ts - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = rel >= 0 ? 0 : (-rel + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            const int64_t base = rel + c_lo * cpitch;                          // block offset of element c_lo (>= 0)
+            uint8_t* dst = a.w.out + it.out_off + (int64_t)r * it.out_pitch + c_lo * epitch;
+            const int64_t n = c_hi + 1 - c_lo;                                 // (< 2^31: at most blen / ts elements)
+            for (int64_t e0 = tid0; e0 < n; e0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t e = e0 + l;
+                    if (e < n) {
+                        const int64_t at = base + e * cpitch;
+                        uint64_t v = 0;
+                        for (int j = 0; j < ts; j++) v |= (uint64_t)wb.byte_at(at + j) << (8 * j);
+                        if (!identity) {
+                            const float y = typed_scale(typed_load(v, src_type), scale, offset);
+                            v = out_type == T_F16 ? (uint64_t)f32_to_half(y) : (uint64_t)f32_bits(y);
+                        }
+                        uint8_t* q = dst + e * epitch;
+                        if (osz == 1) *q = (uint8_t)v;
+                        else if (osz == 2) *reinterpret_cast<uint16_t*>(q) = (uint16_t)v;
+                        else if (osz == 4) *reinterpret_cast<uint32_t*>(q) = (uint32_t)v;
+                        else *reinterpret_cast<uint64_t*>(q) = v;
                     }
                 }
             }

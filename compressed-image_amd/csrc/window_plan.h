@@ -9,7 +9,8 @@
 // are decoded whole through the batch path first and cut from there (copy-mode items).  A strided window (StridedWindowSpec, for
 // cimg_decode_window_strided) takes every col_pitch-th element of its rows; its planner lists only the blocks that hold a byte of
 // a sampled element, and run_windows and plan_windows_host serve both kinds of window.  A grouped call (run_windows_grouped, for
-// cimg_decode_window_grouped) plans and runs the same way and regroups each launch's items by block: group_items.
+// cimg_decode_window_grouped) plans and runs the same way and regroups each launch's items by block: group_items.  A typed call
+// (run_windows_typed, for cimg_decode_window_typed) is a grouped call whose windows also say how each element is converted and placed.
 //
 // The host-buffer call (cimg_decompress_windows_host) is planned here too, for the engine and the emulator alike: open_window_call
 // (the opening of both read calls), read_named_headers, stage_chunk and pack_rows (shared with update_plan.h) and plan_windows_host,
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace cimg {
@@ -185,32 +187,37 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
 // plane -- every product is bounded by the plane before it is formed.  A block is listed only if it holds a byte of a sampled
 // element: each row walks sample to sample, and from a listed block straight to the first sample that reaches past its end, so
 // the work is min(blocks, samples) per row and the blocks (and chunks) between far-apart samples are never named.
-inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
-                        const StridedWindowSpec* w, const uint8_t* whole_hint, StridedWindowPlan* plan)
+// (the checks but the one on out_pitch, and the listing, are templates: typed windows -- further down -- share them)
+// 0: good, 1: nothing to list (width or height 0), < 0: refused
+template <class Spec>
+inline int check_strided_window(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, const Spec& s, int* ts_out)
 {
-    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
-    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
-    for (int k = 0; k < nwindows; k++) {
-        const StridedWindowSpec& s = w[k];
-        if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
-        if (s.width < 0 || s.height < 0 || s.col_pitch < 1) return ERR_INVALID_PARAM;
-        int ts = 0;
-        int64_t elems = 0;
-        const int prc = plane_of_window(nchunks, nbytes, blocksize, typesize, s.chunk_first, s.chunk_count, &ts, &elems);
-        if (prc < 0) return prc;
-        if (s.width == 0 || s.height == 0) continue;
-        if (s.out_pitch < (int64_t)s.width * ts || s.out_off < 0) return ERR_INVALID_PARAM;
-        if (s.origin < 0 || s.origin >= elems || s.width > elems) return ERR_INVALID_PARAM;
-        if (s.width > 1 && s.col_pitch > (elems - 1) / (s.width - 1)) return ERR_INVALID_PARAM;       // span > elems
-        const int64_t span = (int64_t)(s.width - 1) * (s.width > 1 ? s.col_pitch : 0) + 1;
-        if (span > elems - s.origin) return ERR_INVALID_PARAM;
-        if (s.height > 1) {
-            if (s.row_pitch < span || s.row_pitch > elems || (int64_t)(s.height - 1) > elems / s.row_pitch) return ERR_INVALID_PARAM;
-            if ((int64_t)(s.height - 1) * s.row_pitch > elems - s.origin - span) return ERR_INVALID_PARAM;
-        }
+    if (s.chunk_first < 0 || s.chunk_count < 1 || s.chunk_first > nchunks - s.chunk_count) return ERR_INVALID_PARAM;
+    if (s.width < 0 || s.height < 0 || s.col_pitch < 1) return ERR_INVALID_PARAM;
+    int ts = 0;
+    int64_t elems = 0;
+    const int prc = plane_of_window(nchunks, nbytes, blocksize, typesize, s.chunk_first, s.chunk_count, &ts, &elems);
+    if (prc < 0) return prc;
+    *ts_out = ts;
+    if (s.width == 0 || s.height == 0) return 1;
+    if (s.out_off < 0) return ERR_INVALID_PARAM;
+    if (s.origin < 0 || s.origin >= elems || s.width > elems) return ERR_INVALID_PARAM;
+    if (s.width > 1 && s.col_pitch > (elems - 1) / (s.width - 1)) return ERR_INVALID_PARAM;       // span > elems
+    const int64_t span = (int64_t)(s.width - 1) * (s.width > 1 ? s.col_pitch : 0) + 1;
+    if (span > elems - s.origin) return ERR_INVALID_PARAM;
+    if (s.height > 1) {
+        if (s.row_pitch < span || s.row_pitch > elems || (int64_t)(s.height - 1) > elems / s.row_pitch) return ERR_INVALID_PARAM;
+        if ((int64_t)(s.height - 1) * s.row_pitch > elems - s.origin - span) return ERR_INVALID_PARAM;
     }
+    return 0;
+}
+
+// the items of validated windows; fill(item, window) completes a fresh item
+template <class Spec, class Item, class Fill>
+inline void list_strided_items(const int32_t* nbytes, const int32_t* typesize, int nwindows, const Spec* w, WindowPlanT<Item>* plan, Fill fill)
+{
     for (int k = 0; k < nwindows; k++) {
-        const StridedWindowSpec& s = w[k];
+        const Spec& s = w[k];
         if (s.width == 0 || s.height == 0) continue;
         const int ts = typesize[s.chunk_first];
         const int cf = s.chunk_first, cn = s.chunk_count;
@@ -236,16 +243,17 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
                 for (int j = jf; j <= jl; j++) {
                     const int b = whole ? -1 : d.blk0 + j;
                     if (plan->items.size() > first_item) {
-                        StridedWindowItem& last = plan->items.back();
+                        Item& last = plan->items.back();
                         if (last.chunk == chunk && last.b == b) { last.r1 = r + 1; continue; }
                     }
-                    StridedWindowItem t{};
+                    Item t{};
                     t.chunk = chunk; t.b = b; t.r0 = r; t.r1 = r + 1;
                     t.p0 = whole ? cs : cs + (int64_t)j * d.blocksize;
                     t.len = whole ? d.nbytes : 0;
                     t.row0 = row0; t.rpitch = rpitch; t.wbytes = (int64_t)ts * s.width;
                     t.out_off = s.out_off; t.out_pitch = s.out_pitch;
                     t.cpitch = cpitch; t.ts = ts;
+                    fill(t, s);
                     plan->items.push_back(t);
                 }
                 if (c + 1 >= s.width) break;                                         // (the row's last sample: nothing to skip to)
@@ -257,6 +265,20 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
             }
         }
     }
+}
+
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const StridedWindowSpec* w, const uint8_t* whole_hint, StridedWindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    for (int k = 0; k < nwindows; k++) {
+        int ts = 0;
+        const int rc = check_strided_window(nchunks, nbytes, blocksize, typesize, w[k], &ts);
+        if (rc < 0) return rc;
+        if (rc == 0 && w[k].out_pitch < (int64_t)w[k].width * ts) return ERR_INVALID_PARAM;
+    }
+    list_strided_items(nbytes, typesize, nwindows, w, plan, [](StridedWindowItem&, const StridedWindowSpec&) {});
     plan_totals(plan);
     return 0;
 }
@@ -337,21 +359,22 @@ int run_windows(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blo
 // The sort is given as a permutation -- order[k]: the item that goes to place k of the launch's table -- so that the 96-byte items
 // are moved once, by whoever fills the table; the units name places.  The blocks of a call usually lie close together: a counting
 // sort over their range where that range is small against the items, a sort of (block, index) keys otherwise.
-inline void group_items(const std::vector<StridedWindowItem>& items, std::vector<int32_t>* order, std::vector<WindowUnit>* units)
+template <class Item>
+inline void group_items(const std::vector<Item>& items, std::vector<int32_t>* order, std::vector<WindowUnit>* units)
 {
     const size_t n = items.size();
     order->resize(n);
     units->clear();
     int64_t lo = INT64_MAX, hi = -1;
     size_t ndec = 0;
-    for (const StridedWindowItem& t : items)
+    for (const Item& t : items)
         if (t.b >= 0) { lo = t.b < lo ? t.b : lo; hi = t.b > hi ? t.b : hi; ndec++; }
     size_t at = 0;
     if (ndec) {
         const uint64_t range = (uint64_t)(hi - lo) + 1;
         if (range <= 8 * (uint64_t)ndec + 4096) {
             std::vector<int32_t> start((size_t)range + 1, 0);
-            for (const StridedWindowItem& t : items) if (t.b >= 0) start[(size_t)(t.b - lo) + 1]++;
+            for (const Item& t : items) if (t.b >= 0) start[(size_t)(t.b - lo) + 1]++;
             int32_t pos = 0;
             for (size_t j = 0; j < (size_t)range; j++) {
                 const int32_t c = start[j + 1];
@@ -380,7 +403,8 @@ inline void group_items(const std::vector<StridedWindowItem>& items, std::vector
 
 // An upper bound of the items plan_windows lists, without listing them: a sample has bytes in at most `typesize` blocks.  The
 // tables of a grouped launch index items and units with int32 (WindowUnit).
-inline bool grouped_counts_fit(int nchunks, const int32_t* typesize, int nwindows, const StridedWindowSpec* w)
+template <class Spec>
+inline bool grouped_counts_fit(int nchunks, const int32_t* typesize, int nwindows, const Spec* w)
 {
     int64_t bound = 0;
     for (int k = 0; k < nwindows; k++) {
@@ -438,6 +462,123 @@ int run_windows_grouped(Env& env, int nchunks, const int32_t* nbytes, const int3
         if (plan.items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
     }
     GroupedEnv<Env> g{env};
+    const int rc = run_windows(g, nchunks, nbytes, blocksize, typesize, nwindows, w, std::move(hint), status, stats);
+    stats->blocks_decoded = g.blocks;
+    return rc;
+}
+
+// ---- typed windows: convert, scale and place each element in the launch -------------------------------------------------------
+// (cimg_decode_window_typed, window_kernel.h).  A typed window is a strided window with a description of the memory side: element c
+// of row r goes to out_off + r * out_pitch + c * elem_pitch as out_type, after y = fl32(fl32((float)v * scale) + offset); a window
+// whose out_type is its src_type with scale 1 and offset 0 copies elements unchanged.  The window checks are those of the strided
+// windows but for out_pitch (a row need not be dense); added: known types, src_type of the plane's typesize, only float32 / float16
+// out of a conversion, elem_pitch >= the output size, rows that do not run into each other, natural alignment of every output
+// element, and blocks made of whole elements all through the window's plane (a converted element cannot come from two blocks).
+// = cimg_window_typed (include/cimg_hip.h)
+struct TypedWindowSpec {
+    int32_t chunk_first, chunk_count;
+    int64_t origin;
+    int64_t row_pitch;
+    int64_t col_pitch;
+    int32_t width, height;
+    int64_t out_off, out_pitch;
+    int64_t elem_pitch;
+    int32_t src_type, out_type;
+    float scale, offset;
+};
+using TypedWindowPlan = WindowPlanT<TypedWindowItem>;
+template <> struct PlanOf<TypedWindowSpec> { using type = TypedWindowPlan; };
+
+inline bool typed_identity(const TypedWindowSpec& s) { return s.out_type == s.src_type && s.scale == 1.0f && s.offset == 0.0f; }
+
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const TypedWindowSpec* w, const uint8_t* whole_hint, TypedWindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    for (int k = 0; k < nwindows; k++) {
+        const TypedWindowSpec& s = w[k];
+        int ts = 0;
+        const int rc = check_strided_window(nchunks, nbytes, blocksize, typesize, s, &ts);
+        if (rc < 0) return rc;
+        const int osz = type_size(s.out_type);
+        if (!osz || type_size(s.src_type) != ts) return ERR_INVALID_PARAM;
+        if (!typed_identity(s) && s.out_type != T_F32 && s.out_type != T_F16) return ERR_INVALID_PARAM;
+        for (int i = s.chunk_first; i < s.chunk_first + s.chunk_count; i++) if (blocksize[i] % ts) return ERR_INVALID_PARAM;
+        if (s.elem_pitch < osz || s.elem_pitch % osz) return ERR_INVALID_PARAM;
+        if (rc) continue;
+        if (s.out_off % osz) return ERR_INVALID_PARAM;
+        if (s.width > 1 && s.elem_pitch > (INT64_MAX - osz) / (s.width - 1)) return ERR_INVALID_PARAM;
+        if (s.height > 1 && (s.out_pitch < (int64_t)(s.width - 1) * s.elem_pitch + osz || s.out_pitch % osz)) return ERR_INVALID_PARAM;
+    }
+    list_strided_items(nbytes, typesize, nwindows, w, plan, [](TypedWindowItem& t, const TypedWindowSpec& s) {
+        t.epitch = s.elem_pitch; t.src_type = s.src_type; t.out_type = s.out_type; t.scale = s.scale; t.offset = s.offset;
+    });
+    plan_totals(plan);
+    return 0;
+}
+
+// The order of a typed launch's decode units: by the output address of the first element each writes.  The windows of the C planes
+// of a pixel-major read fill the channel slots of the same cache lines from C workgroups; this puts those workgroups side by side
+// in the grid (stable: the channels stay in order).  Copy-mode units stay behind the others.
+inline void order_units_by_output(const std::vector<TypedWindowItem>& items, const std::vector<int32_t>& order, std::vector<WindowUnit>* units)
+{
+    size_t ndec = 0;
+    while (ndec < units->size() && items[(size_t)order[(size_t)(*units)[ndec].item0]].b >= 0) ndec++;
+    std::vector<std::pair<int64_t, int32_t>> keys(ndec);
+    for (size_t k = 0; k < ndec; k++) {
+        const TypedWindowItem& t = items[(size_t)order[(size_t)(*units)[k].item0]];
+        const int64_t rel = t.row0 + (int64_t)t.r0 * t.rpitch - t.p0;
+        const int64_t c_lo = rel >= 0 ? 0 : (-rel + t.cpitch - 1) / t.cpitch;
+        keys[k] = {t.out_off + (int64_t)t.r0 * t.out_pitch + c_lo * t.epitch, (int32_t)k};
+    }
+    std::sort(keys.begin(), keys.end());
+    std::vector<WindowUnit> sorted(ndec);
+    for (size_t k = 0; k < ndec; k++) sorted[k] = (*units)[(size_t)keys[k].second];
+    std::copy(sorted.begin(), sorted.end(), units->begin());
+}
+
+// run_windows' Env for a typed call (GroupedEnv's counterpart), over an Env that provides decode_whole and
+//   int run_typed_units(const TypedWindowPlan& plan, const std::vector<TypedWindowItem>& items, const std::vector<int32_t>& order,
+//                       const std::vector<WindowUnit>& units, int32_t* status)
+template <class Env>
+struct TypedEnv {
+    Env& env;
+    int64_t blocks = 0;
+
+    int decode_whole(const std::vector<int>& list, const std::vector<int64_t>& dst_off, int64_t total, int32_t* st)
+    {
+        return env.decode_whole(list, dst_off, total, st);
+    }
+    int run_items(const TypedWindowPlan& plan, const std::vector<TypedWindowItem>& items, int32_t* status)
+    {
+        if (items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
+        std::vector<int32_t> order;
+        std::vector<WindowUnit> units;
+        group_items(items, &order, &units);
+        order_units_by_output(items, order, &units);
+        const int rc = env.run_typed_units(plan, items, order, units, status);
+        if (rc < 0) return rc;
+        for (const WindowUnit& u : units) {
+            const TypedWindowItem& t = items[(size_t)order[(size_t)u.item0]];
+            if (t.b >= 0 && status[t.chunk] != STATUS_ZSTD_PENDING && status[t.chunk] != STATUS_ZSTD_PENDING_SPLIT) blocks++;
+        }
+        return 0;
+    }
+};
+
+// run_windows_grouped for typed windows: same status, return value and stats (distinct blocks)
+template <class Env>
+int run_windows_typed(Env& env, int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                      const TypedWindowSpec* w, std::vector<uint8_t> hint, int32_t* status, WindowStats* stats)
+{
+    if (nwindows > 0 && w && !grouped_counts_fit(nchunks, typesize, nwindows, w)) {
+        TypedWindowPlan plan;
+        const int rc = plan_windows(nchunks, nbytes, blocksize, typesize, nwindows, w, hint.empty() ? nullptr : hint.data(), &plan);
+        if (rc < 0) return rc;
+        if (plan.items.size() > (size_t)INT32_MAX) return ERR_INVALID_PARAM;
+    }
+    TypedEnv<Env> g{env};
     const int rc = run_windows(g, nchunks, nbytes, blocksize, typesize, nwindows, w, std::move(hint), status, stats);
     stats->blocks_decoded = g.blocks;
     return rc;

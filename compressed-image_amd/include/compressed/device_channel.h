@@ -163,6 +163,34 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 		}
 	}
 
+	namespace detail
+	{
+		/// The CIMG_T_* code of an element type (typed region reads).
+		template <typename U> constexpr int32_t typed_code()
+		{
+			if constexpr (std::is_same_v<U, uint8_t>) return CIMG_T_U8;
+			else if constexpr (std::is_same_v<U, int8_t>) return CIMG_T_I8;
+			else if constexpr (std::is_same_v<U, uint16_t>) return CIMG_T_U16;
+			else if constexpr (std::is_same_v<U, int16_t>) return CIMG_T_I16;
+			else if constexpr (std::is_same_v<U, uint32_t>) return CIMG_T_U32;
+			else if constexpr (std::is_same_v<U, int32_t>) return CIMG_T_I32;
+			else if constexpr (std::is_same_v<U, half>) return CIMG_T_F16;
+			else if constexpr (std::is_same_v<U, float>) return CIMG_T_F32;
+			else if constexpr (std::is_same_v<U, double>) return CIMG_T_F64;
+			else return -1;
+		}
+		/// What a typed read may produce from pixels stored as T: float, half, or T itself with scale 1 and offset 0.
+		template <typename T, typename U> void check_typed_result(float scale, float offset, const char* what)
+		{
+			static_assert(std::is_same_v<U, float> || std::is_same_v<U, half> || std::is_same_v<U, T>,
+				"a typed region read produces float, half or the stored type");
+			static_assert(typed_code<T>() >= 0, "typed region reads: unsupported element type");
+			if constexpr (!std::is_same_v<U, float> && !std::is_same_v<U, half>)
+				if (scale != 1.0f || offset != 0.0f)
+					throw std::invalid_argument(text(what, ": a result of the stored type takes scale 1 and offset 0 (float and half results are converted)"));
+		}
+	}
+
 	template <typename T> struct device_image;
 
 	template <typename T>
@@ -385,6 +413,62 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			detail::engine_call(e, cimg_decompress_windows_grouped_device(e, static_cast<int32_t>(m_Store->num_chunks()), m_Store->base,
 				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)),
 				static_cast<int32_t>(w.size()), w.data(), d_out, status.data()), "Decoding the regions");
+		}
+		/// The rectangle (subsampled) as U = float, half or T: y = fl32(fl32((float)v * scale) + offset), rounded once more for half --
+		/// numpy's (v.astype(float32) * float32(scale) + float32(offset)).astype(U), bit for bit -- converted in the decode launch
+		/// itself.  U = T takes scale 1 and offset 0 and copies the elements.
+		template <typename U>
+		void get_region(U* d_out, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, float scale, float offset) const
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			get_regions(d_out, std::span<const region>(&r, 1), scale, offset);
+		}
+		/// get_regions with every element converted as above: one engine call (cimg_decompress_windows_typed_device), each block decoded once.
+		template <typename U>
+		void get_regions(U* d_out, std::span<const region> regions, float scale, float offset) const
+		{
+			detail::check_typed_result<T, U>(scale, offset, "get_regions");
+			const size_t total = check_regions(regions);
+			require();
+			std::vector<cimg_window_typed> w;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				if (r.width && r.height) w.push_back(typed_window<U>(r, at * sizeof(U), sizeof(U), scale, offset));
+				at += r.out_elems();
+			}
+			if (w.empty()) return;
+			detail::device_range(m_Store->engine, d_out, total * sizeof(U), "get_regions");
+			run_typed(*m_Store, w, d_out);
+		}
+		/// A region as a typed window over this channel's chunks: element c of row r at out_off + (r * out_width + c) * elem_pitch.
+		template <typename U>
+		cimg_window_typed typed_window(const region& r, size_t out_off, size_t elem_pitch, float scale, float offset) const
+		{
+			const cimg_window_strided s = region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, out_off);
+			cimg_window_typed w{};
+			w.chunk_first = s.chunk_first; w.chunk_count = s.chunk_count;
+			w.origin = s.origin; w.row_pitch = s.row_pitch; w.col_pitch = s.col_pitch;
+			w.width = s.width; w.height = s.height;
+			w.out_off = s.out_off;
+			w.elem_pitch = static_cast<int64_t>(elem_pitch);
+			w.out_pitch = static_cast<int64_t>(static_cast<size_t>(s.width) * elem_pitch);
+			w.src_type = detail::typed_code<T>();
+			w.out_type = detail::typed_code<U>();
+			w.scale = scale; w.offset = offset;
+			return w;
+		}
+		/// One typed windows call over a store.  (A member template's body: only code that asks for typed reads refers to the entry point.)
+		template <typename Window = cimg_window_typed>
+		static void run_typed(const detail::device_store& store, const std::vector<Window>& w, void* d_out)
+		{
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("get_regions: too many regions for one call");
+			cimg_engine* e = store.engine;
+			std::vector<int32_t> status(store.num_chunks(), 0);
+			detail::engine_lock lock(e);
+			detail::engine_call(e, cimg_decompress_windows_typed_device(e, static_cast<int32_t>(store.num_chunks()), store.base, store.off.data(),
+				store.cbytes.data(), store.nbytes.data(), store.blocksize.data(), static_cast<int32_t>(sizeof(T)), static_cast<int32_t>(w.size()), w.data(),
+				d_out, status.data()), "Decoding the typed regions");
 		}
 		/// Every region checked as get_region checks it; returns the elements of all results together.
 		size_t check_regions(std::span<const region> regions) const

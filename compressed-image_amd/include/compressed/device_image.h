@@ -229,6 +229,46 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				m_Store->off.data(), m_Store->cbytes.data(), m_Store->nbytes.data(), m_Store->blocksize.data(), static_cast<int32_t>(sizeof(T)),
 				static_cast<int32_t>(w.size()), w.data(), d_out, status.data()), "Decoding the regions");
 		}
+		/// The rectangle of every channel (subsampled) as U = float, half or T, channel c converted with scales[c] and offsets[c] (a span
+		/// of one value serves every channel) in the decode launch itself: planes (C, oh, ow) or, with `interleaved`, pixels (oh, ow, C)
+		/// written in place by that one launch -- no scratch, no interleave launch, no alignment rule beyond U's own.
+		template <typename U>
+		void get_region(U* d_out, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, std::span<const float> scales,
+			std::span<const float> offsets, bool interleaved = false) const
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			get_regions(d_out, std::span<const region>(&r, 1), scales, offsets, interleaved);
+		}
+		/// Many rectangles of every channel, converted as above, in ONE engine call: (N, C, oh, ow) or, with `interleaved`, (N, oh, ow, C)
+		/// for N regions of one shape (results back to back in region order otherwise).
+		template <typename U>
+		void get_regions(U* d_out, std::span<const region> regions, std::span<const float> scales, std::span<const float> offsets, bool interleaved = false) const
+		{
+			if ((scales.size() != 1 && scales.size() != m_NumChannels) || (offsets.size() != 1 && offsets.size() != m_NumChannels))
+				throw std::invalid_argument(detail::text("get_regions: scales and offsets hold one value or one per channel (", m_NumChannels, ")"));
+			for (size_t c = 0; c < std::max(scales.size(), offsets.size()); ++c)
+				detail::check_typed_result<T, U>(scales[scales.size() == 1 ? 0 : c], offsets[offsets.size() == 1 ? 0 : c], "get_regions");
+			const size_t per_channel = prototype().check_regions(regions);
+			if (m_NumChannels == 0) return;
+			std::vector<cimg_window_typed> w;
+			size_t at = 0;                                                       // elements of U before this region
+			for (const region& r : regions)
+			{
+				for (size_t c = 0; c < m_NumChannels && r.width && r.height; ++c)
+				{
+					device_channel<T> p = prototype();
+					p.m_First = c * chunks_per_channel();
+					p.m_Count = chunks_per_channel();
+					const float sc = scales[scales.size() == 1 ? 0 : c], of = offsets[offsets.size() == 1 ? 0 : c];
+					if (interleaved) w.push_back(p.template typed_window<U>(r, (at + c) * sizeof(U), m_NumChannels * sizeof(U), sc, of));
+					else w.push_back(p.template typed_window<U>(r, (at + c * r.out_elems()) * sizeof(U), sizeof(U), sc, of));
+				}
+				at += r.out_elems() * m_NumChannels;
+			}
+			if (w.empty()) return;
+			detail::device_range(m_Store->engine, d_out, per_channel * m_NumChannels * sizeof(U), "get_regions");
+			device_channel<T>::run_typed(*m_Store, w, d_out);
+		}
 		/// Write planes (num_channels x height x width elements in device memory, channel-major) over the rectangle of every channel:
 		/// one update call, one repack of the store.  Nothing changes unless the whole call succeeds.
 		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height)

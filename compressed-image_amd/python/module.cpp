@@ -656,6 +656,33 @@ namespace
 		if (v.readonly) throw py::value_error(std::string(what) + ": out is read-only");
 		return { static_cast<T*>(v.ptr), out };
 	}
+	// ---- typed reads (device_channel.h / device_image.h: get_region<U>, get_regions<U>) ----
+	// scale= / offset=: a number, or a sequence of one value per channel
+	inline std::vector<float> float_list(const py::object& o, size_t channels, const char* name)
+	{
+		std::vector<float> v;
+		if (py::hasattr(o, "__len__")) for (auto h : o) v.push_back(static_cast<float>(h.cast<double>()));
+		else v.push_back(static_cast<float>(o.cast<double>()));
+		if (v.size() != 1 && v.size() != channels)
+			throw py::value_error(std::string(name) + ": expected a number or one value per channel (" + std::to_string(channels) + "), got " + std::to_string(v.size()));
+		return v;
+	}
+	// without dtype= nothing is converted: scale and offset must be left at 1 and 0
+	inline void require_plain(const std::vector<float>& scales, const std::vector<float>& offsets, const char* what)
+	{
+		for (float s : scales) if (s != 1.0f) throw py::value_error(std::string(what) + ": scale needs dtype= (float32, float16)");
+		for (float o : offsets) if (o != 0.0f) throw py::value_error(std::string(what) + ": offset needs dtype= (float32, float16)");
+	}
+	// f.template operator()<U>() for the result type dtype= names: the stored type T, float or half
+	template <typename T, typename F> py::object typed_dispatch(const py::object& dtype, F&& f, const char* what)
+	{
+		const py::dtype dt = as_dtype(dtype);
+		if (dt.is(np_dtype<T>())) return f.template operator()<T>();
+		if (dt.is(np_dtype<float>())) return f.template operator()<float>();
+		if (dt.is(np_dtype<compressed::half>())) return f.template operator()<compressed::half>();
+		throw py::value_error(std::string(what) + ": dtype must be float32, float16 or the stored dtype, got " + std::string(py::str(dt)));
+	}
+
 	inline void check_region_args(py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h)
 	{
 		if (x < 0 || y < 0 || w < 0 || h < 0) throw py::value_error("region coordinates and sizes must be >= 0");
@@ -719,12 +746,22 @@ namespace
 			});
 		}
 		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, std::optional<uintptr_t> stream,
-			py::ssize_t step_x, py::ssize_t step_y) const
+			py::ssize_t step_x, py::ssize_t step_y, const py::object& dtype, const py::object& scale, const py::object& offset) const
 		{
 			check_region_args(x, y, width, height);
 			check_steps(step_x, step_y);
-			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
+			if (dtype.is_none()) require_plain(sc, of, "get_region");
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) -> py::object {
 				ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
+				if (!dtype.is_none())
+					return typed_dispatch<T>(dtype, [&]<typename U>() -> py::object {
+						auto [p, ret] = result_target<U>(out, { ceil_div(height, step_y), ceil_div(width, step_x) }, "get_region");
+						wait_for(stream);
+						ch.get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height),
+							static_cast<size_t>(step_x), static_cast<size_t>(step_y), sc[0], of[0]);
+						return ret;
+					}, "get_region");
 				auto [p, ret] = result_target<T>(out, { ceil_div(height, step_y), ceil_div(width, step_x) }, "get_region");
 				wait_for(stream);
 				if (step_x == 1 && step_y == 1)
@@ -737,11 +774,22 @@ namespace
 		}
 		// Channel.get_regions / get_pixels into device memory: `out` or a new DeviceArray
 		py::object get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& out,
-			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels) const
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels, const py::object& dtype = py::none(),
+			const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0)) const
 		{
 			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
-			return visit([&]<typename T>(compressed::device_channel<T>& ch) {
+			const char* what = pixels ? "get_pixels" : "get_regions";
+			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
+			if (dtype.is_none()) require_plain(sc, of, what);
+			return visit([&]<typename T>(compressed::device_channel<T>& ch) -> py::object {
 				ch.check_regions(regions);
+				if (!dtype.is_none())
+					return typed_dispatch<T>(dtype, [&]<typename U>() -> py::object {
+						auto [p, ret] = result_target<U>(out, regions_shape(regions.size(), std::nullopt, width, height, step_x, step_y, pixels), what);
+						wait_for(stream);
+						ch.get_regions(p, std::span<const compressed::region>(regions), sc[0], of[0]);
+						return ret;
+					}, what);
 				auto [p, ret] = result_target<T>(out, regions_shape(regions.size(), std::nullopt, width, height, step_x, step_y, pixels),
 					pixels ? "get_pixels" : "get_regions");
 				wait_for(stream);
@@ -901,13 +949,24 @@ namespace
 			});
 		}
 		py::object get_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& out, bool interleaved,
-			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y) const
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, const py::object& dtype, const py::object& scale,
+			const py::object& offset) const
 		{
 			check_region_args(x, y, width, height);
 			check_steps(step_x, step_y);
-			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+			return visit([&]<typename T>(const dimg_ptr<T>& img) -> py::object {
+				const std::vector<float> sc = float_list(scale, img->num_channels(), "scale"), of = float_list(offset, img->num_channels(), "offset");
+				if (dtype.is_none()) require_plain(sc, of, "get_region");
 				if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height));
 				const py::ssize_t C = static_cast<py::ssize_t>(img->num_channels()), oh = ceil_div(height, step_y), ow = ceil_div(width, step_x);
+				if (!dtype.is_none())
+					return typed_dispatch<T>(dtype, [&]<typename U>() -> py::object {
+						auto [p, ret] = result_target<U>(out, interleaved ? std::vector<py::ssize_t>{ oh, ow, C } : std::vector<py::ssize_t>{ C, oh, ow }, "get_region");
+						wait_for(stream);
+						img->get_region(p, static_cast<size_t>(x), static_cast<size_t>(y), static_cast<size_t>(width), static_cast<size_t>(height),
+							static_cast<size_t>(step_x), static_cast<size_t>(step_y), std::span<const float>(sc), std::span<const float>(of), interleaved);
+						return ret;
+					}, "get_region");
 				auto [p, ret] = result_target<T>(out, interleaved ? std::vector<py::ssize_t>{ oh, ow, C } : std::vector<py::ssize_t>{ C, oh, ow }, "get_region");
 				wait_for(stream);
 				if (step_x == 1 && step_y == 1)
@@ -919,12 +978,29 @@ namespace
 			});
 		}
 		// Image.get_regions / get_pixels into device memory: `out` or a new DeviceArray
+		// (interleaved: (N, oh, ow, C) -- with or without dtype= a typed call, which places each channel's elements in its slots)
 		py::object get_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& out,
-			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels) const
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, bool pixels, const py::object& dtype = py::none(),
+			const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0), bool interleaved = false) const
 		{
 			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
-			return visit([&]<typename T>(const dimg_ptr<T>& img) {
+			const char* what = pixels ? "get_pixels" : "get_regions";
+			return visit([&]<typename T>(const dimg_ptr<T>& img) -> py::object {
+				const std::vector<float> sc = float_list(scale, img->num_channels(), "scale"), of = float_list(offset, img->num_channels(), "offset");
+				if (dtype.is_none()) require_plain(sc, of, what);
 				if (img->num_channels()) img->channel(0).check_regions(regions);
+				if (!dtype.is_none() || interleaved)
+				{
+					const py::object want = dtype.is_none() ? py::object(np_dtype<T>()) : dtype;
+					return typed_dispatch<T>(want, [&]<typename U>() -> py::object {
+						std::vector<py::ssize_t> shape = regions_shape(regions.size(), img->num_channels(), width, height, step_x, step_y, pixels);
+						if (interleaved && !pixels) shape = { shape[0], shape[2], shape[3], shape[1] };
+						auto [p, ret] = result_target<U>(out, shape, what);
+						wait_for(stream);
+						img->get_regions(p, std::span<const compressed::region>(regions), std::span<const float>(sc), std::span<const float>(of), interleaved);
+						return ret;
+					}, what);
+				}
 				auto [p, ret] = result_target<T>(out, regions_shape(regions.size(), img->num_channels(), width, height, step_x, step_y, pixels),
 					pixels ? "get_pixels" : "get_regions");
 				wait_for(stream);
@@ -1125,14 +1201,18 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("read_only", [](const DeviceChannel& c) { return c.visit([](auto& ch) { return ch.read_only(); }); })
 		.def("get_decompressed", &DeviceChannel::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceChannel::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
-			py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+			py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0,
+			py::arg("offset") = 0.0)
 		.def("get_regions", [](const DeviceChannel& c, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& out,
-				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy) { return c.get_regions(xs, ys, w, h, out, stream, sx, sy, false); },
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset) {
+				return c.get_regions(xs, ys, w, h, out, stream, sx, sy, false, dtype, scale, offset); },
 			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt,
-			py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("get_pixels", [](const DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream) {
-				return c.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
-			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0)
+		.def("get_pixels", [](const DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream,
+				const py::object& dtype, const py::object& scale, const py::object& offset) {
+				return c.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true, dtype, scale, offset); },
+			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(),
+			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
 		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
 			py::arg("step_x") = 1, py::arg("step_y") = 1)
@@ -1159,14 +1239,19 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("channel", &DeviceImage::channel, py::arg("key"))
 		.def("get_decompressed", &DeviceImage::get_decompressed, py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
 		.def("get_region", &DeviceImage::get_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(),
-			py::arg("interleaved") = false, py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
+			py::arg("interleaved") = false, py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(),
+			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("get_regions", [](const DeviceImage& i, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& out,
-				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy) { return i.get_regions(xs, ys, w, h, out, stream, sx, sy, false); },
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset,
+				bool interleaved) { return i.get_regions(xs, ys, w, h, out, stream, sx, sy, false, dtype, scale, offset, interleaved); },
 			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt,
-			py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("get_pixels", [](const DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream) {
-				return i.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true); },
-			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt)
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0,
+			py::arg("interleaved") = false)
+		.def("get_pixels", [](const DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& out, std::optional<uintptr_t> stream,
+				const py::object& dtype, const py::object& scale, const py::object& offset) {
+				return i.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true, dtype, scale, offset); },
+			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(),
+			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
 			py::arg("step_x") = 1, py::arg("step_y") = 1)
 		.def("set_regions", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,

@@ -245,6 +245,40 @@ int cimg_decompress_windows_grouped_device(cimg_engine* e, int32_t nchunks, cons
 int cimg_decompress_windows_grouped_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                                          const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
                                          int32_t* status);
+/* Typed windows: convert, scale and place each element in the launch.  A typed window is a cimg_window_strided plus the memory
+ * side: element c of row r goes to d_out + out_off + r * out_pitch + c * elem_pitch as out_type; the bytes between elements are
+ * not written, so the windows of C planes can fill pixel-major rows (elem_pitch = C * size of out_type) in one launch.  For a
+ * stored value v, each step rounded to nearest even: x = (float)v (exact for 8 / 16-bit integers and float16; int32, uint32 and
+ * float64 take one rounding), y = fl32(fl32(x * scale) + offset) -- two roundings, not a fused multiply-add, float32 denormals
+ * kept --, and the output is y (CIMG_T_F32) or y rounded once to float16 (CIMG_T_F16: overflow gives inf, subnormals are kept).
+ * That is numpy's (v.astype(float32) * float32(scale) + float32(offset)).astype(out), bit for bit.  A window with
+ * out_type == src_type, scale 1 and offset 0 copies each element's bytes unchanged (NaN payloads and -0 survive); any other window
+ * with an integer or CIMG_T_F64 out_type is refused.
+ * Grouping, locking, voiding of pending _begin calls, status[], the return value and cimg_engine_window_stats are those of
+ * cimg_decompress_windows_grouped_device: one workgroup per distinct block, each block staged once however many windows meet it;
+ * a call whose windows are all identity with elem_pitch == typesize gives that call's bytes, status and stats.  The launch is
+ * cimg_decode_window_typed (CIMG_K_DECODE_WINDOW_TYPED).  Nothing runs, and the call returns BLOSC2_ERROR_INVALID_PARAM, unless
+ * every window passes the checks of the strided windows -- but for out_pitch, which here must be at least
+ * (width - 1) * elem_pitch + the size of out_type when height > 1 -- and: both types are known; the size of src_type is
+ * `typesize`; elem_pitch is at least the size of out_type; out_off, out_pitch (height > 1), elem_pitch and d_out are multiples of
+ * the size of out_type (every element is one naturally aligned store); and, for every chunk of the window's plane, blocksize -- and
+ * nbytes unless it is the plane's last chunk -- is a multiple of typesize (a converted element must not straddle two blocks).
+ * There is no _host form: converting uint8 to float32 before PCIe would quadruple the traffic, and the host-resident classes
+ * return one array per channel; host callers read windows in the stored type and convert where the pixels land. */
+enum { CIMG_T_U8 = 0, CIMG_T_I8 = 1, CIMG_T_U16 = 2, CIMG_T_I16 = 3, CIMG_T_U32 = 4, CIMG_T_I32 = 5, CIMG_T_F16 = 6, CIMG_T_F32 = 7,
+       CIMG_T_F64 = 8 };
+typedef struct cimg_window_typed {
+    int32_t chunk_first, chunk_count;
+    int64_t origin, row_pitch, col_pitch;
+    int32_t width, height;
+    int64_t out_off, out_pitch;      /* bytes */
+    int64_t elem_pitch;              /* bytes; >= size of out_type */
+    int32_t src_type, out_type;      /* CIMG_T_* */
+    float scale, offset;
+} cimg_window_typed;
+int cimg_decompress_windows_typed_device(cimg_engine* e, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                         const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, int32_t typesize,
+                                         int32_t nwindows, const cimg_window_typed* w, void* d_out, int32_t* status);
 
 /* ---- window writes: edit compressed planes in place of get_chunk + set_chunk ------------------------
  * The windows are cimg_window, with out_off / out_pitch describing the SOURCE: row r of a window is taken from
@@ -376,7 +410,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* BloscLZ streams beyond 65 535 bytes (blocks up to 256 KiB): the wide encoder's BloscLZ instance */
        CIMG_K_ENCODE_WIDE_BLOSCLZ = 25,
        /* the patch launch of cimg_update_windows_strided_device / _host */
-       CIMG_K_UPDATE_PATCH_STRIDED = 26, CIMG_K_COUNT = 27 };
+       CIMG_K_UPDATE_PATCH_STRIDED = 26,
+       /* the window launch of cimg_decompress_windows_typed_device */
+       CIMG_K_DECODE_WINDOW_TYPED = 27, CIMG_K_COUNT = 28 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

@@ -29,6 +29,13 @@ Strided write leg, in a child process (`--write-strided-l
       into a device-resident 4096^2 float16 plane (lz4 + shuffle, 32 KiB blocks) through the strided call against the same 4096
       1 x 1 windows through the plain call; every 4th pixel in x and y of a 2048^2 region of that plane through
       DeviceChannel.set_region(..., step_x=4, step_y=4) against get_region of the rectangle + a torch scatter + set_region.
+Typed leg, a process of its own (`python tools/diag_windows.py --typed-leg [--out file]`, torch first; it does
+not build the plane of (1)) that writes profiles/typed/diag_windows_typed.json:
+  (8) 256 seeded random 224^2 crops of a 3 x 4096^2 uint8 DeviceImage (lz4 + shuffle) as float32 with per-channel scale / offset,
+      planar and pixel-major, through get_regions(dtype=, scale=, offset=[, interleaved=True]) against get_regions followed by
+      torch's .float().mul_().add_() (and .permute().contiguous()); one 2048^2 crop of a 4 x 4096^2 float16 DeviceImage pixel-major
+      in its own type through get_region(dtype=float16, interleaved=True) against get_region(interleaved=True).  The two routes
+      alternate; kernel time (the shared engine's HIP events plus torch events around torch's part) and wall time, medians of REPS.
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -41,7 +48,8 @@ import time
 STRIDED_LEG = "--strided-leg" in sys.argv
 GROUPED_LEG = "--grouped-leg" in sys.argv
 WRITE_STRIDED_LEG = "--write-strided-leg" in sys.argv
-if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG:
+TYPED_LEG = "--typed-leg" in sys.argv
+if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG or TYPED_LEG:
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +58,94 @@ import numpy as np  # noqa: E402
 from cimg import hip, synth  # noqa: E402
 
 REPS = 10
+
+
+def typed_leg():
+    """(8): typed reads of the device classes against the routes they replace"""
+    import ctypes as C
+    path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
+    spec_m = importlib.util.spec_from_file_location("compressed_image", path)
+    ci = importlib.util.module_from_spec(spec_m)
+    spec_m.loader.exec_module(ci)
+    m = 4096
+    planes8 = np.stack([synth.tiled_channel(np.uint8, m, m, c=k) for k in range(3)])
+    img8 = ci.DeviceImage(np.uint8, torch.from_numpy(planes8).cuda(), m, m)
+    planes16 = np.stack([synth.tiled_channel(np.float16, m, m, c=k) for k in range(4)])
+    img16 = ci.DeviceImage(np.float16, torch.from_numpy(planes16).cuda(), m, m)
+    L = hip.load()
+    L.cimg_shared_engine.restype = C.c_void_p
+    se = hip.Engine.__new__(hip.Engine)                    # the module's engine, for its kernel times
+    se.handle = C.c_void_p(L.cimg_shared_engine())
+    windows = (hip.K_DECODE_WINDOW, hip.K_DECODE_WINDOW_STRIDED, hip.K_DECODE_WINDOW_GROUPED, hip.K_DECODE_WINDOW_TYPED, hip.K_INTERLEAVE)
+    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def alternating(old, new, old_has_torch):
+        old(); new()
+        torch.cuda.synchronize()
+        se.enable_timing(1)
+        rows = {"old": ([], []), "typed": ([], [])}
+        for _ in range(REPS):
+            for name, f in (("old", old), ("typed", new)):
+                se.reset_timing()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                rows[name][0].append((time.perf_counter() - t) * 1e6)
+                k = sum(se.kernel_time(kid)[0] for kid in windows) * 1e3
+                rows[name][1].append(k + (ev_a.elapsed_time(ev_b) * 1e3 if name == "old" and old_has_torch else 0.0))
+        se.enable_timing(0)
+        return {name: dict(wall_us=round(float(np.median(wl)), 1), wall_min_us=round(float(np.min(wl)), 1), wall_max_us=round(float(np.max(wl)), 1),
+                           kernel_us=round(float(np.median(kl)), 1)) for name, (wl, kl) in rows.items()}
+
+    out = {}
+    rng = np.random.default_rng(8)
+    N, c = 256, 224
+    xs, ys = rng.integers(0, m - c, N), rng.integers(0, m - c, N)
+    scale, offset = [1 / (255 * 0.229), 1 / (255 * 0.224), 1 / (255 * 0.225)], [-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225]
+    sc_t = torch.tensor(scale, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    of_t = torch.tensor(offset, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    u8 = torch.empty((N, 3, c, c), dtype=torch.uint8, device="cuda")
+    for il in (False, True):
+        res_new = torch.empty((N, c, c, 3) if il else (N, 3, c, c), dtype=torch.float32, device="cuda")
+        kept = []
+
+        def old():
+            img8.get_regions(xs, ys, c, c, out=u8)
+            ev_a.record()
+            f = u8.float().mul_(sc_t).add_(of_t)
+            kept[:] = [f.permute(0, 2, 3, 1).contiguous() if il else f]
+            ev_b.record()
+
+        def new():
+            img8.get_regions(xs, ys, c, c, out=res_new, dtype=np.float32, scale=scale, offset=offset, interleaved=il)
+
+        r = alternating(old, new, True)
+        r["bit_equal"] = bool(torch.equal(kept[0].view(torch.int32), res_new.view(torch.int32)))
+        r["result_bytes"] = res_new.numel() * 4
+        r["old_temporary_bytes"] = u8.numel() + (res_new.numel() * 4 if il else 0)       # the uint8 crops; and the planar floats under permute
+        out["crops256_224_u8_f32_" + ("pixel_major" if il else "planar")] = r
+        del kept[:]
+    x0, y0, w2 = 1000, 1500, 2048
+    a16 = torch.empty((w2, w2, 4), dtype=torch.float16, device="cuda")
+    b16 = torch.empty((w2, w2, 4), dtype=torch.float16, device="cuda")
+    r = alternating(lambda: img16.get_region(x0, y0, w2, w2, out=a16, interleaved=True),
+                    lambda: img16.get_region(x0, y0, w2, w2, out=b16, interleaved=True, dtype=np.float16), False)
+    r["bit_equal"] = bool(torch.equal(a16.view(torch.int16), b16.view(torch.int16)))
+    r["result_bytes"] = a16.numel() * 2
+    r["old_temporary_bytes"] = a16.numel() * 2                                            # the scratch planes the interleave launch reads
+    out["crop_2048_f16x4_pixel_major"] = r
+    return out
+
+
+if TYPED_LEG:
+    line = json.dumps(typed_leg())
+    print("TYPED " + line)
+    dst = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "typed", "diag_windows_typed.json")
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    open(dst, "w").write(line + "\n")
+    sys.exit(0)
+
 res = {}
 eng = hip.Engine(0)
 n, chunk = 16384, 4 << 20
