@@ -24,6 +24,7 @@ K_DECODE_WINDOW_GROUPED = 24                   # grouped windows: every block st
 K_ENCODE_WIDE_BLOSCLZ = 25                     # BloscLZ streams beyond 65 535 bytes: the wide encoder's BloscLZ instance (csrc/wide_kernel.h)
 K_UPDATE_PATCH_STRIDED = 26                    # strided window writes: the patch launch of cimg_update_windows_strided_* (csrc/update_kernel.h)
 K_DECODE_WINDOW_TYPED = 27                     # typed windows: convert, scale and place each element in the launch (csrc/window_kernel.h)
+K_UPDATE_PATCH_TYPED = 28                      # typed window writes: unscale, round and store each element in the patch launch (csrc/update_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -32,7 +33,7 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
            "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz", "cimg_update_patch_strided",
-           "cimg_decode_window_typed")
+           "cimg_decode_window_typed", "cimg_update_patch_typed")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -57,7 +58,7 @@ EXPORTS = (
     "cimg_decompress_windows_strided_device", "cimg_decompress_windows_strided_host",
     "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host", "cimg_decompress_windows_typed_device",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
-    "cimg_update_windows_strided_device", "cimg_update_windows_strided_host",
+    "cimg_update_windows_strided_device", "cimg_update_windows_strided_host", "cimg_update_windows_typed_device",
     "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
     "cimg_interleave_device", "cimg_engine_wait_stream", "cimg_device_range_check",
     # include/blosc2.h
@@ -232,6 +233,8 @@ def load():
     L.cimg_engine_update_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
     L.cimg_update_windows_strided_device.argtypes = L.cimg_update_windows_device.argtypes
     L.cimg_update_windows_strided_host.argtypes = L.cimg_update_windows_host.argtypes
+    if hasattr(L, "cimg_update_windows_typed_device"):          # (a CIMG_LIB build from before it)
+        L.cimg_update_windows_typed_device.argtypes = L.cimg_update_windows_device.argtypes
     L.cimg_compress_batch_device_packed_begin.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp]
     L.cimg_compress_batch_device_packed_fetch.argtypes = [vp, C.c_int32, vp, vp]
     L.cimg_pack_chunks_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
@@ -569,6 +572,23 @@ class Engine:
         """update_windows_device over cimg_window_strided specs (with col_pitch): cimg_update_windows_strided_device"""
         return self.update_windows_device(p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size, check,
                                           strided=True)
+
+    def update_windows_typed_device(self, p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_new, new_off, comp_size=None,
+                                    check=True, new_cbytes=None, status=None):
+        """typed windows (cimg_window_typed specs; out_off / out_pitch / elem_pitch / out_type describe the SOURCE at d_src) converted
+        and written into device-resident chunks through cimg_update_windows_typed_device.  Returns as update_windows_device does;
+        new_cbytes / status: int32 arrays to hand to the call in place of fresh zeros."""
+        comp_off, nbytes, blocksize, destsize, new_off = _i64(comp_off), _i32(nbytes), _i32(blocksize), _i32(destsize), _i64(new_off)
+        cs = _i32(comp_size) if comp_size is not None else None
+        status = np.zeros(nbytes.size, np.int32) if status is None else status
+        ncb = np.zeros(nbytes.size, np.int32) if new_cbytes is None else new_cbytes
+        rc = load().cimg_update_windows_typed_device(self.handle, C.byref(p), nbytes.size, d_comp, _ptr(comp_off),
+                                                     _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), _ptr(destsize),
+                                                     len(specs), typed_windows(specs), d_src, d_new, _ptr(new_off), _ptr(ncb), _ptr(status))
+        if check:
+            self._check(rc)
+            return ncb, status
+        return rc, ncb, status
 
     def update_windows_strided_host(self, p, chunks, destsize, specs, src, check=True):
         """update_windows_host over cimg_window_strided specs: cimg_update_windows_strided_host"""

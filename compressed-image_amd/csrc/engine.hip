@@ -336,6 +336,30 @@ extern "C" __global__ __launch_bounds__(256) void cimg_update_patch_strided(Stri
     }
 }
 
+// Typed window writes: staging and schedules as above; the overlays of TypedPatchBlock load each written element as float32 / float16,
+// unscale and round it, and store it as the plane's type.
+extern "C" __global__ __launch_bounds__(256) void cimg_update_patch_typed(TypedPatchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    TypedPatchBlock tb(a, lds, (int)blockIdx.x);
+    tb.pb.phase_a(wave);
+    __syncthreads();
+    tb.pb.phase_base(wave);
+    __syncthreads();
+    const int n = tb.pb.u.nitems;
+    if (n == 1) {
+        tb.overlay(0, wave * 64, 256);
+    } else if (tb.disjoint) {
+        for (int k = wave; k < n; k += 4) tb.overlay(k, 0, 64);
+    } else {
+        for (int k = 0; k < n; k++) {
+            if (k) __syncthreads();                                  // (a later window wins where two overlap)
+            tb.overlay(k, wave * 64, 256);
+        }
+    }
+}
+
 // Splice: one wave lays out each spliced chunk (old streams of untouched blocks, new streams of re-encoded ones); then one workgroup
 // per block copies the streams into place.
 extern "C" __global__ __launch_bounds__(64) void cimg_update_layout(SpliceArgs a)
@@ -457,7 +481,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16) / typed window decode (17)
+    int max_dyn_lds[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16) / typed window decode (17) / typed window-write patch (18)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -664,6 +688,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_DECODE_WINDOW_TYPED: return "cimg_decode_window_typed";
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_PATCH_STRIDED: return "cimg_update_patch_strided";
+    case CIMG_K_UPDATE_PATCH_TYPED: return "cimg_update_patch_typed";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
     case CIMG_K_PACK: return "cimg_pack_chunks";
@@ -2535,8 +2560,15 @@ struct EngineUpdateEnv : EngineChunks {
     {
         return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
     }
+    int patch_typed(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<StridedPatchUnit>& units,
+                    const std::vector<WindowItem>& stage, const std::vector<TypedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                    int32_t* status)
+    {
+        return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
+    }
 
-    // cimg_update_patch over PatchUnit / WindowItem, or cimg_update_patch_strided over StridedPatchUnit / StridedWindowItem
+    // cimg_update_patch over PatchUnit / WindowItem, cimg_update_patch_strided over StridedPatchUnit / StridedWindowItem, or
+    // cimg_update_patch_typed over StridedPatchUnit / TypedWindowItem
     template <class Unit, class Item>
     int patch_launch(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<Unit>& units, const std::vector<WindowItem>& stage,
                      const std::vector<Item>& items, int to_whole, int64_t patch_bytes, int32_t* status)
@@ -2559,7 +2591,11 @@ struct EngineUpdateEnv : EngineChunks {
         pa.src = d_src;
         pa.dst = (uint8_t*)(to_whole ? e->win_whole.p : e->upd_patch.p);
         pa.nunits = (int32_t)units.size();
-        if constexpr (std::is_same_v<Item, StridedWindowItem>) {
+        if constexpr (std::is_same_v<Item, TypedWindowItem>) {
+            const TypedPatchArgs ta{pa, (const StridedPatchUnit*)e->upd_units.p, (const TypedWindowItem*)e->upd_items.p};
+            if ((rc = e->allow_lds(cimg_update_patch_typed, 18, lds_bytes))) return rc;
+            rc = e->launch(CIMG_K_UPDATE_PATCH_TYPED, cimg_update_patch_typed, ta, (int)units.size(), 256, lds_bytes);
+        } else if constexpr (std::is_same_v<Item, StridedWindowItem>) {
             const StridedPatchArgs sa{pa, (const StridedPatchUnit*)e->upd_units.p, (const StridedWindowItem*)e->upd_items.p};
             if ((rc = e->allow_lds(cimg_update_patch_strided, 16, lds_bytes))) return rc;
             rc = e->launch(CIMG_K_UPDATE_PATCH_STRIDED, cimg_update_patch_strided, sa, (int)units.size(), 256, lds_bytes);
@@ -2747,6 +2783,27 @@ int cimg_update_windows_strided_host(cimg_engine* e, const cimg_cparams* p, int3
 {
     return update_host_call(e, p, nchunks, h_comp, comp_off, comp_size, destsize, nwindows, reinterpret_cast<const StridedWindowSpec*>(w),
                             h_src, alloc, user, new_chunks, new_cbytes, status);
+}
+
+// The typed checks run before the call touches status or new_cbytes (update_plan.h: check_typed_update); everything else is the
+// strided call's.
+int cimg_update_windows_typed_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                     const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                                     int32_t nwindows, const cimg_window_typed* w, const void* d_src, void* d_new,
+                                     const int64_t* new_off, int32_t* new_cbytes, int32_t* status)
+{
+    const TypedWindowSpec* tw = reinterpret_cast<const TypedWindowSpec*>(w);
+    if (nchunks > 0 && nwindows > 0 && p && tw && nbytes && blocksize &&
+        check_typed_update(nchunks, nbytes, blocksize, p->typesize, nwindows, tw, d_src) < 0) {
+        std::lock_guard<std::recursive_mutex> lock_(e->mu);
+        e->upd_stats = UpdateStats{};
+        return e->fail(ERR_INVALID_PARAM, "invalid typed update: the checks of a strided window write and of a typed window (known types, src_type of "
+                                          "the plane's typesize, float32 / float16 or the stored type in memory, elem_pitch, out_pitch, out_off "
+                                          "and d_src multiples of the memory type's size, blocks of whole elements), a finite non-zero scale and a "
+                                          "finite offset; float64 planes and integer memory types take the identity only");
+    }
+    return update_device_call(e, p, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, tw, d_src, d_new, new_off,
+                              new_cbytes, status);
 }
 
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole, int64_t* bytes_uploaded)

@@ -8,6 +8,9 @@
 //                       block the windows cover completely is not staged: only the source bytes are copied.
 //   cimg_update_patch_strided
 //                       the same for windows with a col_pitch (StridedPatchBlock, below): same staging, its own overlay and schedule.
+//   cimg_update_patch_typed
+//                       the same for typed windows (TypedPatchBlock, below): every written element is loaded as float32 / float16,
+//                       unscaled, rounded and stored as the plane's type on its way into the unit.
 //   cimg_update_layout  one wave per spliced chunk.  Lane j takes block j: a touched block's size comes from the stream records the
 //                       encode launch left for it; an untouched block's streams are harvested from the old chunk (a negative csize
 //                       word is a run, csize == neblock raw, anything else a coded stream whose payload stays where it is).  A wave
@@ -227,6 +230,113 @@ struct StridedPatchBlock {
                         } else {
                             for (int i = 0; i < ts; i++)
                                 if (at + i >= 0 && at + i < len) d[i] = s[i];
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// ---- typed patch: cimg_update_patch_typed -----------------------------------------------------------------------------------------
+// The patch kernel of the typed write call, the inverse of cimg_decode_window_typed.  Units, staging and the two schedules are those
+// of the strided patch kernel; the overlay always walks elements, one lane an element: element c of window row r is loaded from
+// src + out_off + r * out_pitch + c * epitch as out_type (one naturally aligned load), converted -- typed_unscale, then
+// typed_store_bits for the plane's src_type -- and stored at plane byte row0 + r * rpitch + c * cpitch.  An item whose out_type is
+// its src_type with scale 1 and offset 0 copies the element's bytes unchanged.  The planner admits only planes whose blocks hold
+// whole elements of 1, 2, 4 or 8 bytes, and units start on multiples of 64 in their buffers: every element lies inside one unit
+// and its store is one aligned store of its size -- there is no byte-wise tail here.  Identity items with dense rows on both sides
+// (epitch == cpitch == typesize) are copied in dword units.
+struct TypedPatchArgs {
+    PatchArgs p;                      // (p.units and p.items unused)
+    const StridedPatchUnit* units;
+    const TypedWindowItem* items;     // overlays, in call order inside a unit (out_off / out_pitch / epitch locate the SOURCE elements)
+};
+
+struct TypedPatchBlock {
+    const TypedPatchArgs& a;
+    PatchBlock pb;
+    int disjoint;
+
+    CIMG_DEV TypedPatchBlock(const TypedPatchArgs& a_, uint8_t* lds, int k)
+        : a(a_), pb(a_.p, lds, k, PatchBlock::uniform_unit(&a_.units[k].u)), disjoint(uni(a_.units[k].disjoint)) {}
+
+    // rows r0 .. r1 of a dense item, copied unchanged in dword units aligned on the destination (the row loop of PatchBlock::overlay
+    // with tid0 and the stride as parameters)
+    CIMG_DEV void dense_rows(const WindowItem& it, int tid0, int stride)
+    {
+        const int64_t len = pb.u.len;
+        uint8_t* const unit = a.p.dst + pb.u.dst_off;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rs = it.row0 + (int64_t)r * it.rpitch, re = rs + it.wbytes;
+            const int64_t s = rs > it.p0 ? rs : it.p0;
+            const int64_t e = re < it.p0 + len ? re : it.p0 + len;
+            if (s >= e) continue;
+            const uint8_t* src = a.p.src + it.out_off + (int64_t)r * it.out_pitch + (s - rs);
+            uint8_t* dst = unit + (s - it.p0);
+            const int64_t n = e - s;
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t q0 = 4 * (u0 + l) - mis;
+                    if (u0 + l < units) {
+                        if (q0 >= 0 && q0 + 4 <= n) {
+                            const uint32_t v = (uint32_t)src[q0] | ((uint32_t)src[q0 + 1] << 8) | ((uint32_t)src[q0 + 2] << 16) |
+                                               ((uint32_t)src[q0 + 3] << 24);
+                            *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                        } else {
+                            for (int i = 0; i < 4; i++) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) dst[q] = src[q];
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    // overlay k of the unit by threads tid0 + lane, + stride, ...
+    CIMG_DEV void overlay(int k, int tid0, int stride)
+    {
+        const TypedWindowItem* ip = a.items + pb.u.item0 + k;
+        const WindowItem it = WindowBlock::uniform_item(ip);
+        const int64_t cpitch = uni64(ip->cpitch), epitch = uni64(ip->epitch);
+        const int ts = uni(ip->ts), src_type = uni(ip->src_type), out_type = uni(ip->out_type);
+        const float scale = bits_f32(uni(f32_bits(ip->scale))), offset = bits_f32(uni(f32_bits(ip->offset)));
+        const bool identity = out_type == src_type && scale == 1.0f && offset == 0.0f;
+        if (identity && cpitch == ts && epitch == ts) { dense_rows(it, tid0, stride); return; }
+        const int64_t len = pb.u.len, width = it.wbytes / ts;
+        uint8_t* const unit = a.p.dst + pb.u.dst_off;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the unit
+            // elements c_lo .. c_hi of the row lie inside [0, len) (whole: the planner admits no element over a unit's edge)
+            const int64_t hi = len - ts - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = rel >= 0 ? 0 : (-rel + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            uint8_t* dst = unit + rel + c_lo * cpitch;                         // element c_lo (>= the unit's first byte)
+            const uint8_t* src = a.p.src + it.out_off + (int64_t)r * it.out_pitch + c_lo * epitch;
+            const int64_t ne = c_hi + 1 - c_lo;
+            for (int64_t e0 = tid0; e0 < ne; e0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t e = e0 + l;
+                    if (e < ne) {
+                        const uint8_t* s = src + e * epitch;
+                        uint8_t* d = dst + e * cpitch;
+                        if (identity) {
+                            if (ts == 1) *d = *s;
+                            else if (ts == 2) *reinterpret_cast<uint16_t*>(d) = *reinterpret_cast<const uint16_t*>(s);
+                            else if (ts == 4) *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
+                            else *reinterpret_cast<uint64_t*>(d) = *reinterpret_cast<const uint64_t*>(s);
+                        } else {
+                            const uint32_t v = typed_store_bits(typed_unscale(typed_load_mem(s, out_type), scale, offset), src_type);
+                            if (ts == 1) *d = (uint8_t)v;
+                            else if (ts == 2) *reinterpret_cast<uint16_t*>(d) = (uint16_t)v;
+                            else *reinterpret_cast<uint32_t*>(d) = v;
                         }
                     }
                 }

@@ -68,6 +68,9 @@ inline bool items_cover(const std::vector<WindowItem>& items, size_t first, size
 //   int patch_strided(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
 //                                                          -- the same for a call over StridedWindowSpec: cimg_update_patch_strided over
 //                                                             StridedPatchUnit and StridedWindowItem (only such calls need it)
+//   int patch_typed(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
+//                                                          -- the same for a call over TypedWindowSpec: cimg_update_patch_typed over
+//                                                             StridedPatchUnit and TypedWindowItem (only such calls need it)
 //   int trunc(typesize, mask64, off, len)    [optional]    -- trunc-prec in place over pieces of the patch buffer, in front of encode().
 //                                                             An env without it cannot truncate: parameters that name the filter are
 //                                                             ERR_INVALID_PARAM there, as they were before the filter was built.
@@ -79,7 +82,8 @@ struct env_has_trunc<Env, std::void_t<decltype(std::declval<Env&>().trunc(0, uin
 // ---- strided windows (StridedWindowSpec: cimg_update_windows_strided_*) -----------------------------------------------------------
 // Coverage: a unit needs no staging only if its DENSE items (cpitch == typesize: col_pitch 1, or one element a row) cover it --
 // items_cover over those; strided items never prove coverage.
-inline bool items_cover(const std::vector<StridedWindowItem>& items, size_t first, size_t count, int64_t len)
+template <class Item, class = std::enable_if_t<std::is_base_of_v<StridedWindowItem, Item>>>
+inline bool items_cover(const std::vector<Item>& items, size_t first, size_t count, int64_t len)
 {
     int64_t written = 0;                                             // (most units are not covered: no table for them)
     for (size_t k = first; k < first + count; k++) if (items[k].cpitch == items[k].ts) written += (int64_t)(items[k].r1 - items[k].r0) * items[k].wbytes;
@@ -98,7 +102,8 @@ inline bool items_cover(const std::vector<StridedWindowItem>& items, size_t firs
 enum : int { UPDATE_DISJOINT_MAX_ROWS = 4096 };
 inline bool items_disjoint(const std::vector<WindowItem>&, size_t, size_t, int64_t, std::vector<std::pair<int64_t, int64_t>>*) { return false; }
 // (ivp: the caller's table, so that the units of a call share one allocation)
-inline bool items_disjoint(const std::vector<StridedWindowItem>& items, size_t first, size_t count, int64_t len,
+template <class Item, class = std::enable_if_t<std::is_base_of_v<StridedWindowItem, Item>>>
+inline bool items_disjoint(const std::vector<Item>& items, size_t first, size_t count, int64_t len,
                            std::vector<std::pair<int64_t, int64_t>>* ivp)
 {
     if (count < 2) return false;                                 // (one item: the schedule does not matter)
@@ -108,7 +113,7 @@ inline bool items_disjoint(const std::vector<StridedWindowItem>& items, size_t f
     std::vector<std::pair<int64_t, int64_t>>& iv = *ivp;
     iv.clear();
     for (size_t k = first; k < first + count; k++) {
-        const StridedWindowItem& t = items[k];
+        const Item& t = items[k];
         const int64_t width = t.wbytes / t.ts;
         for (int r = t.r0; r < t.r1; r++) {
             const int64_t rel = t.row0 + (int64_t)r * t.rpitch - t.p0;
@@ -144,6 +149,38 @@ int patch_units(Env& env, const std::vector<ChunkDesc>& descs, int lds_bytes, co
     std::vector<StridedPatchUnit> su(units.size());
     for (size_t k = 0; k < units.size(); k++) su[k] = StridedPatchUnit{units[k], disjoint[k], 0};
     return env.patch_strided(descs, lds_bytes, su, stage, items, to_whole, patch_bytes, status);
+}
+template <class Env>
+int patch_units(Env& env, const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<uint8_t>& disjoint,
+                const std::vector<WindowItem>& stage, const std::vector<TypedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                int32_t* status)
+{
+    std::vector<StridedPatchUnit> su(units.size());
+    for (size_t k = 0; k < units.size(); k++) su[k] = StridedPatchUnit{units[k], disjoint[k], 0};
+    return env.patch_typed(descs, lds_bytes, su, stage, items, to_whole, patch_bytes, status);
+}
+
+// ---- typed windows (TypedWindowSpec: cimg_update_windows_typed_device) -------------------------------------------------------------
+// A typed WRITE reads its windows the other way round: out_off / out_pitch / elem_pitch / out_type describe the SOURCE in memory,
+// src_type the plane.  run_update serves it as it serves the strided call (same items through list_strided_items, same units, same
+// coverage and disjointness proofs -- both look at the plane side only); this is what is checked on top, BEFORE the call touches
+// status or new_cbytes: every check of the typed reads (check_typed_windows), a finite non-zero scale and a finite offset, a float64
+// plane only as the identity, and d_src aligned like every other part of a source address.
+inline int check_typed_update(int nchunks, const int32_t* nbytes, const int32_t* blocksize, int typesize, int nwindows, const TypedWindowSpec* w,
+                              const void* d_src)
+{
+    if (nchunks < 0 || nwindows < 0 || typesize <= 0) return ERR_INVALID_PARAM;
+    const auto finite = [](float f) { return (f32_bits(f) & 0x7F800000u) != 0x7F800000u; };
+    for (int k = 0; k < nwindows; k++) {
+        const TypedWindowSpec& s = w[k];
+        if (!finite(s.scale) || !finite(s.offset) || s.scale == 0.0f) return ERR_INVALID_PARAM;
+        const int msz = type_size(s.out_type);
+        if (!msz || !type_size(s.src_type)) return ERR_INVALID_PARAM;
+        if (!typed_identity(s) && s.src_type == T_F64) return ERR_INVALID_PARAM;
+        if ((uintptr_t)d_src % (uintptr_t)msz) return ERR_INVALID_PARAM;
+    }
+    const std::vector<int32_t> tsv((size_t)nchunks, typesize > 255 ? 1 : typesize);
+    return check_typed_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w);
 }
 
 template <class Env, class Spec>

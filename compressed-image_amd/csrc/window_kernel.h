@@ -445,6 +445,45 @@ CIMG_DEV float typed_scale(float x, float scale, float offset)
     return p + offset;
 }
 
+// ---- the way back (typed window WRITES: update_kernel.h, TypedPatchBlock) ---------------------------------------------------------
+// fl32(fl32(y - offset) / scale), the inverse of typed_scale with the same pair: the difference is rounded before the quotient, and
+// the quotient is the IEEE correctly rounded division -- not a multiply by a reciprocal, not a fast divide (the product is built
+// without fast-math, and HIP's default keeps fp32 division correctly rounded, denormals included)
+CIMG_DEV float typed_unscale(float y, float scale, float offset)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float d = y - offset;
+    return d / scale;
+}
+
+// the element at m, of memory type mem_type (T_F32 or T_F16), as float32: exact
+CIMG_DEV float typed_load_mem(const uint8_t* m, int mem_type)
+{
+    if (mem_type == T_F16) return half_to_f32(*reinterpret_cast<const uint16_t*>(m));
+    return bits_f32(*reinterpret_cast<const uint32_t*>(m));
+}
+
+// t as a stored element of dst_type (its low bytes).  Integers: NaN gives 0, otherwise rint (ties to even) saturated to the type's
+// range -- the bounds are compared in float32, where 2^31 and 2^32 are exact and every integer-valued float below them converts
+// exactly.  float16: one rounding to nearest even, overflow to inf, subnormals kept.  float32: t itself.
+CIMG_DEV uint32_t typed_store_bits(float t, int dst_type)
+{
+    if (dst_type == T_F32) return f32_bits(t);
+    if (dst_type == T_F16) return f32_to_half(t);
+    if (t != t) return 0;
+    const float r = __builtin_rintf(t);
+    switch (dst_type) {
+    case T_U8: return r <= 0.0f ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
+    case T_I8: return (uint32_t)(uint8_t)(int8_t)(r <= -128.0f ? -128 : r >= 127.0f ? 127 : (int32_t)r);
+    case T_U16: return r <= 0.0f ? 0u : r >= 65535.0f ? 65535u : (uint32_t)r;
+    case T_I16: return (uint32_t)(uint16_t)(int16_t)(r <= -32768.0f ? -32768 : r >= 32767.0f ? 32767 : (int32_t)r);
+    case T_U32: return r <= 0.0f ? 0u : r >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)r;
+    default: return r <= -2147483648.0f ? 0x80000000u : r >= 2147483648.0f ? 0x7FFFFFFFu : (uint32_t)(int32_t)r;   // T_I32
+    }
+}
+
 struct TypedWindowBlock {
     const TypedWindowArgs& a;
     WindowUnit u;

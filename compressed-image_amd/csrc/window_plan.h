@@ -491,11 +491,10 @@ template <> struct PlanOf<TypedWindowSpec> { using type = TypedWindowPlan; };
 
 inline bool typed_identity(const TypedWindowSpec& s) { return s.out_type == s.src_type && s.scale == 1.0f && s.offset == 0.0f; }
 
-inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
-                        const TypedWindowSpec* w, const uint8_t* whole_hint, TypedWindowPlan* plan)
+// the checks of typed windows (shared by the reads, below, and the typed write call: update_plan.h)
+inline int check_typed_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                               const TypedWindowSpec* w)
 {
-    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
-    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
     for (int k = 0; k < nwindows; k++) {
         const TypedWindowSpec& s = w[k];
         int ts = 0;
@@ -511,6 +510,16 @@ inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* block
         if (s.width > 1 && s.elem_pitch > (INT64_MAX - osz) / (s.width - 1)) return ERR_INVALID_PARAM;
         if (s.height > 1 && (s.out_pitch < (int64_t)(s.width - 1) * s.elem_pitch + osz || s.out_pitch % osz)) return ERR_INVALID_PARAM;
     }
+    return 0;
+}
+
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const TypedWindowSpec* w, const uint8_t* whole_hint, TypedWindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    const int crc = check_typed_windows(nchunks, nbytes, blocksize, typesize, nwindows, w);
+    if (crc < 0) return crc;
     list_strided_items(nbytes, typesize, nwindows, w, plan, [](TypedWindowItem& t, const TypedWindowSpec& s) {
         t.epitch = s.elem_pitch; t.src_type = s.src_type; t.out_type = s.out_type; t.scale = s.scale; t.offset = s.offset;
     });

@@ -13,6 +13,7 @@
 // wait_stream() first.  Results need no counterpart: every call returns after the engine's stream has been synchronised.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -188,6 +189,21 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			if constexpr (!std::is_same_v<U, float> && !std::is_same_v<U, half>)
 				if (scale != 1.0f || offset != 0.0f)
 					throw std::invalid_argument(text(what, ": a result of the stored type takes scale 1 and offset 0 (float and half results are converted)"));
+		}
+		/// What a typed write may take for pixels stored as T: float, half, or T itself with scale 1 and offset 0.  The scale is finite
+		/// and not 0, the offset finite; float64 pixels are written from float64 only.
+		template <typename T, typename U> void check_typed_source(float scale, float offset, const char* what)
+		{
+			static_assert(std::is_same_v<U, float> || std::is_same_v<U, half> || std::is_same_v<U, T>,
+				"a typed region write takes float, half or the stored type");
+			static_assert(typed_code<T>() >= 0, "typed region writes: unsupported element type");
+			if (!std::isfinite(scale) || !std::isfinite(offset) || scale == 0.0f)
+				throw std::invalid_argument(text(what, ": scale must be finite and not 0, offset must be finite"));
+			if constexpr (!std::is_same_v<U, float> && !std::is_same_v<U, half>)
+				if (scale != 1.0f || offset != 0.0f)
+					throw std::invalid_argument(text(what, ": a source of the stored type takes scale 1 and offset 0 (float and half sources are converted)"));
+			if constexpr (std::is_same_v<T, double> && !std::is_same_v<U, double>)
+				throw std::invalid_argument(text(what, ": float64 pixels are written from float64 only"));
 		}
 	}
 
@@ -524,6 +540,37 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, w, d_src);
 		}
 
+		/// Write `d_src` -- U = float, half or T, ceil(height / step_y) rows of ceil(width / step_x) elements -- over the (subsampled)
+		/// rectangle, each element converted in the patch launch itself: the inverse of get_region<U> with the same scale and offset,
+		/// t = fl32(fl32((float)y - offset) / scale), then rint saturated to T's range (NaN gives 0) for integer pixels, t rounded once
+		/// for half pixels, t for float pixels -- numpy's answer bit for bit.  U = T takes scale 1 and offset 0 and copies the elements.
+		template <typename U>
+		void set_region(const U* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, float scale, float offset)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src, scale, offset);
+		}
+		/// set_regions with every element converted as above: ONE engine call (cimg_update_windows_typed_device) and one repack.
+		template <typename U>
+		void set_regions(std::span<const region> regions, const U* d_src, float scale, float offset)
+		{
+			if (m_ReadOnly) throw std::runtime_error("set_regions: this device_channel shares the store of a device_image and is read-only; use device_image::set_regions");
+			detail::check_typed_source<T, U>(scale, offset, "set_regions");
+			const size_t total = check_regions(regions);
+			require();
+			std::vector<cimg_window_typed> w;
+			size_t at = 0;
+			for (const region& r : regions)
+			{
+				if (r.width && r.height) w.push_back(typed_window<U>(r, at * sizeof(U), sizeof(U), scale, offset));
+				at += r.out_elems();
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("set_regions: too many regions for one call");
+			detail::device_range(m_Store->engine, d_src, total * sizeof(U), "set_regions");
+			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, w, d_src);
+		}
+
 		void check_region(size_t x, size_t y, size_t width, size_t height) const
 		{
 			if (x > m_Width || y > m_Height || width > m_Width - x || height > m_Height - y)
@@ -576,13 +623,14 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 
 		/// Apply window writes to a store: the update's output goes to a scratch allocation, then ONE pack launch gathers the new
 		/// store -- untouched chunks from the old one, touched ones from the scratch.  The old store is left as it was.
-		/// (Window: cimg_window through cimg_update_windows_device, cimg_window_strided through cimg_update_windows_strided_device --
-		/// only the strided instantiation refers to the strided entry point)
+		/// (Window: cimg_window through cimg_update_windows_device, cimg_window_strided through cimg_update_windows_strided_device,
+		/// cimg_window_typed through cimg_update_windows_typed_device -- each instantiation refers to its own entry point only)
 		template <typename Window>
 		static std::shared_ptr<detail::device_store> updated_store(const detail::device_store& old, const cimg_cparams& cp, size_t nominal_chunk_bytes,
 			const std::vector<Window>& windows, const void* d_src)
 		{
-			constexpr bool strided = std::is_same_v<Window, cimg_window_strided>;
+			constexpr bool typed = std::is_same_v<Window, cimg_window_typed>;
+			constexpr bool strided = std::is_same_v<Window, cimg_window_strided> || typed;
 			cimg_engine* e = old.engine;
 			const size_t n = old.num_chunks();
 			const int32_t dest = static_cast<int32_t>(blosc2::min_compressed_size(nominal_chunk_bytes));
@@ -610,7 +658,11 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			detail::device_store scratch;
 			scratch.allocate(e, scratch_bytes + 64);
 			detail::engine_lock lock(e);
-			if constexpr (strided)
+			if constexpr (typed)
+				detail::engine_call(e, cimg_update_windows_typed_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(),
+					old.nbytes.data(), old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base,
+					new_off.data(), new_cbytes.data(), status.data()), "Writing the typed regions");
+			else if constexpr (strided)
 				detail::engine_call(e, cimg_update_windows_strided_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(),
 					old.nbytes.data(), old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base,
 					new_off.data(), new_cbytes.data(), status.data()), "Writing the regions");

@@ -317,6 +317,53 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
 		}
 
+		/// Write U = float, half or T over the (subsampled) rectangle of every channel, channel c converted with the inverse of
+		/// get_region<U> under scales[c] and offsets[c] (a span of one value serves every channel) in the patch launch itself.  d_src holds
+		/// planes (C, oh, ow) or, with `interleaved`, pixels (oh, ow, C): the C windows of a region then read the channel slots of the
+		/// same rows -- no permute, no stored-type copy.  One update call, one repack of the store.
+		template <typename U>
+		void set_region(const U* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, std::span<const float> scales,
+			std::span<const float> offsets, bool interleaved = false)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src, scales, offsets, interleaved);
+		}
+		/// Many rectangles of every channel, converted as above, in ONE engine call and one repack: the source is region-major,
+		/// channel-minor (N, C, oh, ow) or, with `interleaved`, (N, oh, ow, C).  Later regions win where two overlap.
+		template <typename U>
+		void set_regions(std::span<const region> regions, const U* d_src, std::span<const float> scales, std::span<const float> offsets, bool interleaved = false)
+		{
+			if ((scales.size() != 1 && scales.size() != m_NumChannels) || (offsets.size() != 1 && offsets.size() != m_NumChannels))
+				throw std::invalid_argument(detail::text("set_regions: scales and offsets hold one value or one per channel (", m_NumChannels, ")"));
+			for (size_t c = 0; c < std::max(scales.size(), offsets.size()); ++c)
+				detail::check_typed_source<T, U>(scales[scales.size() == 1 ? 0 : c], offsets[offsets.size() == 1 ? 0 : c], "set_regions");
+			const size_t per_channel = prototype().check_regions(regions);
+			if (m_NumChannels == 0) return;
+			std::vector<device_channel<T>> per_ch;                    // one prototype a channel, made once
+			for (size_t c = 0; c < m_NumChannels; ++c)
+			{
+				per_ch.push_back(prototype());
+				per_ch.back().m_First = c * chunks_per_channel();
+				per_ch.back().m_Count = chunks_per_channel();
+			}
+			std::vector<cimg_window_typed> w;
+			size_t at = 0;                                                       // elements of U before this region
+			for (const region& r : regions)
+			{
+				for (size_t c = 0; c < m_NumChannels && r.width && r.height; ++c)
+				{
+					const float sc = scales[scales.size() == 1 ? 0 : c], of = offsets[offsets.size() == 1 ? 0 : c];
+					if (interleaved) w.push_back(per_ch[c].template typed_window<U>(r, (at + c) * sizeof(U), m_NumChannels * sizeof(U), sc, of));
+					else w.push_back(per_ch[c].template typed_window<U>(r, (at + c * r.out_elems()) * sizeof(U), sizeof(U), sc, of));
+				}
+				at += r.out_elems() * m_NumChannels;
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("set_regions: too many regions for one call");
+			detail::device_range(m_Store->engine, d_src, per_channel * m_NumChannels * sizeof(U), "set_regions");
+			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
+		}
+
 		size_t width() const noexcept { return m_Width; }
 		size_t height() const noexcept { return m_Height; }
 		size_t num_channels() const noexcept { return m_NumChannels; }

@@ -683,6 +683,20 @@ namespace
 		throw py::value_error(std::string(what) + ": dtype must be float32, float16 or the stored dtype, got " + std::string(py::str(dt)));
 	}
 
+	// f.template operator()<U>() for the source type dtype= names -- the stored type T, float or half; the array must hold exactly that
+	template <typename T, typename F> void typed_source_dispatch(const py::object& dtype, const py::dtype& have, F&& f, const char* what)
+	{
+		const py::dtype dt = as_dtype(dtype);
+		const bool stored = dt.is(np_dtype<T>()), f32 = dt.is(np_dtype<float>()), f16 = dt.is(np_dtype<compressed::half>());
+		if (!stored && !f32 && !f16)
+			throw py::value_error(std::string(what) + ": dtype must be float32, float16 or the stored dtype, got " + std::string(py::str(dt)));
+		if (!have.is(dt))
+			throw py::type_error(std::string(what) + ": the array has dtype " + std::string(py::str(have)) + ", dtype= says " + std::string(py::str(dt)));
+		if (stored) f.template operator()<T>();
+		else if (f32) f.template operator()<float>();
+		else f.template operator()<compressed::half>();
+	}
+
 	inline void check_region_args(py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h)
 	{
 		if (x < 0 || y < 0 || w < 0 || h < 0) throw py::value_error("region coordinates and sizes must be >= 0");
@@ -810,12 +824,28 @@ namespace
 			});
 		}
 		// array: (h', w') in device memory, written over every step_y-th row and step_x-th element from (x, y)
-		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y)
+		// (dtype=: the array holds float32, float16 or the stored type and every element is unscaled, rounded and stored in the patch launch)
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y,
+			const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0))
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
 			check_steps(step_x, step_y);
+			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
+			if (dtype.is_none()) require_plain(sc, of, "set_region");
 			const device_view v = view_of(array, "set_region");
 			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				if (!dtype.is_none())
+				{
+					typed_source_dispatch<T>(dtype, v.dt, [&]<typename U>() {
+						if (v.shape.size() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(v.shape.size()) + " dimensions");
+						const size_t w = covered(v.shape[1], step_x), h = covered(v.shape[0], step_y);
+						ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+						wait_for(stream);
+						ch.set_region(static_cast<const U*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x),
+							static_cast<size_t>(step_y), sc[0], of[0]);
+					}, "set_region");
+					return 0;
+				}
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
 				if (v.shape.size() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(v.shape.size()) + " dimensions");
 				const size_t w = covered(v.shape[1], step_x), h = covered(v.shape[0], step_y);
@@ -831,10 +861,13 @@ namespace
 		}
 		// arrays: (N, h', w') in device memory (pixels: (N,)), region k from (xs[k], ys[k]); later regions win
 		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
-			py::ssize_t step_y, bool pixels)
+			py::ssize_t step_y, bool pixels, const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0),
+			const py::object& offset = py::float_(0.0))
 		{
 			const char* what = pixels ? "set_pixels" : "set_regions";
 			check_steps(step_x, step_y);
+			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
+			if (dtype.is_none()) require_plain(sc, of, what);
 			const device_view v = view_of(arrays, what);
 			if (v.shape.size() != (pixels ? 1u : 3u)) throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N,)" : ": arrays must have the shape (N, height, width)"));
 			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[2], step_x)),
@@ -842,6 +875,15 @@ namespace
 			if (regions.size() != static_cast<size_t>(v.shape[0]))
 				throw py::value_error(std::string(what) + ": got " + std::to_string(v.shape[0]) + " arrays for " + std::to_string(regions.size()) + " coordinates");
 			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				if (!dtype.is_none())
+				{
+					typed_source_dispatch<T>(dtype, v.dt, [&]<typename U>() {
+						ch.check_regions(regions);
+						wait_for(stream);
+						ch.set_regions(std::span<const compressed::region>(regions), static_cast<const U*>(v.ptr), sc[0], of[0]);
+					}, what);
+					return 0;
+				}
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
 				ch.check_regions(regions);
 				if (regions.empty() || v.count() == 0) return 0;
@@ -1009,12 +1051,33 @@ namespace
 			});
 		}
 		// one (C, h', w') device array over every step_y-th row and step_x-th element from (x, y) of every channel
-		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y)
+		// (dtype=: the array holds float32, float16 or the stored type, converted in the patch launch with one scale / offset or one per
+		// channel; interleaved: the array is pixel-major, (h', w', C))
+		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y,
+			const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0),
+			bool interleaved = false)
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
 			check_steps(step_x, step_y);
+			if (dtype.is_none() && interleaved) throw py::value_error("set_region: interleaved needs dtype= (float32, float16 or the stored dtype)");
 			const device_view v = view_of(array, "set_region");
 			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				const std::vector<float> sc = float_list(scale, img->num_channels(), "scale"), of = float_list(offset, img->num_channels(), "offset");
+				if (dtype.is_none()) require_plain(sc, of, "set_region");
+				else
+				{
+					typed_source_dispatch<T>(dtype, v.dt, [&]<typename U>() {
+						const size_t ci = interleaved ? 2 : 0, hi = interleaved ? 0 : 1, wi = interleaved ? 1 : 2;
+						if (v.shape.size() != 3 || static_cast<size_t>(v.shape[ci]) != img->num_channels())
+							throw py::value_error(interleaved ? "region arrays must have the shape (height, width, channels)" : "region arrays must have the shape (channels, height, width)");
+						const size_t w = covered(v.shape[wi], step_x), h = covered(v.shape[hi], step_y);
+						if (img->num_channels()) img->channel(0).check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+						wait_for(stream);
+						img->set_region(static_cast<const U*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x),
+							static_cast<size_t>(step_y), std::span<const float>(sc), std::span<const float>(of), interleaved);
+					}, "set_region");
+					return 0;
+				}
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
 				if (v.shape.size() != 3 || static_cast<size_t>(v.shape[0]) != img->num_channels())
 					throw py::value_error("region arrays must have the shape (channels, height, width)");
@@ -1030,18 +1093,37 @@ namespace
 			});
 		}
 		// arrays: (N, C, h', w') in device memory (pixels: (N, C)), region k from (xs[k], ys[k]) of every channel; later regions win
+		// (dtype=: converted in the patch launch; interleaved: (N, h', w', C) -- pixels are (N, C) either way)
 		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
-			py::ssize_t step_y, bool pixels)
+			py::ssize_t step_y, bool pixels, const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0),
+			const py::object& offset = py::float_(0.0), bool interleaved = false)
 		{
 			const char* what = pixels ? "set_pixels" : "set_regions";
 			check_steps(step_x, step_y);
+			if (dtype.is_none() && interleaved) throw py::value_error(std::string(what) + ": interleaved needs dtype= (float32, float16 or the stored dtype)");
 			const device_view v = view_of(arrays, what);
-			if (v.shape.size() != (pixels ? 2u : 4u)) throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N, channels)" : ": arrays must have the shape (N, channels, height, width)"));
-			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[3], step_x)),
-				pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[2], step_y)), step_x, step_y);
+			const bool pm = interleaved && !pixels;                       // (N, h', w', C)
+			if (v.shape.size() != (pixels ? 2u : 4u))
+				throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N, channels)" : pm ? ": arrays must have the shape (N, height, width, channels)" : ": arrays must have the shape (N, channels, height, width)"));
+			const size_t ci = pm ? 3 : 1;
+			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[pm ? 2 : 3], step_x)),
+				pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[pm ? 1 : 2], step_y)), step_x, step_y);
 			if (regions.size() != static_cast<size_t>(v.shape[0]))
 				throw py::value_error(std::string(what) + ": got " + std::to_string(v.shape[0]) + " arrays for " + std::to_string(regions.size()) + " coordinates");
 			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				const std::vector<float> sc = float_list(scale, img->num_channels(), "scale"), of = float_list(offset, img->num_channels(), "offset");
+				if (dtype.is_none()) require_plain(sc, of, what);
+				else
+				{
+					typed_source_dispatch<T>(dtype, v.dt, [&]<typename U>() {
+						if (static_cast<size_t>(v.shape[ci]) != img->num_channels()) throw py::value_error(std::string(what) + ": the arrays' channel count does not match the image");
+						if (img->num_channels()) img->channel(0).check_regions(regions);
+						wait_for(stream);
+						img->set_regions(std::span<const compressed::region>(regions), static_cast<const U*>(v.ptr), std::span<const float>(sc),
+							std::span<const float>(of), interleaved);
+					}, what);
+					return 0;
+				}
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
 				if (static_cast<size_t>(v.shape[1]) != img->num_channels()) throw py::value_error(std::string(what) + ": the arrays' channel count does not match the image");
 				if (img->num_channels()) img->channel(0).check_regions(regions);
@@ -1215,13 +1297,17 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
 		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
-			py::arg("step_x") = 1, py::arg("step_y") = 1)
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("set_regions", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
-				py::ssize_t sx, py::ssize_t sy) { c.set_regions(xs, ys, arrays, stream, sx, sy, false); },
-			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("set_pixels", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream) {
-				c.set_regions(xs, ys, values, stream, 1, 1, true); },
-			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt)
+				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset) {
+				c.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1,
+			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0)
+		.def("set_pixels", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream,
+				const py::object& dtype, const py::object& scale, const py::object& offset) {
+				c.set_regions(xs, ys, values, stream, 1, 1, true, dtype, scale, offset); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(), py::arg("scale") = 1.0,
+			py::arg("offset") = 0.0)
 		.def("__setitem__", &DeviceChannel::setitem, py::arg("key"), py::arg("value"));
 
 	py::class_<DeviceImage>(m, "DeviceImage", py::module_local())
@@ -1253,13 +1339,18 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(),
 			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
-			py::arg("step_x") = 1, py::arg("step_y") = 1)
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0,
+			py::arg("interleaved") = false)
 		.def("set_regions", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
-				py::ssize_t sx, py::ssize_t sy) { i.set_regions(xs, ys, arrays, stream, sx, sy, false); },
-			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("set_pixels", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream) {
-				i.set_regions(xs, ys, values, stream, 1, 1, true); },
-			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt)
+				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved) {
+				i.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset, interleaved); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1,
+			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0, py::arg("interleaved") = false)
+		.def("set_pixels", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream,
+				const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved) {
+				i.set_regions(xs, ys, values, stream, 1, 1, true, dtype, scale, offset, interleaved); },
+			py::arg("xs"), py::arg("ys"), py::arg("values"), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(), py::arg("scale") = 1.0,
+			py::arg("offset") = 0.0, py::arg("interleaved") = false)
 		.def("get_channel_index", [](const DeviceImage& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
 		.def("get_channel_names", [](const DeviceImage& i) { return i.visit([](auto& img) { return img->channelnames(); }); })
 		.def("set_channel_names", [](DeviceImage& i, std::vector<std::string> names) { i.visit([&](auto& img) { img->channelnames(std::move(names)); return 0; }); }, py::arg("channel_names"))

@@ -325,6 +325,37 @@ int cimg_update_windows_strided_host(cimg_engine* e, const cimg_cparams* p, int3
                                      const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_strided* w,
                                      const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
                                      int32_t* status);
+/* Typed window writes: unscale, round and re-encode in the patch launch -- the inverse of cimg_decompress_windows_typed_device,
+ * over the same cimg_window_typed with every field in the same role: src_type is the PLANE's stored type, out_type the type IN
+ * MEMORY, and out_off / out_pitch / elem_pitch describe the memory side, which here is the SOURCE.  Element c of window row r is
+ * loaded from d_src + out_off + r * out_pitch + c * elem_pitch as out_type and written to plane element
+ * origin + r * row_pitch + c * col_pitch; the bytes between source elements are not read, so the C windows of a pixel-major source
+ * (elem_pitch = C * size of out_type) write C planes in one call.  scale and offset keep the READ convention (stored -> memory is
+ * y = v * scale + offset) and the write applies the inverse, so a caller passes the same pair both ways.  For a memory value y,
+ * each step rounded to nearest even and float32 denormals kept: x = (float)y (exact), t = fl32(fl32(x - offset) / scale) -- two
+ * roundings, the division IEEE correctly rounded: not a multiply by a reciprocal, not a fast divide, not an FMA form.  An integer
+ * plane stores rint(t), ties to even, saturated to the type's range (+inf max, -inf min), and 0 for NaN: numpy's
+ * clip(rint(where(isnan(t), 0, t)), min, max).astype(type).  A CIMG_T_F16 plane stores t rounded once to half (overflow gives inf,
+ * subnormals are kept, a NaN stays a NaN), a CIMG_T_F32 plane t.  A window with out_type == src_type, scale 1 and offset 0 copies
+ * each element's bytes unchanged (NaN payloads and -0 survive); CIMG_T_F64 planes and integer or CIMG_T_F64 memory types take only
+ * that.  The chunk's trunc-prec filter applies after the conversion.
+ * The checks, the order (a later window wins on every byte two windows share), new bytes (every touched chunk equals what
+ * cimg_compress_batch_* with `p` gives for the decoded pixels with the CONVERTED windows written in), status[], the return value,
+ * locking and cimg_engine_update_stats are those of cimg_update_windows_strided_device; a call whose windows are all identity with
+ * elem_pitch == typesize gives that call's new chunks, new_cbytes, status, return value and stats.  The patch launch is
+ * cimg_update_patch_typed (CIMG_K_UPDATE_PATCH_TYPED).  Added checks, made before status[] or new_cbytes[] are touched
+ * (BLOSC2_ERROR_INVALID_PARAM, nothing runs): scale is finite and not 0, offset is finite; both types are known and the size of
+ * src_type is p->typesize; elem_pitch is at least the size of out_type; out_pitch >= (width - 1) * elem_pitch + that size when
+ * height > 1 (a source row need not be dense); out_off, out_pitch (height > 1), elem_pitch and d_src are multiples of that size
+ * (every element is one naturally aligned load); and, for every chunk of the window's plane, blocksize -- and nbytes unless it is
+ * the plane's last chunk -- is a multiple of typesize (a converted element never straddles two blocks).
+ * There is no _host form, for the reason the typed reads have none: float32 pixels would cross PCIe at four times the size of the
+ * uint8 they become, and the host-resident classes take arrays of the stored type; host callers convert where the pixels are. */
+int cimg_update_windows_typed_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp,
+                                     const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
+                                     const int32_t* blocksize, const int32_t* destsize, int32_t nwindows,
+                                     const cimg_window_typed* w, const void* d_src, void* d_new, const int64_t* new_off,
+                                     int32_t* new_cbytes, int32_t* status);
 /* The last update call on this engine: blocks staged from their old streams, blocks re-encoded on the splice route, chunks decoded
  * and compressed whole, bytes uploaded (host call only: touched chunks and window bytes).  Any pointer may be NULL. */
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole,
@@ -412,7 +443,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* the patch launch of cimg_update_windows_strided_device / _host */
        CIMG_K_UPDATE_PATCH_STRIDED = 26,
        /* the window launch of cimg_decompress_windows_typed_device */
-       CIMG_K_DECODE_WINDOW_TYPED = 27, CIMG_K_COUNT = 28 };
+       CIMG_K_DECODE_WINDOW_TYPED = 27,
+       /* the patch launch of cimg_update_windows_typed_device */
+       CIMG_K_UPDATE_PATCH_TYPED = 28, CIMG_K_COUNT = 29 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

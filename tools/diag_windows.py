@@ -36,6 +36,14 @@ not build the plane of (1)) that writes profiles/typed/diag_windows_typed.json:
       torch's .float().mul_().add_() (and .permute().contiguous()); one 2048^2 crop of a 4 x 4096^2 float16 DeviceImage pixel-major
       in its own type through get_region(dtype=float16, interleaved=True) against get_region(interleaved=True).  The two routes
       alternate; kernel time (the shared engine's HIP events plus torch events around torch's part) and wall time, medians of REPS.
+Typed write leg, a process of its own (`python tools/diag_windows.py --typed-write-leg [--out file]`, torch
+first) that writes profiles/typed/diag_windows_typed_write.json:
+  (9) 256 seeded random 224^2 crops written into a 3 x 4096^2 uint8 DeviceImage (lz4 + shuffle) from float32 tensors with per-channel
+      scale / offset, planar and pixel-major, through set_regions(dtype=float32, scale=, offset=[, interleaved=True]) against the
+      route without it: torch's sub / div / round / clamp / to(uint8) (after .permute().contiguous() for pixel-major) followed by
+      set_regions.  The two routes alternate in one process; kernel time (every launch of the shared engine, HIP events, plus torch
+      events around torch's part) and wall time, medians of REPS after a warm-up.  Then the patch launch alone on an all-identity
+      call: set_regions(dtype=uint8) (cimg_update_patch_typed) against set_regions (cimg_update_patch_strided), same windows.
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -49,7 +57,8 @@ STRIDED_LEG = "--strided-leg" in sys.argv
 GROUPED_LEG = "--grouped-leg" in sys.argv
 WRITE_STRIDED_LEG = "--write-strided-leg" in sys.argv
 TYPED_LEG = "--typed-leg" in sys.argv
-if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG or TYPED_LEG:
+TYPED_WRITE_LEG = "--typed-write-leg" in sys.argv
+if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG or TYPED_LEG or TYPED_WRITE_LEG:
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -137,6 +146,95 @@ def typed_leg():
     out["crop_2048_f16x4_pixel_major"] = r
     return out
 
+
+def typed_write_leg():
+    """(9): typed writes of the device classes against the route without them"""
+    import ctypes as C
+    path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
+    spec_m = importlib.util.spec_from_file_location("compressed_image", path)
+    ci = importlib.util.module_from_spec(spec_m)
+    spec_m.loader.exec_module(ci)
+    m = 4096
+    planes8 = np.stack([synth.tiled_channel(np.uint8, m, m, c=k) for k in range(3)])
+    dev8 = torch.from_numpy(planes8).cuda()
+    L = hip.load()
+    L.cimg_shared_engine.restype = C.c_void_p
+    se = hip.Engine.__new__(hip.Engine)                    # the module's engine, for its kernel times
+    se.handle = C.c_void_p(L.cimg_shared_engine())
+    every = range(len(hip.KERNELS))
+    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def alternating(old, new, old_has_torch, patch=None):
+        old(); new()
+        torch.cuda.synchronize()
+        se.enable_timing(1)
+        rows = {"old": ([], [], []), "typed": ([], [], [])}
+        for _ in range(REPS):
+            for name, f in (("old", old), ("typed", new)):
+                se.reset_timing()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                rows[name][0].append((time.perf_counter() - t) * 1e6)
+                k = sum(se.kernel_time(kid)[0] for kid in every) * 1e3
+                rows[name][1].append(k + (ev_a.elapsed_time(ev_b) * 1e3 if name == "old" and old_has_torch else 0.0))
+                rows[name][2].append(sum(se.kernel_time(kid)[0] for kid in (hip.K_UPDATE_PATCH_STRIDED, hip.K_UPDATE_PATCH_TYPED)) * 1e3)
+        se.enable_timing(0)
+        return {name: dict(wall_us=round(float(np.median(wl)), 1), wall_min_us=round(float(np.min(wl)), 1), wall_max_us=round(float(np.max(wl)), 1),
+                           kernel_us=round(float(np.median(kl)), 1), patch_kernel_us=round(float(np.median(pl)), 1))
+                for name, (wl, kl, pl) in rows.items()}
+
+    out = {}
+    rng = np.random.default_rng(9)
+    N, c = 256, 224
+    xs, ys = rng.integers(0, m - c, N), rng.integers(0, m - c, N)
+    scale, offset = [1 / (255 * 0.229), 1 / (255 * 0.224), 1 / (255 * 0.225)], [-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225]
+    sc_t = torch.tensor(scale, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    of_t = torch.tensor(offset, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
+    # the source: what a network hands back -- normalised floats around the crops' own pixels, some out of range
+    noise = torch.from_numpy(rng.normal(0.0, 0.02, (N, 3, c, c)).astype(np.float32)).cuda()
+    for il in (False, True):
+        img_old = ci.DeviceImage(np.uint8, dev8, m, m)
+        img_new = ci.DeviceImage(np.uint8, dev8, m, m)
+        planar = img_old.get_regions(xs, ys, c, c, dtype=np.float32, scale=scale, offset=offset)
+        planar = torch.as_tensor(planar, device="cuda") + noise
+        src = planar.permute(0, 2, 3, 1).contiguous() if il else planar
+        kept = []
+
+        def old():
+            ev_a.record()
+            p = src.permute(0, 3, 1, 2).contiguous() if il else src
+            u = p.sub(of_t).div_(sc_t).round_().clamp_(0, 255).to(torch.uint8)
+            kept[:] = [u]
+            ev_b.record()
+            img_old.set_regions(xs, ys, u)
+
+        def new():
+            img_new.set_regions(xs, ys, src, dtype=np.float32, scale=scale, offset=offset, interleaved=il)
+
+        r = alternating(old, new, True)
+        r["pixels_equal"] = bool(torch.equal(torch.as_tensor(img_old.get_decompressed(), device="cuda"), torch.as_tensor(img_new.get_decompressed(), device="cuda")))
+        r["source_bytes"] = src.numel() * 4
+        r["old_temporary_bytes"] = kept[0].numel() * (1 + 4) + (src.numel() * 4 if il else 0)     # the float result of sub and the uint8 copy; and the planar floats under permute
+        out["crops256_224_f32_u8_" + ("pixel_major" if il else "planar")] = r
+        del kept[:], img_old, img_new
+    # the patch launch alone: an all-identity call through both kernels
+    img_a = ci.DeviceImage(np.uint8, dev8, m, m)
+    img_b = ci.DeviceImage(np.uint8, dev8, m, m)
+    u8 = torch.as_tensor(img_a.get_regions(xs, ys, c, c), device="cuda")
+    r = alternating(lambda: img_a.set_regions(xs, ys, u8), lambda: img_b.set_regions(xs, ys, u8, dtype=np.uint8), False)
+    out["crops256_224_u8_identity"] = r
+    return out
+
+
+if TYPED_WRITE_LEG:
+    line = json.dumps(typed_write_leg())
+    print("TYPED_WRITE " + line)
+    dst = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "typed", "diag_windows_typed_write.json")
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    open(dst, "w").write(line + "\n")
+    sys.exit(0)
 
 if TYPED_LEG:
     line = json.dumps(typed_leg())
