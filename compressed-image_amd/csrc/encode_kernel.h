@@ -461,7 +461,7 @@ CIMG_DEV int lz4_encode_body(const uint8_t* in, uint8_t* tab, int n, uint8_t* ou
                 LV<uint32_t> before;
                 FOR_LANES(l) {
                     slot[l] = tab16[h0];
-                    scan[l] = lds_ld32u(in, ip0 + 5 + 4 * l);                 // bytes after the five known run bytes
+                    scan[l] = lds_ld32u_row(in, ip0 + 5, l);                  // bytes after the five known run bytes
                     before[l] = in[ip0 - 1];
                 }
                 const int old0 = (int)readlane(slot, 0);
@@ -469,8 +469,8 @@ CIMG_DEV int lz4_encode_body(const uint8_t* in, uint8_t* tab, int n, uint8_t* ou
                 // decides the hit AND, for a hit, already is the match extension (no literals: nothing backwards)
                 LV<uint32_t> cw, iw;
                 FOR_LANES(l) {
-                    cw[l] = lds_ld32u(in, old0 + 4 * l);
-                    iw[l] = lds_ld32u(in, ip0 + 4 * l);
+                    cw[l] = lds_ld32u_row(in, old0, l);
+                    iw[l] = lds_ld32u_row(in, ip0, l);
                 }
                 // (without this the compiler moves the loads of scan / before / iw into the branches below: a third round trip)
                 needed_here(scan); needed_here(before); needed_here(iw);
@@ -541,7 +541,7 @@ CIMG_DEV int lz4_encode_body(const uint8_t* in, uint8_t* tab, int n, uint8_t* ou
                     const int kb = l < room ? l + 1 : 0;
                     const uint32_t pa = in[ip - kb], pb = in[mp - kb];
                     const int k = 4 * l;
-                    const uint32_t x = lds_ld32u(in, ip + 4 + k) ^ lds_ld32u(in, mp + 4 + k);
+                    const uint32_t x = lds_ld32u_row(in, ip + 4, l) ^ lds_ld32u_row(in, mp + 4, l);
                     eq[l] = (l < room) & (pa == pb);
                     const int ln = imin(x ? (int)(__builtin_ctz(x) >> 3) : 4, imax(maxc - k, 0));
                     len[l] = ln;
@@ -579,9 +579,9 @@ CIMG_DEV int lz4_encode_body(const uint8_t* in, uint8_t* tab, int n, uint8_t* ou
             // ---- park the sequence; budget checks and stores happen 64 sequences at a time -------------------
             {
                 const int slot = np;
-                FOR_LANES(l) {
-                    if (l == slot) { P_anchor[l] = anchor; P_lit[l] = lit; P_off[l] = ip - mp; P_mcode[l] = mcode; }
-                }
+                // (four lane writes picked by a scalar lane number: the `if (l == slot)` form was a compare, an exec save / restore and
+                // four moves)
+                setlane(P_anchor, slot, anchor); setlane(P_lit, slot, lit); setlane(P_off, slot, ip - mp); setlane(P_mcode, slot, mcode);
                 if (++np == 64) {
                     bool fits_;
                     if constexpr (SEQ) fits_ = zstd_take_parked(in, out, cap, op, *sink, np, P_anchor, P_lit, P_off, P_mcode);

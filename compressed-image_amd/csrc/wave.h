@@ -410,6 +410,16 @@ CIMG_DEV uint32_t lds_ld32u(const uint8_t* lds, int off)
     return alignbyte(hi, lo, (uint32_t)off & 3u);
 }
 
+// the same for lane l of a row of dwords, lane l reading the four bytes at off + 4 l with `off` wave-uniform: the aligned start of
+// the row and the byte shift are then scalar work, and the lane adds 4 l to a scalar instead of aligning an address of its own
+CIMG_DEV uint32_t lds_ld32u_row(const uint8_t* lds, int off, int l)
+{
+    const uint8_t* row = lds + (off & ~3);
+    const uint32_t lo = *reinterpret_cast<const uint32_t*>(row + 4 * l);
+    const uint32_t hi = *reinterpret_cast<const uint32_t*>(row + 4 * l + 4);
+    return alignbyte(hi, lo, (uint32_t)off & 3u);
+}
+
 // unaligned 32-bit store to LDS: ONE ds_write_b32 on the GPU (gfx950 runs LDS in unaligned access mode)
 CIMG_DEV void lds_st32u(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 
