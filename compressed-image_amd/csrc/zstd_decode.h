@@ -562,10 +562,17 @@ CIMG_DEV int zstd_huf_stream4(const uint8_t* ls, int z0, int z1, int z2, int z3,
 }
 
 // ---- byte movers: the only lane-parallel part of the decoder (64 bytes per step) -------------------------------------------
-// non-overlapping copy
+// Copy in ascending 64-byte steps, for a source that does not overlap its destination OR lies at or above it: the literals of a
+// block wait at the end of the output area and move down (zstd_block), so the destination may sit a few bytes in front of the
+// source.  A step therefore loads in one body and stores in the next (as zstd_stage does): what a step stores lies below everything
+// later steps load, and within a step no lane reads what another lane of the same body writes (wave.h, R1).
 CIMG_DEV void zstd_copy(uint8_t* dst, const uint8_t* src, int n)
 {
-    for (int k0 = 0; k0 < n; k0 += 64) { FOR_LANES_W(l) { if (k0 + l < n) dst[k0 + l] = src[k0 + l]; } }
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        LV<uint8_t> v;
+        FOR_LANES(l) { v[l] = 0; if (k0 + l < n) v[l] = src[k0 + l]; }
+        FOR_LANES_W(l) { if (k0 + l < n) dst[k0 + l] = v[l]; }
+    }
 }
 CIMG_DEV void zstd_fill(uint8_t* dst, uint8_t v, int n)
 {
@@ -669,9 +676,14 @@ template <class DP> CIMG_DEV void zstd_store_upto16_t(DP d, const u128& v, int n
     CIMG_UNROLL
     for (int k = 0; k < 3; k++) { if (n > t + k && t + k < 16) d[t + k] = (uint8_t)(last >> (8 * k)); }
 }
+// (zstd_copy on a typed pointer: the long literal runs of a batch, source at or above the destination inside one buffer)
 template <class DP> CIMG_DEV void zstd_copy_t(DP dst, DP src, int n)
 {
-    for (int k0 = 0; k0 < n; k0 += 64) { FOR_LANES_W(l) { if (k0 + l < n) dst[k0 + l] = src[k0 + l]; } }
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        LV<uint8_t> v;
+        FOR_LANES(l) { v[l] = 0; if (k0 + l < n) v[l] = src[k0 + l]; }
+        FOR_LANES_W(l) { if (k0 + l < n) dst[k0 + l] = v[l]; }
+    }
 }
 template <class DP> CIMG_DEV void zstd_match_t(DP dst, int offset, int n)
 {

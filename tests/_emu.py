@@ -149,6 +149,23 @@ def zstd_decode(frame, cap):
     return r, out[:max(r, 0)].tobytes()
 
 
+def zstd_encode(src, order=0):
+    """One stream through csrc/zstd_encode.h under a write order: the frame's bytes, b"" for a stream that does not shrink."""
+    s = _u8(src)
+    n = s.size
+    L = lib()
+    L.emu_zstd_encode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.emu_zstd_encode.restype = C.c_int
+    dst = np.full(n + 64, 0xEE, np.uint8)
+    set_write_order(order)
+    try:
+        r = L.emu_zstd_encode(_p(s), n, _p(dst), n)
+    finally:
+        set_write_order(0)
+    assert 0 <= r < n and (dst[n:] == 0xEE).all()          # nothing is written past the stream's budget
+    return dst[:r].tobytes()
+
+
 def blosclz_encode(src, cap=None, clevel=9):
     s = _u8(src)
     n = s.size

@@ -1175,3 +1175,62 @@ def coded_frame(rng, n, flavor):
     frame, ref = got
     assert ref.size == n, (flavor, n, ref.size)
     return (frame, ref) if len(frame) < n else None
+
+
+def mix_streams(count=120, seed=5):
+    """{name: bytes}: streams of random and constant pieces whose lengths cover every literal-length and match-length code (the
+    make-up of the `mix*` inputs of test_emu_zstd.py's encoder test, from a generator of their own).  The frames the repository's
+    encoder makes of them keep their literals raw and their runs long: what the decoder's literal copies are tested on."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for k in range(count):
+        n = int(rng.integers(64, 40000))
+        pieces, left = [], n
+        while left > 0:
+            m = int(min(left, rng.choice([1, 3, 15, 16, 40, 70, 130, 300, 2000])))
+            pieces.append(rng.integers(0, 256, m, dtype=np.uint8) if rng.random() < 0.5 else np.full(m, rng.integers(0, 256), np.uint8))
+            left -= m
+        out["mix%d" % k] = np.concatenate(pieces)
+    return out
+
+
+def chunkable(frames, limit=262144):
+    """the (name, frame, output) cases a blosc2 chunk can carry as the one coded stream of a block: the stream must be SHORTER than the
+    block (a stream of the block's length is a stored one, a longer one is refused) and a block holds 1 .. 256 KiB"""
+    return [(name, fr, want) for name, fr, want in frames if 0 < len(fr) < want.size <= limit]
+
+
+def chunk_of_frame(fr, want):
+    """one chunk, one block, one stream: typesize 1, no filter"""
+    return S.chunk_of_streams(S.ZSTD, [(bytes(fr), want)])
+
+
+# The LDS of cimg_decode_zstd follows the largest block of its batch and holds stage and tables beside it: the forms of the read path
+# that need that kernel (fused, plans_overflow, no memory for plans) refuse a batch with a 150 000-byte block (ERR_CODEC_SUPPORT).  A
+# batch that every form must take stops at the largest block the planes of _streams.zstd_plane_cases prove every form takes
+# (zstd_tail33); blocks beyond LDS_BLOCK_MAX take the wide route.
+FORM_BLOCK_MAX = 131072 + 33
+LDS_BLOCK_MAX = 163840
+
+
+def frame_chunk_cases(golden_dir, encode):
+    """[(name, chunk, expected bytes)] for the batched frame tests of both legs: every spec-built frame a chunk can carry (expected:
+    what its sequences define), the frames libzstd made of inputs up to 160 KiB (tests/golden/zstd_kat.npz; expected: the golden
+    input) and the frames `encode` -- the emulated encoder in ascending order -- makes of the mix streams (expected: the stream).
+    The last two groups hold every frame the decoder's literal copies got wrong in the other write orders."""
+    import os
+    if "frame_chunks" not in _CACHE:
+        cases = list(frame_cases())
+        kat = np.load(os.path.join(golden_dir, "zstd_kat.npz"))
+        for key in kat["frames"]:
+            key = str(key)
+            src = kat["in|" + key.split("|")[0]]
+            if src.size <= 163840:
+                cases.append(("kat|" + key, kat["frame|" + key].tobytes(), src))
+        for name, src in mix_streams().items():
+            fr = encode(src)
+            if fr:
+                cases.append((name, fr, src))
+        _CACHE["frame_chunks"] = [(name, chunk_of_frame(fr, want), want) for name, fr, want in chunkable(cases)]
+    return _CACHE["frame_chunks"]
+

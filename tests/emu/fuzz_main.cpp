@@ -47,7 +47,7 @@ int main(int argc, char** argv)
 {
     const int rounds = argc > 1 ? atoi(argv[1]) : 300;
     long decoded = 0, rejected = 0;
-    for (int codec : {1, 0})                   // lz4, blosclz
+    for (int codec : {1, 0, 5})                // lz4, blosclz, zstd (the write order drawn below holds for the encode AND the decodes of a round)
     for (int ts : {1, 2, 4, 8}) {
         for (int filter : {0, 1, 2}) {
             for (int kind = 0; kind < 5; kind++) {

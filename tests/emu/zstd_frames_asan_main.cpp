@@ -1,12 +1,13 @@
 // tests/emu/zstd_frames_asan_main.cpp -- TEST INFRASTRUCTURE: zstd frames through emu_zstd_decode (emu.cpp: csrc/zstd_decode.h in place,
 // through a stage, all copies serial, and walked + replayed) under AddressSanitizer / UBSan (host code only;
-// tests/test_emu_zstd_streams.py builds it with emu.cpp and runs it once).  The file named on the command line holds a count, then
+// tests/test_emu_zstd_streams.py builds it with emu.cpp and runs it once per write order).  The file named on the command line holds a count, then
 // per frame: its size, the size of its output, the frame, the output.  Frame and destination are heap allocations of exactly their
 // size, so one byte read or written outside them is reported.  Every frame is decoded at capacity n and n + 8 and must be refused
 // at n - 1.  Prints "ok <frames>".
 // A second file, if named, holds chunks (a count, then per chunk: its size, nbytes, blocksize, 1 if it must be refused, the chunk, its
 // pixels): they go through emu_decompress_batch in one batch -- the kernels of the zstd read path with LDS modelled at its exact size
 // (EMU_LDS_SLACK=0) -- in the five forms of the read path, into an output buffer of exactly the pixels' size.  Prints "ok <chunks>".
+// A third argument, a digit, is the emulator's write order (0 ascending, 1 descending, 2 shuffled; wave.h R2) for everything above.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +19,7 @@ extern "C" int emu_decompress_batch(int nchunks, const uint8_t* comp, const int6
                                     uint8_t* raw, const int64_t* raw_off, int32_t* status);
 extern "C" void emu_set_zstd_plan(int cap);
 extern "C" void emu_set_zstd_lanes(int n);
+extern "C" void emu_set_write_order(int o);
 
 static uint32_t rd32(FILE* f)
 {
@@ -68,6 +70,7 @@ static int run_chunks(const char* path)
 int main(int argc, char** argv)
 {
     if (argc < 2) return 2;
+    emu_set_write_order(argc > 3 ? argv[3][0] - '0' : 0);
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     const uint32_t count = rd32(f);

@@ -7,6 +7,7 @@ import pytest
 
 import _emu as E
 import _oracle as O
+import _zstd_streams as Z
 from cimg import synth
 
 
@@ -15,18 +16,71 @@ def kat(golden_dir):
     return np.load(os.path.join(golden_dir, "zstd_kat.npz"))
 
 
+ORDERS = (0, 1, 2)
+
+
+def in_every_write_order(fn):
+    """Run the test once in each order in which the emulator visits the lanes of a FOR_LANES_W body (csrc/wave.h, R2: ascending,
+    descending, shuffled) and put the ascending order back.  The test keeps its name and its other arguments; one that names a
+    `write_order` argument is told the order.  A result must not depend on it: positive frames give their input's BYTES in every
+    order (two copy loops that read what another lane of the same body had stored returned the right length over wrong bytes in
+    the other two orders)."""
+    import functools
+    import inspect
+    sig = inspect.signature(fn)
+    wants = "write_order" in sig.parameters
+
+    @functools.wraps(fn)
+    def run(*args, **kw):
+        try:
+            for order in ORDERS:
+                E.set_write_order(order)
+                try:
+                    fn(*args, **kw, **({"write_order": order} if wants else {}))
+                except AssertionError as e:
+                    raise AssertionError("in write order %d: %s" % (order, e)) from e
+        finally:
+            E.set_write_order(0)
+    del run.__wrapped__
+    run.__signature__ = sig.replace(parameters=[p for name, p in sig.parameters.items() if name != "write_order"])
+    return run
+
+
+@pytest.fixture(params=ORDERS, ids=["ascending", "descending", "shuffled"])
+def write_order(request):
+    """the same as a parameter, for the tests that are about the order"""
+    E.set_write_order(request.param)
+    yield request.param
+    E.set_write_order(0)
+
+
+def libzstd_decodes(frame, src):
+    """the frame through the box's libzstd (the oracle's loader): independent of the emulated decoder"""
+    import ctypes as C
+    OL = O.lib()
+    OL.orc_zstd_decompress_stream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    OL.orc_zstd_decompress_stream.restype = C.c_int
+    fr = np.frombuffer(frame, np.uint8).copy()
+    out = np.zeros(src.size, np.uint8)
+    return OL.orc_zstd_decompress_stream(fr.ctypes.data, fr.size, out.ctypes.data, src.size) == src.size and out.tobytes() == src.tobytes()
+
+
+@in_every_write_order
 def test_every_golden_frame_decodes_to_its_input(kat):
     n = 0
     for key in kat["frames"]:
         key = str(key)
         src = kat["in|" + key.split("|")[0]]
-        r, out = E.zstd_decode(kat["frame|" + key], src.size + 8)
-        assert r == src.size, (key, r)
-        assert out == src.tobytes(), key
+        # (with room behind the output the literals wait a few bytes above where they go; at exact capacity the last run lies in place)
+        for cap in (src.size + 8, src.size):
+            r, out = E.zstd_decode(kat["frame|" + key], cap)
+            assert r == src.size, (key, cap, r)
+            assert out == src.tobytes(), (key, cap)
         n += 1
     assert n >= 100
 
 
+@in_every_write_order
 def test_exact_capacity_and_short_capacity(kat):
     src = kat["in|text"]
     fr = kat["frame|text|L3"]
@@ -38,22 +92,35 @@ def test_exact_capacity_and_short_capacity(kat):
 
 def test_damaged_frames_fail_cleanly(kat):
     """Truncations and bit flips: an error or (for a flipped literal) wrong bytes -- never a crash, never a read or write
-    outside the buffers (the emulator build of CI runs this under ASAN, tests/test_emu_fuzz.py)."""
+    outside the buffers (the emulator build of CI runs this under ASAN, tests/test_emu_fuzz.py).  An error is an error in every
+    write order, and a frame that still decodes gives the same length and bytes in every order."""
     rng = np.random.default_rng(5)
-    for key in ("text|L3", "natural_plane|L19", "tiled_hi_plane|L1", "skewed_16k|L5", "two_blocks_150k|L1"):
-        fr = kat["frame|" + key].copy()
-        n = kat["in|" + key.split("|")[0]].size
-        for cut in (0, 3, 5, 9, fr.size // 2, fr.size - 1):
-            r, _ = E.zstd_decode(fr[:cut], n)
-            assert r < 0, (key, cut)
-        for _ in range(60):
-            bad = fr.copy()
-            i = int(rng.integers(0, bad.size))
-            bad[i] ^= 1 << int(rng.integers(0, 8))
-            r, out = E.zstd_decode(bad, n)
-            assert r <= n
+    try:
+        for key in ("text|L3", "natural_plane|L19", "tiled_hi_plane|L1", "skewed_16k|L5", "two_blocks_150k|L1"):
+            fr = kat["frame|" + key].copy()
+            n = kat["in|" + key.split("|")[0]].size
+            for cut in (0, 3, 5, 9, fr.size // 2, fr.size - 1):
+                for order in ORDERS:
+                    E.set_write_order(order)
+                    r, _ = E.zstd_decode(fr[:cut], n)
+                    assert r < 0, (key, cut, order)
+            for _ in range(60):
+                bad = fr.copy()
+                i = int(rng.integers(0, bad.size))
+                bad[i] ^= 1 << int(rng.integers(0, 8))
+                E.set_write_order(0)
+                r, out = E.zstd_decode(bad, n)
+                assert r <= n
+                for order in ORDERS[1:]:
+                    E.set_write_order(order)
+                    r2, out2 = E.zstd_decode(bad, n)
+                    assert (r2 < 0) == (r < 0), (key, i, order, r, r2)
+                    assert r2 < 0 or (r2 == r and out2 == out), (key, i, order, r, r2)
+    finally:
+        E.set_write_order(0)
 
 
+@in_every_write_order
 def test_blosc2_zstd_chunks_decode_through_the_kernels(kat):
     """Chunks framed the way c-blosc2 frames enums::codec::zstd (codec format 4; split and unsplit, run tokens, stored
     streams, leftover blocks) go lean kernel -> general kernel (ERR_CODEC_SUPPORT) -> zstd kernel, as in the engine."""
@@ -81,6 +148,7 @@ def zstd_read_path(request):
     E.set_zstd_lanes(8)
 
 
+@in_every_write_order
 def test_plans_that_do_not_fit_are_counted_and_their_blocks_still_decode(kat, zstd_read_path):
     name = "natural_f32_split"
     chunk = kat["chunk|" + name]; src = kat["cin|" + name]
@@ -111,6 +179,7 @@ def test_a_block_nobody_decoded_fails_the_batch(kat, zstd_read_path):
     assert rc == 0 and out[0].tobytes() == src.tobytes()
 
 
+@in_every_write_order
 def test_split_and_unsplit_zstd_chunks_in_one_batch(kat):
     """Split chunks go to the two-waves-per-block launch, chunks of one stream per block to the one-wave launch (engine.hip:
     decompress_finish; each launch reads its own kind only): one batch with both, and LZ4 chunks between them."""
@@ -126,6 +195,7 @@ def test_split_and_unsplit_zstd_chunks_in_one_batch(kat):
         assert o.tobytes() == s_.tobytes(), n
 
 
+@in_every_write_order
 def test_the_lowest_damaged_stream_of_a_split_block_is_the_one_reported(kat):
     """Two waves share the streams of a block; what the chunk reports is what decoding the streams in order reports: damage in a
     LATER stream only (a stream header that points outside the chunk = ERR_READ_BUFFER) against damage in the first frame (ERR_DATA
@@ -152,6 +222,7 @@ def test_the_lowest_damaged_stream_of_a_split_block_is_the_one_reported(kat):
     assert nblocks >= 1
 
 
+@in_every_write_order
 def test_a_damaged_zstd_chunk_reports_an_error_and_leaves_its_neighbours_alone(kat):
     good = kat["chunk|tiled_u16_split"]
     src = kat["cin|tiled_u16_split"]
@@ -165,6 +236,7 @@ def test_a_damaged_zstd_chunk_reports_an_error_and_leaves_its_neighbours_alone(k
     assert out[0].tobytes() == src.tobytes() and out[2].tobytes() == src.tobytes()
 
 
+@in_every_write_order
 def test_chunks_made_with_the_local_libzstd(golden_dir, zstd_read_path):
     """Beyond the committed vectors: every element size, split and unsplit, ragged last block -- made here with the system
     libzstd (skipped where there is none), decoded by the emulated kernels."""
@@ -283,30 +355,84 @@ def test_zstd_encoder_frames_decode_with_libzstd_and_with_the_own_decoder():
             left -= m
         cases["mix%d" % k] = np.concatenate(pieces)
     coded = 0
-    for name, src in cases.items():
-        n = src.size
-        dst = np.full(n + 64, 0xEE, np.uint8)
-        r = L.emu_zstd_encode(src.ctypes.data, n, dst.ctypes.data, n)
-        assert 0 <= r < n, name
-        assert (dst[n:] == 0xEE).all(), name                      # nothing is written past the stream's budget
-        if r == 0:
-            continue
-        coded += 1
-        assert bytes(dst[:4]) == b"\x28\xb5\x2f\xfd"
-        r2, own = E.zstd_decode(dst[:r].tobytes(), n)
-        assert r2 == n and own == src.tobytes(), name
-        if have:
-            out = np.zeros(n, np.uint8)
-            assert OL.orc_zstd_decompress_stream(dst.ctypes.data, r, out.ctypes.data, n) == n, name
-            assert out.tobytes() == src.tobytes(), name
+    try:
+        for name, src in cases.items():
+            n = src.size
+            made = []
+            for order in ORDERS:                                      # the frame's bytes do not depend on the emulator's write order
+                E.set_write_order(order)
+                dst = np.full(n + 64, 0xEE, np.uint8)
+                r = L.emu_zstd_encode(src.ctypes.data, n, dst.ctypes.data, n)
+                assert 0 <= r < n, (name, order)
+                assert (dst[n:] == 0xEE).all(), (name, order)         # nothing is written past the stream's budget
+                made.append(dst[:r].tobytes())
+            assert made[0] == made[1] == made[2], name
+            if r == 0:
+                continue
+            coded += 1
+            assert made[0][:4] == b"\x28\xb5\x2f\xfd"
+            if have:                                                  # (the encoder's witness: shares nothing with the emulated decoder)
+                out = np.zeros(n, np.uint8)
+                assert OL.orc_zstd_decompress_stream(dst.ctypes.data, r, out.ctypes.data, n) == n, name
+                assert out.tobytes() == src.tobytes(), name
+            for order in ORDERS:
+                E.set_write_order(order)
+                for cap in (n, n + 8):
+                    r2, own = E.zstd_decode(made[0], cap)
+                    assert r2 == n and own == src.tobytes(), (name, order, cap)
+    finally:
+        E.set_write_order(0)
     assert coded >= 40
     assert L.emu_zstd_encode(cases["random"].ctypes.data, 16384, np.zeros(16500, np.uint8).ctypes.data, 16384) == 0   # noise: no frame
 
 
-def test_zstd_and_lz4hc_chunks_from_the_emulated_kernels():
+def test_mix_streams_encode_to_the_same_bytes_and_decode_in_every_write_order(write_order):
+    """120 streams of literal and match runs at seed 5: the encoder's frame is the same in every write order (it is compared with the
+    ascending one), libzstd reads it, and the decoder returns the input's bytes at exact capacity and with room."""
+    have = O.zstd_available()
+    coded = 0
+    for name, src in Z.mix_streams().items():
+        frame = E.zstd_encode(src, 0)
+        assert E.zstd_encode(src, write_order) == frame, name
+        if not frame:
+            continue
+        coded += 1
+        if have and write_order == 0:
+            assert libzstd_decodes(frame, src), name
+        E.set_write_order(write_order)
+        for cap in (src.size, src.size + 8):
+            r, own = E.zstd_decode(frame, cap)
+            assert r == src.size and own == src.tobytes(), (name, cap, r)
+    assert coded >= 100
+
+
+def compress_batch_in_order(order, *args):
+    """E.compress_batch under a write order; the chunks must be those of the ascending order"""
+    rc0, cb0, chunks0 = E.compress_batch(*args)
+    if order:
+        E.set_write_order(order)
+        try:
+            rc, cb, chunks = E.compress_batch(*args)
+        finally:
+            E.set_write_order(0)
+        assert (rc, cb) == (rc0, cb0) and chunks == chunks0, "chunk bytes depend on the write order %d" % order
+    return rc0, cb0, chunks0
+
+
+def decompress_batch_in_order(order, *args):
+    E.set_write_order(order)
+    try:
+        return E.decompress_batch(*args)
+    finally:
+        E.set_write_order(0)
+
+
+@in_every_write_order
+def test_zstd_and_lz4hc_chunks_from_the_emulated_kernels(write_order):
     """Whole chunks with codec::zstd / codec::lz4hc through the emulated encode kernels + in-launch assembly: the checker's chunk
     layer (libzstd / the LZ4 block decoder) and the emulated decode kernels both return the pixels; lz4hc chunks equal the checker's
-    twin (LZ4 fast at acceleration 1 under compcode 2) byte for byte; zstd splits planes up to clevel 5 like c-blosc2."""
+    twin (LZ4 fast at acceleration 1 under compcode 2) byte for byte; zstd splits planes up to clevel 5 like c-blosc2.  In every
+    write order: the chunks are byte for byte those of the ascending order, and the decode kernels run in the order too."""
     import _oracle as O
     for codec in (O.ZSTD, O.LZ4HC):
         for clevel in (9, 5, 1):
@@ -319,7 +445,7 @@ def test_zstd_and_lz4hc_chunks_from_the_emulated_kernels():
                 raw = np.ascontiguousarray(arr).view(np.uint8).ravel()
                 chunk = 131072 if raw.size == 409600 else 65536
                 sizes = [min(chunk, raw.size - o) for o in range(0, raw.size, chunk)]
-                rc, cb, chunks = E.compress_batch(E.cparams(it, clevel=clevel, compcode=codec), raw, sizes, [chunk + 32] * len(sizes))
+                rc, cb, chunks = compress_batch_in_order(write_order, E.cparams(it, clevel=clevel, compcode=codec), raw, sizes, [chunk + 32] * len(sizes))
                 assert rc == 0
                 off = 0
                 for c, n in zip(chunks, sizes):
@@ -332,7 +458,7 @@ def test_zstd_and_lz4hc_chunks_from_the_emulated_kernels():
                     if codec == O.LZ4HC:
                         assert c == O.compress(O.cparams(it, clevel=clevel, compcode=O.LZ4HC), raw[off:off + n], destsize=chunk + 32)[1]
                     off += n
-                rc, status, outs = E.decompress_batch(chunks, sizes, [O.cbuffer_sizes(c)[2] for c in chunks])
+                rc, status, outs = decompress_batch_in_order(write_order, chunks, sizes, [O.cbuffer_sizes(c)[2] for c in chunks])
                 assert rc == 0 and not any(status)
                 assert b"".join(o.tobytes() for o in outs) == raw.tobytes()
 
@@ -341,11 +467,22 @@ def test_randomized_geometries_zstd_and_lz4hc_on_the_emulated_kernels():
     """The GPU test of the same name (tests/test_gpu_parity.py) at sizes the lane emulator finishes in seconds: random element size,
     block size, chunk size, level, filter, dest capacity and data make-up through the emulated encode kernels; the checker
     (libzstd / the LZ4 block decoder under the oracle's chunk layer) and the emulated decode kernels both return the input."""
+    randomized_geometries(int(os.environ.get("CIMG_TEST_ROUNDS", "200")), 0)
+
+
+@pytest.mark.parametrize("order", ORDERS[1:])
+def test_randomized_geometries_in_the_other_write_orders(order):
+    """the first 40 rounds of the test above (the same seed, so the same geometries) in the descending and the shuffled order: the
+    chunks are byte for byte those of the ascending order, and the decode kernels return the input in that order too"""
+    randomized_geometries(40, order)
+
+
+def randomized_geometries(rounds, order):
     import _oracle as O
     from test_gpu_parity import _mixed_data
     rng = np.random.default_rng(20260304 + int(os.environ.get("CIMG_TEST_SEED", "0")))
     have_zstd = O.zstd_available()
-    for it in range(int(os.environ.get("CIMG_TEST_ROUNDS", "200"))):
+    for it in range(rounds):
         codec = O.ZSTD if it % 3 else O.LZ4HC
         ts = int(rng.choice([1, 2, 2, 4, 4, 8, 3]))
         blocksize = int(rng.choice([256, 1024, 4096, 8192, 32768, 65536])) // ts * ts
@@ -359,7 +496,7 @@ def test_randomized_geometries_zstd_and_lz4hc_on_the_emulated_kernels():
         dest = chunk + 32 if rng.random() < 0.7 else max(40, int(chunk * rng.uniform(0.3, 1.0)))
         sizes = [min(chunk, total - o) for o in range(0, total, chunk)]
         what = (it, codec, ts, blocksize, chunk, clevel, filt, dest)
-        rc, cb, chunks = E.compress_batch(E.cparams(ts, clevel=clevel, blocksize=blocksize, compcode=codec, filters=(0, 0, 0, 0, 0, filt)), raw, sizes, [dest] * len(sizes))
+        rc, cb, chunks = compress_batch_in_order(order, E.cparams(ts, clevel=clevel, blocksize=blocksize, compcode=codec, filters=(0, 0, 0, 0, 0, filt)), raw, sizes, [dest] * len(sizes))
         assert rc == 0, what
         off = 0
         live, live_sizes = [], []
@@ -373,7 +510,7 @@ def test_randomized_geometries_zstd_and_lz4hc_on_the_emulated_kernels():
                 live.append((c, n, off))
             off += n
         if live:
-            rc, status, outs = E.decompress_batch([c for c, _, _ in live], [n for _, n, _ in live], [O.cbuffer_sizes(c)[2] for c, _, _ in live])
+            rc, status, outs = decompress_batch_in_order(order, [c for c, _, _ in live], [n for _, n, _ in live], [O.cbuffer_sizes(c)[2] for c, _, _ in live])
             assert rc == 0 and not any(status), (what, status)
             for o, (_, n, at) in zip(outs, live):
                 assert o.tobytes() == raw[at:at + n].tobytes(), what

@@ -88,6 +88,44 @@ def zstd_read_path(request):
     E.set_zstd_lanes(8)
 
 
+ORDERS = (0, 1, 2)
+
+
+def in_every_write_order(fn):
+    """Run the test once in each order in which the emulator visits the lanes of a FOR_LANES_W body (csrc/wave.h, R2: ascending,
+    descending, shuffled) and put the ascending order back.  The test keeps its name and its other arguments; one that names a
+    `write_order` argument is told the order.  A result must not depend on it: positive frames give their input's BYTES in every
+    order (two copy loops that read what another lane of the same body had stored returned the right length over wrong bytes in
+    the other two orders)."""
+    import functools
+    import inspect
+    sig = inspect.signature(fn)
+    wants = "write_order" in sig.parameters
+
+    @functools.wraps(fn)
+    def run(*args, **kw):
+        try:
+            for order in ORDERS:
+                E.set_write_order(order)
+                try:
+                    fn(*args, **kw, **({"write_order": order} if wants else {}))
+                except AssertionError as e:
+                    raise AssertionError("in write order %d: %s" % (order, e)) from e
+        finally:
+            E.set_write_order(0)
+    del run.__wrapped__
+    run.__signature__ = sig.replace(parameters=[p for name, p in sig.parameters.items() if name != "write_order"])
+    return run
+
+
+@pytest.fixture(params=ORDERS, ids=["ascending", "descending", "shuffled"])
+def write_order(request):
+    """the same as a parameter (the library of the wide route keeps an order of its own: emu_batch sets it)"""
+    E.set_write_order(request.param)
+    yield request.param
+    E.set_write_order(0)
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -107,8 +145,9 @@ def want_buffer(parts, raw_off, size):
     return want
 
 
-def emu_batch(chunks, wide=None):
-    """the emulated batch decode into a canary-filled buffer -> (rc, status, whole buffer, raw_off)"""
+def emu_batch(chunks, wide=None, order=0):
+    """the emulated batch decode into a canary-filled buffer -> (rc, status, whole buffer, raw_off); order: the write order of the
+    wide route's library (the write_order fixture sets the other one)"""
     buf, off, cs = concat(chunks)
     nb, bs = sizes(chunks)
     raw_off, size = out_layout(nb)
@@ -117,7 +156,11 @@ def emu_batch(chunks, wide=None):
     if wide is None:
         rc = E.lib().emu_decompress_batch(len(chunks), _p(buf), _p(off), _p(nb), _p(bs), _p(raw), _p(raw_off), _p(st))
     else:
-        rc = wide.zwemu_decompress_batch(len(chunks), _p(buf), _p(off), _p(cs), _p(nb), _p(bs), _p(raw), _p(raw_off), _p(st))
+        wide.emu_set_write_order(order)
+        try:
+            rc = wide.zwemu_decompress_batch(len(chunks), _p(buf), _p(off), _p(cs), _p(nb), _p(bs), _p(raw), _p(raw_off), _p(st))
+        finally:
+            wide.emu_set_write_order(0)
     return rc, st, raw, raw_off
 
 
@@ -227,6 +270,7 @@ def test_digests_match_the_committed_ones(frames, golden_dir):
 
 
 # ---- bare frames ------------------------------------------------------------------------------------------------------------------
+@in_every_write_order
 def test_every_frame_at_exact_capacity_and_with_room_and_not_without(frames):
     for name, fr, want in frames:
         for cap in (want.size, want.size + 8):
@@ -237,6 +281,7 @@ def test_every_frame_at_exact_capacity_and_with_room_and_not_without(frames):
             assert r < 0, (name, r)
 
 
+@in_every_write_order
 def test_tail_frames_made_by_the_local_libzstd(libzstd):
     if libzstd is None:
         pytest.skip("no system libzstd on this box")
@@ -245,6 +290,7 @@ def test_tail_frames_made_by_the_local_libzstd(libzstd):
         assert r == src.size and out == src.tobytes(), (name, r)
 
 
+@in_every_write_order
 def test_bad_frames_are_refused():
     for name, fr, n, code in Z.bad_frames():
         for cap in (n, n + 8):
@@ -254,7 +300,7 @@ def test_bad_frames_are_refused():
 
 def test_tail_frames_under_address_sanitizer(frames, libzstd, tmp_path_factory):
     """frames A - C, the short-last-block frames and (where there is a libzstd) the 128 KiB + 15 / 17 / 33 ones through emu_zstd_decode
-    in a stand-alone ASan / UBSan program: every buffer an allocation of its exact size"""
+    in a stand-alone ASan / UBSan program: every buffer an allocation of its exact size; once in each write order"""
     d = tmp_path_factory.mktemp("zstd_frames_asan")
     exe = str(d / "zstd_frames_asan")
     subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEMU_LDS_SLACK=0", "-std=c++17",
@@ -284,8 +330,9 @@ def test_tail_frames_under_address_sanitizer(frames, libzstd, tmp_path_factory):
         f.write(len(batch).to_bytes(4, "little"))
         for c, px, refused in batch:
             f.write(len(c).to_bytes(4, "little") + len(px).to_bytes(4, "little") + c[8:12] + refused.to_bytes(4, "little") + c + px)
-    r = subprocess.run([exe, path, cpath], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stdout.split() == ["ok", str(len(picked)), "ok", str(len(batch))], r.stdout[-2000:] + r.stderr[-3000:]
+    for order in ORDERS:
+        r = subprocess.run([exe, path, cpath, str(order)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and r.stdout.split() == ["ok", str(len(picked)), "ok", str(len(batch))], (order, r.stdout[-2000:] + r.stderr[-3000:])
 
 
 # ---- chunks -----------------------------------------------------------------------------------------------------------------------
@@ -305,12 +352,13 @@ def test_chunk_header_is_the_oracles():
 
 
 @pytest.mark.parametrize("case", PLANES, ids=[c[0] for c in PLANES])
-def test_generated_chunks_every_form(case, zstd_read_path):
+@in_every_write_order
+def test_generated_chunks_every_form(case, zstd_read_path, write_order):
     name, codec, ts, kw = case
     chunks, plane, counts = S.build_plane(name, codec, ts, kw)
     assert counts["coded"] >= (2 if kw["policy"] == "all" else 3), counts
     parts = split_plane(chunks, plane)
-    if O.zstd_available() and zstd_read_path == "planned":
+    if O.zstd_available() and zstd_read_path == "planned" and write_order == 0:
         for c, p in zip(chunks, parts):
             r, out = O.decompress(c)
             assert r == p.size and np.array_equal(out, p)
@@ -324,17 +372,47 @@ def test_generated_chunks_every_form(case, zstd_read_path):
 
 
 @pytest.mark.parametrize("case", PLANES, ids=[c[0] for c in PLANES])
-def test_generated_chunks_wide_route(ZW, case):
+@in_every_write_order
+def test_generated_chunks_wide_route(ZW, case, write_order):
     """the route the engine takes with comp_size (blocks beyond LDS: the wide kernel leaves zstd blocks to the wide walk + replay)"""
     name, codec, ts, kw = case
     chunks, plane, _ = S.build_plane(name, codec, ts, kw)
     parts = split_plane(chunks, plane)
-    rc, st, raw, raw_off = emu_batch(chunks, wide=ZW)
+    rc, st, raw, raw_off = emu_batch(chunks, wide=ZW, order=write_order)
     assert rc == 0 and not any(st), st
     assert np.array_equal(raw, want_buffer(parts, raw_off, raw.size))
 
 
-def test_bad_frames_in_a_batch_between_good_chunks(ZW, zstd_read_path):
+def test_every_frame_as_the_one_stream_of_a_chunk_in_one_batch(ZW, zstd_read_path, write_order, golden_dir):
+    """what tests/test_gpu_zstd_streams.py sends to the GPU, here through the emulated kernels: every spec-built frame a chunk can
+    carry, the golden libzstd frames up to 160 KiB and the encoder's frames of the mix streams, one stream per chunk, all chunks of
+    up to 128 KiB + 33 in ONE batch (canaries around every output) in every form; the seven larger ones that fit LDS in a batch of
+    their own in the planned form (Z.FORM_BLOCK_MAX says why), the three frames beyond LDS through the wide route"""
+    cases = Z.frame_chunk_cases(golden_dir, E.zstd_encode)
+    assert len(cases) >= 300 and {"frame_A", "kat|nibbles_16k|L1", "mix18"} - {c[0] for c in cases} == {"frame_A"}   # (frame A is longer than its output)
+    normal = [c for c in cases if c[2].size <= Z.FORM_BLOCK_MAX]
+    if zstd_read_path == "planned":
+        large = [c for c in cases if Z.FORM_BLOCK_MAX < c[2].size <= Z.LDS_BLOCK_MAX]
+        assert len(large) == 7
+        rc, st, raw, raw_off = emu_batch([c for _, c, _ in large])
+        assert rc == 0 and not st.any(), st
+        assert np.array_equal(raw, want_buffer([w for _, _, w in large], raw_off, raw.size))
+    rc, st, raw, raw_off = emu_batch([c for _, c, _ in normal])
+    assert rc == 0 and not st.any(), [(n, int(s)) for (n, _, _), s in zip(normal, st) if s]
+    want = want_buffer([w for _, _, w in normal], raw_off, raw.size)
+    for (name, _, w), o in zip(normal, raw_off):
+        assert np.array_equal(raw[o:o + w.size], w), name
+    assert np.array_equal(raw, want)
+    if zstd_read_path == "planned":
+        wide = [c for c in cases if c[2].size > Z.LDS_BLOCK_MAX]
+        assert len(wide) == 3
+        rc, st, raw, raw_off = emu_batch([c for _, c, _ in wide], wide=ZW, order=write_order)
+        assert rc == 0 and not st.any(), st
+        assert np.array_equal(raw, want_buffer([w for _, _, w in wide], raw_off, raw.size))
+
+
+@in_every_write_order
+def test_bad_frames_in_a_batch_between_good_chunks(ZW, zstd_read_path, write_order):
     good, gplane, _ = S.build_plane(*PLANES[0][:3], PLANES[0][3], nchunks=1)
     batch, want, bad_at = [], [], []
     for name, fr, n, code in Z.bad_frames():
@@ -344,7 +422,7 @@ def test_bad_frames_in_a_batch_between_good_chunks(ZW, zstd_read_path):
     batch.append(good[0])
     want.append(gplane)
     for wide in (None, ZW):
-        rc, st, raw, raw_off = emu_batch(batch, wide=wide)
+        rc, st, raw, raw_off = emu_batch(batch, wide=wide, order=write_order)
         assert rc == 0
         for k, name, code in bad_at:
             assert st[k] < 0 and (code is None or st[k] == code), (name, st[k])

@@ -8,7 +8,9 @@ directory, with the flags of tests/emu/Makefile.  Checked:
     encoder writes nothing past its budget,
   * round trips at 128 / 192 / 256 KiB blocks for float32 / float16 / uint8 at clevel 5 and 9,
   * chunks libzstd wrote with 160 / 192 / 256 KiB blocks (tests/golden/zstd_wide_kat.npz, make_zstd_wide_golden.py),
-  * a corrupt frame and a truncated chunk, and the 256 KiB ceiling.
+  * a corrupt frame and a truncated chunk, and the 256 KiB ceiling,
+  * all of it in the three write orders of the emulator (csrc/wave.h, R2): what the encoders write is byte for byte what they write
+    in the ascending order, and the read path returns the pixels in every order.
 """
 import ctypes as C
 import ctypes.util
@@ -63,6 +65,49 @@ def libzstd():
     return z
 
 
+ORDERS = (0, 1, 2)
+_order = 0                 # the write order of the running test (in_every_write_order)
+
+
+def set_order(Z, order):
+    """both libraries keep an order: the wide one (Z) and the one behind _emu.zstd_decode"""
+    Z.emu_set_write_order(order)
+    E.set_write_order(order)
+
+
+def use_order(Z, order):
+    global _order
+    _order = order
+    set_order(Z, order)
+
+
+def in_every_write_order(fn):
+    """Run the test once in each order in which the emulator visits the lanes of a FOR_LANES_W body (csrc/wave.h, R2: ascending,
+    descending, shuffled) and put the ascending order back.  The test keeps its name and its other arguments; one that names a
+    `write_order` argument is told the order (every test here takes the library fixture Z, by name).  A result must not depend on it: positive frames give their input's BYTES in every
+    order (two copy loops that read what another lane of the same body had stored returned the right length over wrong bytes in
+    the other two orders)."""
+    import functools
+    import inspect
+    sig = inspect.signature(fn)
+    wants = "write_order" in sig.parameters
+
+    @functools.wraps(fn)
+    def run(*args, **kw):
+        try:
+            for order in ORDERS:
+                use_order(kw["Z"], order)
+                try:
+                    fn(*args, **kw, **({"write_order": order} if wants else {}))
+                except AssertionError as e:
+                    raise AssertionError("in write order %d: %s" % (order, e)) from e
+        finally:
+            use_order(kw["Z"], 0)
+    del run.__wrapped__
+    run.__signature__ = sig.replace(parameters=[p for name, p in sig.parameters.items() if name != "write_order"])
+    return run
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -75,7 +120,20 @@ def cparams(ts, blocksize, compcode=ZSTD, clevel=9, splitmode=3, filt=1):
 
 
 def compress(Z, p, chunks):
-    """chunks: list of uint8 arrays -> (rc, [chunk bytes])"""
+    """chunks: list of uint8 arrays -> (rc, [chunk bytes]), written in the ascending order; in another write order the encoders
+    run once more and must return the same code and the same bytes"""
+    set_order(Z, 0)
+    try:
+        rc, out = compress_once(Z, p, chunks)
+        if _order:
+            set_order(Z, _order)
+            assert compress_once(Z, p, chunks) == (rc, out), "chunk bytes depend on the write order %d" % _order
+    finally:
+        set_order(Z, _order)
+    return rc, out
+
+
+def compress_once(Z, p, chunks):
     n = len(chunks)
     raw = np.concatenate(chunks)
     nbytes = np.array([c.size for c in chunks], np.int32)
@@ -126,7 +184,8 @@ def _streams():
     }
 
 
-def test_wide_frames_decode_with_libzstd_and_our_decoder(Z, libzstd):
+@in_every_write_order
+def test_wide_frames_decode_with_libzstd_and_our_decoder(Z, libzstd, write_order):
     written = 0
     for name, src in _streams().items():
         n = src.size
@@ -135,6 +194,12 @@ def test_wide_frames_decode_with_libzstd_and_our_decoder(Z, libzstd):
             r = Z.zwemu_zstd_encode(_p(src), n, _p(out), cap)
             assert 0 <= r < n and r <= cap, (name, cap, r)
             assert (out[cap:] == 0xEE).all(), (name, cap)        # nothing past the budget
+            if write_order:                                      # the frame is the one the ascending order writes
+                set_order(Z, 0)
+                out0 = np.full(n + 4096, 0xEE, np.uint8)
+                r0 = Z.zwemu_zstd_encode(_p(src), n, _p(out0), cap)
+                set_order(Z, write_order)
+                assert r0 == r and np.array_equal(out0, out), (name, cap)
             if r == 0:
                 continue
             written += 1
@@ -151,6 +216,7 @@ def test_wide_frames_decode_with_libzstd_and_our_decoder(Z, libzstd):
 @pytest.mark.parametrize("dt", [np.float32, np.float16, np.uint8])
 @pytest.mark.parametrize("blk", [131072, 196608, 262144])
 @pytest.mark.parametrize("clevel", [5, 9])
+@in_every_write_order
 def test_round_trip_table(Z, dt, blk, clevel):
     it = np.dtype(dt).itemsize
     arr = synth.natural_channel(dt, 1024, 1048576 // 1024 // it)
@@ -173,6 +239,7 @@ def _periodic_images():
 
 
 @pytest.mark.parametrize("clevel", [5, 9])
+@in_every_write_order
 def test_streams_that_are_one_match_per_zstd_block_round_trip(Z, clevel):
     for name, img, filt in _periodic_images():
         raw = np.ascontiguousarray(img).view(np.uint8).ravel()
@@ -184,6 +251,7 @@ def test_streams_that_are_one_match_per_zstd_block_round_trip(Z, clevel):
         assert out[0] == raw.tobytes(), name
 
 
+@in_every_write_order
 def test_float32_clevel5_256k_is_written_by_the_normal_path_and_read_by_the_wide_one(Z):
     arr = synth.natural_channel(np.float32, 512, 512)
     raw = arr.view(np.uint8).ravel()
@@ -194,6 +262,7 @@ def test_float32_clevel5_256k_is_written_by_the_normal_path_and_read_by_the_wide
     assert out[0] == raw.tobytes()
 
 
+@in_every_write_order
 def test_a_mixed_batch_decodes_in_one_call(Z):
     small = synth.tiled_channel(np.float16, 512, 256).view(np.uint8).ravel()
     big = synth.natural_channel(np.uint16, 1024, 512).view(np.uint8).ravel()
@@ -224,6 +293,7 @@ def golden_inputs(golden_dir, wkat):
     return inputs
 
 
+@in_every_write_order
 def test_libzstd_chunks_decode(Z, wkat, golden_inputs):
     names = [str(n) for n in wkat["chunks"]]
     assert len(names) >= 20
@@ -238,6 +308,7 @@ def test_libzstd_chunks_decode(Z, wkat, golden_inputs):
     assert all(o == golden_inputs[n][0].tobytes() for o, n in zip(out, names))
 
 
+@in_every_write_order
 def test_corrupt_frame_and_truncated_chunk(Z):
     raw = synth.natural_channel(np.uint8, 1024, 512).ravel()
     rc, chunks = compress(Z, cparams(1, 262144), [raw])

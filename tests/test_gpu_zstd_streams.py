@@ -7,6 +7,12 @@ windows of tests/_windows.py; then once per form of the zstd read path (one engi
 test_every_form_of_the_zstd_read_path_on_the_gpu does).  The frames every decoder must refuse run in a batch between good chunks.
 Pixel bytes, the status of every chunk and the canary around the outputs are asserted.  Nothing here is meant to fault: the invalid
 frames are ordinary decode traffic that must be reported.
+
+Then every frame on its own (tests/_zstd_streams.py: frame_chunk_cases): each spec-built frame a chunk can carry, the frames libzstd
+made of the golden inputs up to 160 KiB and the frames the repository's encoder makes of the mix streams -- among the last two groups
+every frame whose literal copies the host emulator got wrong in its descending and shuffled write orders -- one
+stream per chunk, all of them in ONE batch per entry point and per form of the read path, canaries around every output.  Expected
+bytes: what the frames' sequences define, the golden inputs, the streams; never anything the code under test computed.
 """
 import hashlib
 import json
@@ -170,3 +176,92 @@ def test_bad_frames_are_reported_on_every_entry_point(eng, dctx, planes):
         dev, host, _, _ = windows_both(eng, [chunk], 1, [dict(chunk_first=0, chunk_count=1, origin=0, row_pitch=n, width=n, height=1)])
         for what, (rc, st, _) in (("device", dev), ("host", host)):
             assert rc < 0 and st[0] < 0, (name, what, rc, st)
+
+
+# ---- every frame as the one stream of a chunk --------------------------------------------------------------------------------------
+LDS_BLOCK_MAX, FORM_BLOCK_MAX = Z.LDS_BLOCK_MAX, Z.FORM_BLOCK_MAX
+
+
+@pytest.fixture(scope="module")
+def frame_chunks(golden_dir):
+    """(name, chunk, expected bytes): the spec-built frames against the digests libzstd validated, before anything is decoded"""
+    import _emu as Em
+    cases = Z.frame_chunk_cases(golden_dir, Em.zstd_encode)
+    with open(os.path.join(golden_dir, "zstd_streams_digests.json")) as f:
+        pinned = json.load(f)["frames"]
+    seen = 0
+    for name, chunk, want in cases:
+        assert want.size == int.from_bytes(chunk[4:8], "little") and 0 < len(chunk) - 40 < want.size, name
+        if name in pinned:
+            assert pinned[name] == [hashlib.sha256(chunk[40:]).hexdigest(), hashlib.sha256(want.tobytes()).hexdigest()], name
+            seen += 1
+    names = {c[0] for c in cases}
+    assert seen >= 150 and len(cases) >= 300 and "kat|nibbles_16k|L1" in names and "mix18" in names
+    return cases
+
+
+def check_frame_batch(e, cases, what, refused_wide=False):
+    """one decompress_device call (canaries between the outputs) and one decompress_host call over all the chunks"""
+    chunks = [c for _, c, _ in cases]
+    st, out, raw_off = device_batch(e, chunks, check=False)
+    if refused_wide:
+        assert (st == -4).all(), (what, st)
+        return
+    assert not st.any(), (what, [(n, int(s)) for (n, _, _), s in zip(cases, st) if s])
+    for (name, _, w), o in zip(cases, raw_off):
+        assert np.array_equal(out[o:o + w.size], w), (what, name)
+    assert np.array_equal(out, want_buffer([w for _, _, w in cases], raw_off, out.size)), what       # (the canaries)
+    outs, st = e.decompress_host(chunks, check=False)
+    assert not st.any(), (what, st)
+    for (name, _, w), o in zip(cases, outs):
+        assert np.array_equal(o, w), (what, name, "host")
+
+
+def test_every_frame_as_the_one_stream_of_a_chunk(eng, frame_chunks):
+    normal = [c for c in frame_chunks if c[2].size <= LDS_BLOCK_MAX]
+    wide = [c for c in frame_chunks if c[2].size > LDS_BLOCK_MAX]
+    assert len(wide) == 3 and min(c[2].size for c in normal) <= 100 and max(c[2].size for c in normal) >= 140000
+    check_frame_batch(eng, normal, "default")
+    check_frame_batch(eng, wide, "default, wide route")
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_every_frame_as_the_one_stream_of_a_chunk_every_form_of_the_read_path(form, frame_chunks, monkeypatch):
+    for k in FORM_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    e = hip.Engine(0)
+    try:
+        cases = [c for c in frame_chunks if c[2].size <= FORM_BLOCK_MAX]
+        assert len(cases) >= len(frame_chunks) - 10          # (left to the default engine: 139 084 .. 150 000 bytes, and the wide three)
+        check_frame_batch(e, cases, form)
+    finally:
+        e.close()
+
+
+def test_mix_chunks_written_on_the_gpu_are_the_emulators_and_decode(eng):
+    """codec::zstd over mix streams (every fifth one, mix18 among them), a chunk each: byte for byte what the kernel sources write on
+    the host lane emulator; the GPU reads them back (one batch, canaries), and so does libzstd where the box has one"""
+    import _emu as Em
+    import _oracle as O
+    mix = Z.mix_streams()
+    picked = [mix["mix%d" % k] for k in range(3, 120, 5)]
+    assert mix["mix18"] is picked[3]
+    raw = np.concatenate(picked)
+    sizes_ = [p.size for p in picked]
+    dest = [n + 32 for n in sizes_]
+    got = eng.compress_host(hip.cparams(1, clevel=9, compcode=hip.ZSTD), raw, sizes_, dest)
+    rc, cb, emu = Em.compress_batch(Em.cparams(1, clevel=9, compcode=hip.ZSTD), raw, sizes_, dest)
+    assert rc == 0 and got == emu
+    assert sum(1 for c in got if not c[2] & 0x02) >= 12                    # (most of them shrink: coded, not memcpyed)
+    st, out, raw_off = device_batch(eng, got, check=False)
+    assert not st.any(), st
+    assert np.array_equal(out, want_buffer(picked, raw_off, out.size))
+    outs, st = eng.decompress_host(got, check=False)
+    assert not st.any() and all(np.array_equal(o, p) for o, p in zip(outs, picked))
+    if O.zstd_available():
+        for c, p in zip(got, picked):
+            r, px = O.decompress(c)
+            assert r == p.size and np.array_equal(px, p)
+
