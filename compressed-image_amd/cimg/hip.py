@@ -25,6 +25,7 @@ K_ENCODE_WIDE_BLOSCLZ = 25                     # BloscLZ streams beyond 65 535 b
 K_UPDATE_PATCH_STRIDED = 26                    # strided window writes: the patch launch of cimg_update_windows_strided_* (csrc/update_kernel.h)
 K_DECODE_WINDOW_TYPED = 27                     # typed windows: convert, scale and place each element in the launch (csrc/window_kernel.h)
 K_UPDATE_PATCH_TYPED = 28                      # typed window writes: unscale, round and store each element in the patch launch (csrc/update_kernel.h)
+K_UPDATE_PATCH_MASKED = 29                     # masked and constant window writes: the patch launch of cimg_update_windows_masked_* (csrc/update_kernel.h)
 # names by timing id (cimg_kernel_name).  K_ENCODE times whichever of cimg_encode_streams / _blosclz the codec selects; K_DECODE
 # times the pair cimg_decode_lean + cimg_decode_blocks (the second only runs for blocks the first left): bench.py reports it under
 # the kernel that did the work
@@ -33,7 +34,7 @@ KERNELS = ("cimg_encode_streams", "cimg_layout_chunks", "cimg_emit_blocks", "cim
            "cimg_encode_wide", "cimg_decode_wide", "cimg_encode_wide_zstd", "cimg_zstd_replay_wide", "cimg_decode_window",
            "cimg_update_patch", "cimg_update_layout", "cimg_update_emit", "cimg_pack_chunks", "cimg_interleave", "cimg_decode_window_strided",
            "cimg_trunc_prec", "cimg_decode_window_grouped", "cimg_encode_wide_blosclz", "cimg_update_patch_strided",
-           "cimg_decode_window_typed", "cimg_update_patch_typed")
+           "cimg_decode_window_typed", "cimg_update_patch_typed", "cimg_update_patch_masked")
 # (K_DECODE_ZSTD times the zstd read path of a batch as a whole -- cimg_zstd_walk + cimg_zstd_lit + cimg_zstd_seq + cimg_zstd_replay, and
 # cimg_decode_zstd behind them for blocks the walk refused; for wide blocks, behind cimg_decode_wide: cimg_zstd_walk + cimg_zstd_replay_wide;
 # the ids from K_ZSTD_WALK on time those launches one by one)
@@ -59,6 +60,7 @@ EXPORTS = (
     "cimg_decompress_windows_grouped_device", "cimg_decompress_windows_grouped_host", "cimg_decompress_windows_typed_device",
     "cimg_update_windows_device", "cimg_update_windows_host", "cimg_engine_update_stats",
     "cimg_update_windows_strided_device", "cimg_update_windows_strided_host", "cimg_update_windows_typed_device",
+    "cimg_update_windows_masked_device", "cimg_update_windows_masked_host",
     "cimg_compress_batch_device_packed_begin", "cimg_compress_batch_device_packed_fetch", "cimg_pack_chunks_device",
     "cimg_interleave_device", "cimg_engine_wait_stream", "cimg_device_range_check",
     # include/blosc2.h
@@ -138,6 +140,29 @@ def typed_windows(specs):
         arr[i].col_pitch, arr[i].scale = 1, 1.0
         for k, v in (s.items() if isinstance(s, dict) else ((f, getattr(s, f)) for f, _ in TypedWindow._fields_)):
             setattr(arr[i], k, float(v) if k in ("scale", "offset") else int(v))
+    return arr
+
+
+WM_CONST, WM_MASK = 1, 2                       # CIMG_WM_* (include/cimg_hip.h)
+
+
+class MaskedWindow(C.Structure):
+    """cimg_window_masked (include/cimg_hip.h)"""
+    _fields_ = StridedWindow._fields_ + [("mask_off", C.c_int64), ("mask_pitch", C.c_int64), ("flags", C.c_int32), ("pad_", C.c_int32),
+                                         ("value", C.c_uint8 * 8)]
+
+
+def masked_windows(specs):
+    """dicts (or MaskedWindow) with the fields of cimg_window_masked -> a ctypes array (col_pitch defaults to 1; value: up to 8 bytes)"""
+    arr = (MaskedWindow * max(len(specs), 1))()
+    for i, s in enumerate(specs):
+        arr[i].col_pitch = 1
+        for k, v in (s.items() if isinstance(s, dict) else ((f, getattr(s, f)) for f, _ in MaskedWindow._fields_)):
+            if k == "value":
+                for j, b in enumerate(bytes(v)[:8]):
+                    arr[i].value[j] = b
+            else:
+                setattr(arr[i], k, int(v))
     return arr
 
 
@@ -235,6 +260,9 @@ def load():
     L.cimg_update_windows_strided_host.argtypes = L.cimg_update_windows_host.argtypes
     if hasattr(L, "cimg_update_windows_typed_device"):          # (a CIMG_LIB build from before it)
         L.cimg_update_windows_typed_device.argtypes = L.cimg_update_windows_device.argtypes
+    if hasattr(L, "cimg_update_windows_masked_device"):
+        L.cimg_update_windows_masked_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+        L.cimg_update_windows_masked_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, vp, _ALLOC_FN, vp, vp, vp, vp]
     L.cimg_compress_batch_device_packed_begin.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp]
     L.cimg_compress_batch_device_packed_fetch.argtypes = [vp, C.c_int32, vp, vp]
     L.cimg_pack_chunks_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
@@ -589,6 +617,52 @@ class Engine:
             self._check(rc)
             return ncb, status
         return rc, ncb, status
+
+    def update_windows_masked_device(self, p, d_comp, comp_off, nbytes, blocksize, destsize, specs, d_src, d_mask, d_new, new_off,
+                                     comp_size=None, check=True, new_cbytes=None, status=None):
+        """masked / constant windows (cimg_window_masked specs; d_src may be None when every window is constant, d_mask when none is
+        masked) written into device-resident chunks through cimg_update_windows_masked_device.  Returns as update_windows_device
+        does; new_cbytes / status: int32 arrays to hand to the call in place of fresh zeros."""
+        comp_off, nbytes, blocksize, destsize, new_off = _i64(comp_off), _i32(nbytes), _i32(blocksize), _i32(destsize), _i64(new_off)
+        cs = _i32(comp_size) if comp_size is not None else None
+        status = np.zeros(nbytes.size, np.int32) if status is None else status
+        ncb = np.zeros(nbytes.size, np.int32) if new_cbytes is None else new_cbytes
+        rc = load().cimg_update_windows_masked_device(self.handle, C.byref(p), nbytes.size, d_comp, _ptr(comp_off),
+                                                      _ptr(cs) if cs is not None else None, _ptr(nbytes), _ptr(blocksize), _ptr(destsize),
+                                                      len(specs), masked_windows(specs), d_src, d_mask, d_new, _ptr(new_off), _ptr(ncb),
+                                                      _ptr(status))
+        if check:
+            self._check(rc)
+            return ncb, status
+        return rc, ncb, status
+
+    def update_windows_masked_host(self, p, chunks, destsize, specs, src, mask, check=True, new_cbytes=None, status=None):
+        """update_windows_host over cimg_window_masked specs: cimg_update_windows_masked_host (src / mask: uint8 arrays or None)"""
+        sizes = [len(c) for c in chunks]
+        comp_off = _i64(np.concatenate([[0], np.cumsum(sizes[:-1], dtype=np.int64)]))
+        comp = np.frombuffer(b"".join(chunks) + bytes(16), np.uint8)
+        held, destsize = _i32(sizes), _i32(destsize)
+        n = len(chunks)
+        status = np.zeros(n, np.int32) if status is None else status
+        ncb = np.zeros(n, np.int32) if new_cbytes is None else new_cbytes
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep = []
+
+        def alloc(_user, nbytes):
+            b = C.create_string_buffer(max(int(nbytes), 1))
+            keep.append(b)
+            return C.addressof(b)
+        cb = _ALLOC_FN(alloc)
+        src = None if src is None else np.ascontiguousarray(src).view(np.uint8)
+        mask = None if mask is None else np.ascontiguousarray(mask).view(np.uint8)
+        rc = load().cimg_update_windows_masked_host(self.handle, C.byref(p), n, _ptr(comp), _ptr(comp_off), _ptr(held), _ptr(destsize),
+                                                    len(specs), masked_windows(specs), None if src is None else _ptr(src),
+                                                    None if mask is None else _ptr(mask), cb, None, ptrs, _ptr(ncb), _ptr(status))
+        new = [C.string_at(ptrs[i], int(ncb[i])) if ptrs[i] and ncb[i] > 0 else None for i in range(n)]
+        if check:
+            self._check(rc)
+            return new, status
+        return rc, new, status
 
     def update_windows_strided_host(self, p, chunks, destsize, specs, src, check=True):
         """update_windows_host over cimg_window_strided specs: cimg_update_windows_strided_host"""

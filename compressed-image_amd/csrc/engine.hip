@@ -360,6 +360,30 @@ extern "C" __global__ __launch_bounds__(256) void cimg_update_patch_typed(TypedP
     }
 }
 
+// Masked and constant window writes: staging and schedules as above; the overlays of MaskedPatchBlock write an element only where its
+// mask byte is not 0, and a constant item's value without reading a source.  No overlay reads unit bytes back to merge them.
+extern "C" __global__ __launch_bounds__(256) void cimg_update_patch_masked(MaskedPatchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    MaskedPatchBlock mb(a, lds, (int)blockIdx.x);
+    mb.pb.phase_a(wave);
+    __syncthreads();
+    mb.pb.phase_base(wave);
+    __syncthreads();
+    const int n = mb.pb.u.nitems;
+    if (n == 1) {
+        mb.overlay(0, wave * 64, 256);
+    } else if (mb.disjoint) {
+        for (int k = wave; k < n; k += 4) mb.overlay(k, 0, 64);
+    } else {
+        for (int k = 0; k < n; k++) {
+            if (k) __syncthreads();                                  // (a later window wins where two overlap)
+            mb.overlay(k, wave * 64, 256);
+        }
+    }
+}
+
 // Splice: one wave lays out each spliced chunk (old streams of untouched blocks, new streams of re-encoded ones); then one workgroup
 // per block copies the streams into place.
 extern "C" __global__ __launch_bounds__(64) void cimg_update_layout(SpliceArgs a)
@@ -481,7 +505,7 @@ struct cimg_engine {
     int lean_lds_pad = getenv("CIMG_LEAN_LDS_PAD") ? atoi(getenv("CIMG_LEAN_LDS_PAD")) : 0;   // diagnostic: fewer resident lean decode workgroups
     int dbg_count[2] = {0, 0};          // workgroups stamped by the last encode / decode launch
     PinBuf h_descs, h_descs_dec, h_out, h_dec;      // compress and decompress batches may be in flight together: nothing pinned is shared
-    int max_dyn_lds[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16) / typed window decode (17) / typed window-write patch (18)
+    int max_dyn_lds[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // largest dynamic LDS already enabled for encode (lz4) / decode / lean decode / encode (blosclz) / encode (zstd) / decode (zstd), one and two waves per block, ... / window decode (12) / window-write patch (13) / strided window decode (14) / grouped window decode (15) / strided window-write patch (16) / typed window decode (17) / typed window-write patch (18) / masked window-write patch (19)
     bool timing = false;              // events around the kernels of the current batch call
     int timing_period = 0;            // 0 = off, n = every n-th batch call is timed
     int64_t batch_no[2] = {0, 0};     // compress / decompress batch calls since timing was switched on
@@ -520,7 +544,7 @@ struct cimg_engine {
     PinBuf h_win_items, h_win_descs, h_win_st;
     WindowStats win_stats;
     // window writes (update_plan.h): patched blocks, the launches' tables, the host call's staged sources and new chunks
-    DevBuf upd_patch, upd_units, upd_stage, upd_items, upd_descs, upd_chunks, upd_blocks, upd_layout, upd_src, upd_new;
+    DevBuf upd_patch, upd_units, upd_stage, upd_items, upd_descs, upd_chunks, upd_blocks, upd_layout, upd_src, upd_new, upd_mask;
     PinBuf h_upd_st, h_upd_hdr;
     // the pack launch's piece table (pack_kernel.h), and the event cimg_engine_wait_stream records on the caller's stream
     DevBuf pack_tab;
@@ -689,6 +713,7 @@ const char* cimg_kernel_name(int k)
     case CIMG_K_UPDATE_PATCH: return "cimg_update_patch";
     case CIMG_K_UPDATE_PATCH_STRIDED: return "cimg_update_patch_strided";
     case CIMG_K_UPDATE_PATCH_TYPED: return "cimg_update_patch_typed";
+    case CIMG_K_UPDATE_PATCH_MASKED: return "cimg_update_patch_masked";
     case CIMG_K_UPDATE_LAYOUT: return "cimg_update_layout";
     case CIMG_K_UPDATE_EMIT: return "cimg_update_emit";
     case CIMG_K_PACK: return "cimg_pack_chunks";
@@ -767,7 +792,7 @@ void cimg_engine_destroy(cimg_engine* e)
     for (DevBuf* b : {&e->descs_enc, &e->descs_dec, &e->recs, &e->layout, &e->scratch, &e->stage_raw, &e->stage_comp, &e->stage_il, &e->dbg, &e->queue, &e->done, &e->sync, &e->next_item, &e->qheads, &e->placed, &e->zstd_seq, &e->zstd_tables, &e->zplan,
                     &e->wide_planes, &e->wide_queue, &e->wide_slots, &e->descs_wide, &e->wide_zseq, &e->wide_zslots,
                     &e->upd_patch, &e->upd_units, &e->upd_stage, &e->upd_items, &e->upd_descs, &e->upd_chunks, &e->upd_blocks, &e->upd_layout,
-                    &e->upd_src, &e->upd_new, &e->pack_tab, &e->trunc_tab, &e->trunc_src})
+                    &e->upd_src, &e->upd_new, &e->upd_mask, &e->pack_tab, &e->trunc_tab, &e->trunc_src})
         if (b->p) (void)hipFree(b->p);
     for (PinBuf* b : {&e->h_descs, &e->h_descs_dec, &e->h_out, &e->h_dec, &e->h_descs_wide, &e->h_wst, &e->h_upd_st, &e->h_upd_hdr, &e->h_pack_tab, &e->h_trunc_tab})
         if (b->p) (void)hipHostFree(b->p);
@@ -2521,6 +2546,7 @@ struct EngineUpdateEnv : EngineChunks {
     uint8_t* d_new;
     const uint8_t* h_comp;             // host call: the headers are read here, at h_off
     const int64_t* h_off;
+    const uint8_t* d_mask = nullptr;   // masked calls: the windows' mask bytes
 
     int upload(DevBuf& b, const void* src, size_t bytes, const char* what)
     {
@@ -2567,8 +2593,16 @@ struct EngineUpdateEnv : EngineChunks {
         return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
     }
 
-    // cimg_update_patch over PatchUnit / WindowItem, cimg_update_patch_strided over StridedPatchUnit / StridedWindowItem, or
-    // cimg_update_patch_typed over StridedPatchUnit / TypedWindowItem
+    int patch_masked(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<StridedPatchUnit>& units,
+                     const std::vector<WindowItem>& stage, const std::vector<MaskedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                     int32_t* status)
+    {
+        return patch_launch(descs, lds_bytes, units, stage, items, to_whole, patch_bytes, status);
+    }
+
+    // cimg_update_patch over PatchUnit / WindowItem, cimg_update_patch_strided over StridedPatchUnit / StridedWindowItem,
+    // cimg_update_patch_typed over StridedPatchUnit / TypedWindowItem, or cimg_update_patch_masked over StridedPatchUnit /
+    // MaskedWindowItem
     template <class Unit, class Item>
     int patch_launch(const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<Unit>& units, const std::vector<WindowItem>& stage,
                      const std::vector<Item>& items, int to_whole, int64_t patch_bytes, int32_t* status)
@@ -2591,7 +2625,11 @@ struct EngineUpdateEnv : EngineChunks {
         pa.src = d_src;
         pa.dst = (uint8_t*)(to_whole ? e->win_whole.p : e->upd_patch.p);
         pa.nunits = (int32_t)units.size();
-        if constexpr (std::is_same_v<Item, TypedWindowItem>) {
+        if constexpr (std::is_same_v<Item, MaskedWindowItem>) {
+            const MaskedPatchArgs ma{pa, (const StridedPatchUnit*)e->upd_units.p, (const MaskedWindowItem*)e->upd_items.p, d_mask};
+            if ((rc = e->allow_lds(cimg_update_patch_masked, 19, lds_bytes))) return rc;
+            rc = e->launch(CIMG_K_UPDATE_PATCH_MASKED, cimg_update_patch_masked, ma, (int)units.size(), 256, lds_bytes);
+        } else if constexpr (std::is_same_v<Item, TypedWindowItem>) {
             const TypedPatchArgs ta{pa, (const StridedPatchUnit*)e->upd_units.p, (const TypedWindowItem*)e->upd_items.p};
             if ((rc = e->allow_lds(cimg_update_patch_typed, 18, lds_bytes))) return rc;
             rc = e->launch(CIMG_K_UPDATE_PATCH_TYPED, cimg_update_patch_typed, ta, (int)units.size(), 256, lds_bytes);
@@ -2667,18 +2705,20 @@ template <class Spec>
 int update_device_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
                        const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
                        int32_t nwindows, const Spec* w, const void* d_src, void* d_new, const int64_t* new_off,
-                       int32_t* new_cbytes, int32_t* status)
+                       int32_t* new_cbytes, int32_t* status, const void* d_mask = nullptr)
 {
+    constexpr bool kMasked = std::is_same_v<Spec, MaskedWindowSpec>;     // (a masked call has checked its source and mask pointers already)
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
     int rc = open_update_call(nchunks, nwindows, status, new_cbytes, nullptr);
     if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
-    if (!p || !w || !comp_off || !nbytes || !blocksize || !destsize || !status || !new_cbytes || !new_off || !d_comp || !d_src || !d_new)
+    if (!p || !w || !comp_off || !nbytes || !blocksize || !destsize || !status || !new_cbytes || !new_off || !d_comp || (!d_src && !kMasked) || !d_new)
         return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
     e->dflight_open = false;
     e->cflight_chunks = -1;
-    EngineUpdateEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, p, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr};
+    EngineUpdateEnv env{{e, (const uint8_t*)d_comp, comp_off, comp_size, nbytes, blocksize}, p, (const uint8_t*)d_src, (uint8_t*)d_new, nullptr, nullptr,
+                        (const uint8_t*)d_mask};
     UpdateStats st;
     rc = run_update(env, to_host(p), nchunks, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, w, new_off, new_cbytes, status, &st);
     e->upd_stats = st;
@@ -2688,13 +2728,15 @@ int update_device_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, c
 template <class Spec>
 int update_host_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                      const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const Spec* w,
-                     const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
+                     const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status,
+                     const void* h_mask = nullptr)
 {
+    constexpr bool kMasked = std::is_same_v<Spec, MaskedWindowSpec>;     // (a masked call has checked its source and mask pointers already)
     std::lock_guard<std::recursive_mutex> lock_(e->mu);
     e->upd_stats = UpdateStats{};
     int rc = open_update_call(nchunks, nwindows, status, new_cbytes, new_chunks);
     if (rc) return rc > 0 ? 0 : open_fail(e, nchunks, nwindows);
-    if (!p || !w || !comp_off || !destsize || !status || !new_cbytes || !new_chunks || !h_comp || !h_src || !alloc)
+    if (!p || !w || !comp_off || !destsize || !status || !new_cbytes || !new_chunks || !h_comp || (!h_src && !kMasked) || !alloc)
         return e->fail(ERR_INVALID_PARAM, "null argument");
     if (nchunks == 0) return open_fail(e, nchunks, nwindows);
     (void)hipSetDevice(e->device);
@@ -2710,6 +2752,7 @@ int update_host_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, con
     if ((rc = e->reserve(e->stage_comp, (size_t)hp.comp_total + 64))) return rc;
     if ((rc = e->reserve(e->upd_src, (size_t)hp.rows_total + 64))) return rc;
     if ((rc = e->reserve(e->upd_new, (size_t)hp.new_total + 64))) return rc;
+    if (kMasked && (rc = e->reserve(e->upd_mask, (size_t)hp.mask_total + 64))) return rc;
     uint8_t* sc = (uint8_t*)e->stage_comp.p;
     uint8_t* ss = (uint8_t*)e->upd_src.p;
     const uint8_t* hs = (const uint8_t*)h_src;
@@ -2722,7 +2765,17 @@ int update_host_call(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, con
             rc = copy_rows(e, ss + d.out_off, d.out_pitch, hs + w[k].out_off, w[k].out_pitch, d.out_pitch, w[k].height, hipMemcpyHostToDevice, "window H2D");
             if (rc) { (void)cimg_engine_synchronize(e); return rc; }
         }
-        EngineUpdateEnv env{{e, sc, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data()}, p, ss, (uint8_t*)e->upd_new.p, hc, comp_off};
+        if constexpr (kMasked) {                           // the mask rows of the masked windows, packed likewise
+            for (int k = 0; k < nwindows; k++) {
+                const Spec& d = dw[(size_t)k];
+                if (!hp.mbytes[(size_t)k]) continue;
+                rc = copy_rows(e, (uint8_t*)e->upd_mask.p + d.mask_off, d.mask_pitch, (const uint8_t*)h_mask + w[k].mask_off, w[k].mask_pitch, d.mask_pitch,
+                               w[k].height, hipMemcpyHostToDevice, "mask H2D");
+                if (rc) { (void)cimg_engine_synchronize(e); return rc; }
+            }
+        }
+        EngineUpdateEnv env{{e, sc, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data()}, p, ss, (uint8_t*)e->upd_new.p, hc, comp_off,
+                            kMasked ? (const uint8_t*)e->upd_mask.p : nullptr};
         UpdateStats st;
         rc = run_update(env, to_host(p), nchunks, hp.d_comp_off.data(), hp.held.data(), hp.nbytes.data(), hp.blocksize.data(), destsize, nwindows,
                         dw.data(), hp.new_off.data(), new_cbytes, status, &st);
@@ -2804,6 +2857,46 @@ int cimg_update_windows_typed_device(cimg_engine* e, const cimg_cparams* p, int3
     }
     return update_device_call(e, p, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, tw, d_src, d_new, new_off,
                               new_cbytes, status);
+}
+
+// The masked checks run before the call touches status or new_cbytes (update_plan.h: check_masked_update); everything else is the
+// strided calls'.
+static_assert(sizeof(cimg_window_masked) == sizeof(MaskedWindowSpec) && offsetof(cimg_window_masked, col_pitch) == offsetof(MaskedWindowSpec, col_pitch) &&
+              offsetof(cimg_window_masked, out_pitch) == offsetof(MaskedWindowSpec, out_pitch) &&
+              offsetof(cimg_window_masked, mask_pitch) == offsetof(MaskedWindowSpec, mask_pitch) &&
+              offsetof(cimg_window_masked, flags) == offsetof(MaskedWindowSpec, flags) &&
+              offsetof(cimg_window_masked, value) == offsetof(MaskedWindowSpec, value), "cimg_window_masked != MaskedWindowSpec");
+static_assert(CIMG_WM_CONST == WM_CONST && CIMG_WM_MASK == WM_MASK, "CIMG_WM_* != WM_*");
+
+static int masked_refused(cimg_engine* e)
+{
+    std::lock_guard<std::recursive_mutex> lock_(e->mu);
+    e->upd_stats = UpdateStats{};
+    return e->fail(ERR_INVALID_PARAM, "invalid masked update: only CIMG_WM_CONST and CIMG_WM_MASK are flags; a constant needs typesize <= 8; a masked "
+                                      "window needs mask_off >= 0, mask_pitch >= 0 (>= width when height > 1) and a mask pointer; a window "
+                                      "without CIMG_WM_CONST needs a source pointer");
+}
+
+int cimg_update_windows_masked_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp, const int64_t* comp_off,
+                                      const int32_t* comp_size, const int32_t* nbytes, const int32_t* blocksize, const int32_t* destsize,
+                                      int32_t nwindows, const cimg_window_masked* w, const void* d_src, const void* d_mask, void* d_new,
+                                      const int64_t* new_off, int32_t* new_cbytes, int32_t* status)
+{
+    const MaskedWindowSpec* mw = reinterpret_cast<const MaskedWindowSpec*>(w);
+    if (nwindows > 0 && p && mw && check_masked_update(p->typesize, nwindows, mw, d_src, d_mask) < 0) return masked_refused(e);
+    return update_device_call(e, p, nchunks, d_comp, comp_off, comp_size, nbytes, blocksize, destsize, nwindows, mw, d_src, d_new, new_off,
+                              new_cbytes, status, d_mask);
+}
+
+int cimg_update_windows_masked_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                    const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_masked* w,
+                                    const void* h_src, const void* h_mask, cimg_alloc_fn alloc, void* user, void** new_chunks,
+                                    int32_t* new_cbytes, int32_t* status)
+{
+    const MaskedWindowSpec* mw = reinterpret_cast<const MaskedWindowSpec*>(w);
+    if (nwindows > 0 && p && mw && check_masked_update(p->typesize, nwindows, mw, h_src, h_mask) < 0) return masked_refused(e);
+    return update_host_call(e, p, nchunks, h_comp, comp_off, comp_size, destsize, nwindows, mw, h_src, alloc, user, new_chunks, new_cbytes,
+                            status, h_mask);
 }
 
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole, int64_t* bytes_uploaded)

@@ -11,6 +11,9 @@
 //   cimg_update_patch_typed
 //                       the same for typed windows (TypedPatchBlock, below): every written element is loaded as float32 / float16,
 //                       unscaled, rounded and stored as the plane's type on its way into the unit.
+//   cimg_update_patch_masked
+//                       the same for masked and constant windows (MaskedPatchBlock, below): an element is written only where the
+//                       window's mask byte is not 0, and a constant window writes one value and reads no source.
 //   cimg_update_layout  one wave per spliced chunk.  Lane j takes block j: a touched block's size comes from the stream records the
 //                       encode launch left for it; an untouched block's streams are harvested from the old chunk (a negative csize
 //                       word is a run, csize == neblock raw, anything else a coded stream whose payload stays where it is).  A wave
@@ -337,6 +340,168 @@ struct TypedPatchBlock {
                             if (ts == 1) *d = (uint8_t)v;
                             else if (ts == 2) *reinterpret_cast<uint16_t*>(d) = (uint16_t)v;
                             else *reinterpret_cast<uint32_t*>(d) = v;
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// ---- masked patch: cimg_update_patch_masked ---------------------------------------------------------------------------------------
+// The patch kernel of the masked / constant write calls.  Units, staging (PatchBlock::phase_a and phase_base) and the two schedules
+// are those of the strided patch kernel; an item carries flags (WM_CONST: the written bytes are `value`, no source is read; WM_MASK:
+// element c of window row r is written only if mask[mask_off + r * mask_pitch + c] != 0).  Three overlay paths:
+//   dense_rows   items with cpitch == typesize that are unmasked, or masked with typesize 1 or 2 and elements that sit whole and
+//                aligned in the unit: one lane a destination dword.  Unmasked: a whole dword is one store (of source bytes, or of the
+//                value replicated at the dword's phase -- the fill reads no source at all), the ragged ends go byte by byte.  Masked:
+//                the lane looks at the mask bytes of the dword's 4 or 2 elements; all set: one dword store, else one store per
+//                written element.
+//   elements     everything else (strided items, typesize 3 and other odd sizes, typesize 4 and 8 under a mask, elements over the
+//                unit's edge): the strided overlay's walk c_lo .. c_hi, one lane an element, the element's mask byte in front of
+//                its stores; a straddling element is written byte by byte by the units that hold its bytes, each consulting the
+//                same mask byte.
+// NO READ-MODIFY-WRITE: every store writes new bytes only -- a whole dword of them, or single elements / bytes.  Old and new bytes
+// are never merged into a word that is then stored: under the disjoint schedule four waves write one unit with no barrier, and
+// lanes of one wave write neighbouring bytes of one dword; byte-level disjointness protects byte stores, not a dword RMW.  (The
+// host emulator runs waves one after the other and cannot show such a race: this is kept by construction.)
+enum : int { WM_CONST = 1, WM_MASK = 2 };
+
+struct MaskedWindowItem : StridedWindowItem {
+    int64_t mask_off, mask_pitch;     // WM_MASK: the mask byte of element c of window row r is mask[mask_off + r * mask_pitch + c]
+    uint64_t value;                   // WM_CONST: the element's bytes, byte i at bits 8 i
+    int32_t flags;                    // WM_*
+    int32_t pad2_;
+};
+
+struct MaskedPatchArgs {
+    PatchArgs p;                      // (p.units and p.items unused; p.src may be null when every item is constant)
+    const StridedPatchUnit* units;
+    const MaskedWindowItem* items;    // overlays, in call order inside a unit
+    const uint8_t* mask;              // (may be null when no item is masked)
+};
+
+struct MaskedPatchBlock {
+    const MaskedPatchArgs& a;
+    PatchBlock pb;
+    int disjoint;
+
+    CIMG_DEV MaskedPatchBlock(const MaskedPatchArgs& a_, uint8_t* lds, int k)
+        : a(a_), pb(a_.p, lds, k, PatchBlock::uniform_unit(&a_.units[k].u)), disjoint(uni(a_.units[k].disjoint)) {}
+
+    CIMG_DEV static uint32_t value_byte(uint64_t v, int i) { return (uint32_t)(v >> (8 * i)) & 0xFFu; }
+
+    // rows r0 .. r1 of a dense item in dword units aligned on the destination.  masked: ts is 1 or 2 and every element of the rows
+    // lies whole and ts-aligned in the unit (the caller checked)
+    CIMG_DEV void dense_rows(const WindowItem& it, int ts, bool constant, bool masked, uint64_t value, int64_t mask_off, int64_t mask_pitch,
+                             int tid0, int stride)
+    {
+        const int64_t len = pb.u.len;
+        uint8_t* const unit = a.p.dst + pb.u.dst_off;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rs = it.row0 + (int64_t)r * it.rpitch, re = rs + it.wbytes;
+            const int64_t s = rs > it.p0 ? rs : it.p0;
+            const int64_t e = re < it.p0 + len ? re : it.p0 + len;
+            if (s >= e) continue;
+            const int64_t rb = s - rs;                                         // row byte of the first byte written here
+            const uint8_t* src = constant ? nullptr : a.p.src + it.out_off + (int64_t)r * it.out_pitch + rb;
+            const uint8_t* mrow = masked ? a.mask + mask_off + (int64_t)r * mask_pitch : nullptr;
+            uint8_t* dst = unit + (s - it.p0);
+            const int64_t n = e - s;
+            const int64_t mis = (int64_t)((uintptr_t)dst & 3);
+            const int64_t units = (mis + n + 3) >> 2;
+            for (int64_t u0 = tid0; u0 < units; u0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t q0 = 4 * (u0 + l) - mis;
+                    if (u0 + l < units) {
+                        const bool full = q0 >= 0 && q0 + 4 <= n;
+                        // the four new bytes (those inside the row)
+                        uint32_t b[4] = {0, 0, 0, 0};
+                        if (constant) {
+                            int ph = (int)((rb + (q0 < 0 ? 0 : q0)) % ts);             // element byte of the first byte inside
+                            for (int i = 0; i < 4; i++) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) { b[i] = value_byte(value, ph); ph = ph + 1 == ts ? 0 : ph + 1; }
+                            }
+                        } else {
+                            for (int i = 0; i < 4; i++) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) b[i] = src[q];
+                            }
+                        }
+                        const uint32_t v = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+                        if (!masked) {
+                            if (full) *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                            else
+                                for (int i = 0; i < 4; i++) {
+                                    const int64_t q = q0 + i;
+                                    if (q >= 0 && q < n) dst[q] = (uint8_t)b[i];
+                                }
+                        } else {
+                            // the mask bytes of the dword's elements (element of row byte x: x / ts)
+                            bool w[4] = {false, false, false, false};
+                            bool all = full;
+                            for (int i = 0; i < 4; i += ts) {
+                                const int64_t q = q0 + i;
+                                if (q >= 0 && q < n) w[i] = mrow[(rb + q) / ts] != 0;
+                                all = all && w[i];
+                            }
+                            if (all) *reinterpret_cast<uint32_t*>(dst + q0) = v;
+                            else if (ts == 1) { for (int i = 0; i < 4; i++) if (w[i]) dst[q0 + i] = (uint8_t)b[i]; }
+                            else { for (int i = 0; i < 4; i += 2) if (w[i]) *reinterpret_cast<uint16_t*>(dst + q0 + i) = (uint16_t)(b[i] | (b[i + 1] << 8)); }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    // overlay k of the unit by threads tid0 + lane, + stride, ...
+    CIMG_DEV void overlay(int k, int tid0, int stride)
+    {
+        const MaskedWindowItem* ip = a.items + pb.u.item0 + k;
+        const WindowItem it = WindowBlock::uniform_item(ip);
+        const int64_t cpitch = uni64(ip->cpitch), mask_off = uni64(ip->mask_off), mask_pitch = uni64(ip->mask_pitch);
+        const uint64_t value = (uint64_t)uni64((int64_t)ip->value);
+        const int ts = uni(ip->ts), flags = uni(ip->flags);
+        const bool constant = (flags & WM_CONST) != 0, masked = (flags & WM_MASK) != 0;
+        const int64_t len = pb.u.len;
+        uint8_t* const unit = a.p.dst + pb.u.dst_off;
+        if (cpitch == ts && (!masked || ts == 1 || (ts == 2 && ((it.p0 | len | (int64_t)(uintptr_t)unit) & 1) == 0))) {
+            dense_rows(it, ts, constant, masked, value, mask_off, mask_pitch, tid0, stride);
+            return;
+        }
+        const int64_t width = it.wbytes / ts;
+        const bool dwords = ts == 4 || ts == 8;
+        for (int r = it.r0; r < it.r1; r++) {
+            const int64_t rel = it.row0 + (int64_t)r * it.rpitch - it.p0;      // the row's first byte, seen from the unit
+            // elements c_lo .. c_hi of the row have a byte in [0, len)
+            const int64_t lo = -rel - (ts - 1), hi = len - 1 - rel;
+            if (hi < 0) continue;
+            const int64_t c_lo = lo <= 0 ? 0 : (lo + cpitch - 1) / cpitch;
+            int64_t c_hi = hi / cpitch;
+            if (c_hi > width - 1) c_hi = width - 1;
+            if (c_lo > c_hi) continue;
+            const int64_t base = rel + c_lo * cpitch;                          // unit offset of element c_lo (>= -(ts - 1))
+            const uint8_t* src = constant ? nullptr : a.p.src + it.out_off + (int64_t)r * it.out_pitch + c_lo * ts;
+            const uint8_t* m = masked ? a.mask + mask_off + (int64_t)r * mask_pitch + c_lo : nullptr;
+            const int64_t ne = c_hi + 1 - c_lo;
+            for (int64_t e0 = tid0; e0 < ne; e0 += stride) {
+                FOR_LANES(l) {
+                    const int64_t e = e0 + l;
+                    if (e < ne && (!masked || m[e] != 0)) {
+                        const int64_t at = base + e * cpitch;                  // the element's bytes: [at, at + ts) of the unit
+                        const uint8_t* s = constant ? nullptr : src + e * ts;
+                        uint8_t* d = unit + at;
+                        if (dwords && at >= 0 && at + ts <= len && ((uintptr_t)d & 3) == 0) {
+                            for (int i = 0; i < ts; i += 4) {
+                                const uint32_t v = constant ? (uint32_t)(value >> (8 * i))
+                                                            : (uint32_t)s[i] | ((uint32_t)s[i + 1] << 8) | ((uint32_t)s[i + 2] << 16) | ((uint32_t)s[i + 3] << 24);
+                                *reinterpret_cast<uint32_t*>(d + i) = v;
+                            }
+                        } else {
+                            for (int i = 0; i < ts; i++)
+                                if (at + i >= 0 && at + i < len) d[i] = constant ? (uint8_t)value_byte(value, i) : s[i];
                         }
                     }
                 }

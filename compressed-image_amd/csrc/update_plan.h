@@ -1,7 +1,8 @@
 // update_plan.h -- window writes: validation, routing and the order in which an update call runs.  Pure C++, shared by the engine
 // (engine.hip) and the emulator tests (tests/emu/window_write_emu.cpp, tests/emu/mock_window_write.cpp), like window_plan.h.
 //
-// Windows are cimg_window / WindowSpec -- or, for the strided calls, cimg_window_strided / StridedWindowSpec: run_update and
+// Windows are cimg_window / WindowSpec -- or, for the strided calls, cimg_window_strided / StridedWindowSpec, for the typed call
+// cimg_window_typed / TypedWindowSpec, for the masked and constant calls cimg_window_masked / MaskedWindowSpec: run_update and
 // plan_update_host are templates over the window type, as run_windows and plan_windows_host are -- with out_off / out_pitch locating the SOURCE rows.  Every touched chunk's new bytes are what a
 // from-scratch compress of its decoded pixels with the windows written in gives.  Two routes:
 //   splice  regular lz4 / lz4hc / blosclz chunks whose blocks the window kernel can stage and the batch encoder can take: the touched
@@ -71,6 +72,10 @@ inline bool items_cover(const std::vector<WindowItem>& items, size_t first, size
 //   int patch_typed(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
 //                                                          -- the same for a call over TypedWindowSpec: cimg_update_patch_typed over
 //                                                             StridedPatchUnit and TypedWindowItem (only such calls need it)
+//   int patch_masked(descs, lds_bytes, units, stage_items, items, to_whole, patch_bytes, status)
+//                                                          -- the same for a call over MaskedWindowSpec: cimg_update_patch_masked over
+//                                                             StridedPatchUnit and MaskedWindowItem, the env's mask beside its source
+//                                                             (only such calls need it)
 //   int trunc(typesize, mask64, off, len)    [optional]    -- trunc-prec in place over pieces of the patch buffer, in front of encode().
 //                                                             An env without it cannot truncate: parameters that name the filter are
 //                                                             ERR_INVALID_PARAM there, as they were before the filter was built.
@@ -181,6 +186,90 @@ inline int check_typed_update(int nchunks, const int32_t* nbytes, const int32_t*
     }
     const std::vector<int32_t> tsv((size_t)nchunks, typesize > 255 ? 1 : typesize);
     return check_typed_windows(nchunks, nbytes, blocksize, tsv.data(), nwindows, w);
+}
+
+// ---- masked and constant windows (MaskedWindowSpec: cimg_update_windows_masked_*) ---------------------------------------------------
+// A strided window with flags: WM_CONST (every written element is `value`; out_off / out_pitch are ignored and no source is read)
+// and WM_MASK (element c of row r is written only where mask[mask_off + r * mask_pitch + c] != 0).  run_update serves the call as
+// it serves the strided one, the items through list_strided_items.  Coverage: only dense UNMASKED items prove that a unit needs no
+// staging, constant or not; a masked item never does, whatever its mask holds -- the mask is never read on the host, so a unit
+// whose mask bytes are all 0 is still staged, re-encoded and comes out byte for byte the old block.  Disjointness: items_disjoint
+// looks at the plane side only and stays sound, since a mask only removes writes.
+// = cimg_window_masked (include/cimg_hip.h)
+struct MaskedWindowSpec {
+    int32_t chunk_first, chunk_count;
+    int64_t origin;
+    int64_t row_pitch;
+    int64_t col_pitch;
+    int32_t width, height;
+    int64_t out_off, out_pitch;
+    int64_t mask_off, mask_pitch;
+    int32_t flags;
+    int32_t pad_;
+    uint8_t value[8];
+};
+using MaskedWindowPlan = WindowPlanT<MaskedWindowItem>;
+template <> struct PlanOf<MaskedWindowSpec> { using type = MaskedWindowPlan; };
+
+// what a masked call checks on top of the strided call's checks, BEFORE it touches status or new_cbytes
+inline int check_masked_update(int typesize, int nwindows, const MaskedWindowSpec* w, const void* src, const void* mask)
+{
+    for (int k = 0; k < nwindows; k++) {
+        const MaskedWindowSpec& s = w[k];
+        if (s.flags & ~(WM_CONST | WM_MASK)) return ERR_INVALID_PARAM;
+        if ((s.flags & WM_CONST) && typesize > 8) return ERR_INVALID_PARAM;
+        if (!(s.flags & WM_CONST) && !src) return ERR_INVALID_PARAM;
+        if (s.flags & WM_MASK) {
+            if (!mask || s.mask_off < 0 || s.mask_pitch < 0) return ERR_INVALID_PARAM;
+            if (s.height > 1 && s.mask_pitch < s.width) return ERR_INVALID_PARAM;
+            // (the last mask byte's offset fits an int64)
+            if (s.height > 1 && s.width >= 0 && s.mask_pitch > (INT64_MAX - s.mask_off - s.width) / (s.height - 1)) return ERR_INVALID_PARAM;
+        }
+    }
+    return 0;
+}
+
+inline int plan_windows(int nchunks, const int32_t* nbytes, const int32_t* blocksize, const int32_t* typesize, int nwindows,
+                        const MaskedWindowSpec* w, const uint8_t* whole_hint, MaskedWindowPlan* plan)
+{
+    if (nchunks < 0 || nwindows < 0 || (nwindows > 0 && !w)) return ERR_INVALID_PARAM;
+    plan_descs(nchunks, nbytes, blocksize, whole_hint, plan);
+    for (int k = 0; k < nwindows; k++) {
+        int ts = 0;
+        MaskedWindowSpec s = w[k];
+        if (s.flags & WM_CONST) s.out_off = 0;                       // (a constant window's source fields are ignored, not checked)
+        const int rc = check_strided_window(nchunks, nbytes, blocksize, typesize, s, &ts);
+        if (rc < 0) return rc;
+        if (rc == 0 && !(s.flags & WM_CONST) && s.out_pitch < (int64_t)s.width * ts) return ERR_INVALID_PARAM;
+    }
+    list_strided_items(nbytes, typesize, nwindows, w, plan, [](MaskedWindowItem& t, const MaskedWindowSpec& s) {
+        t.flags = s.flags; t.mask_off = s.mask_off; t.mask_pitch = s.mask_pitch;
+        t.value = 0;
+        for (int i = 0; i < 8; i++) t.value |= (uint64_t)s.value[i] << (8 * i);
+    });
+    plan_totals(plan);
+    return 0;
+}
+
+inline bool items_cover(const std::vector<MaskedWindowItem>& items, size_t first, size_t count, int64_t len)
+{
+    const auto proves = [](const MaskedWindowItem& t) { return t.cpitch == t.ts && !(t.flags & WM_MASK); };
+    int64_t written = 0;
+    for (size_t k = first; k < first + count; k++) if (proves(items[k])) written += (int64_t)(items[k].r1 - items[k].r0) * items[k].wbytes;
+    if (written < len) return false;
+    std::vector<WindowItem> dense;
+    for (size_t k = first; k < first + count; k++) if (proves(items[k])) dense.push_back(items[k]);
+    return items_cover(dense, 0, dense.size(), len);
+}
+
+template <class Env>
+int patch_units(Env& env, const std::vector<ChunkDesc>& descs, int lds_bytes, const std::vector<PatchUnit>& units, const std::vector<uint8_t>& disjoint,
+                const std::vector<WindowItem>& stage, const std::vector<MaskedWindowItem>& items, int to_whole, int64_t patch_bytes,
+                int32_t* status)
+{
+    std::vector<StridedPatchUnit> su(units.size());
+    for (size_t k = 0; k < units.size(); k++) su[k] = StridedPatchUnit{units[k], disjoint[k], 0};
+    return env.patch_masked(descs, lds_bytes, su, stage, items, to_whole, patch_bytes, status);
 }
 
 template <class Env, class Spec>
@@ -452,7 +541,38 @@ struct UpdateHostPlan : HostCallPlan {
     std::vector<int32_t> held;          // the bytes the caller holds of each chunk: comp_size, or what the header says
     std::vector<int64_t> new_off;       // the touched chunks' new forms, in 64-byte slots of destsize each
     int64_t new_total = 0, new_used = 0, bytes_uploaded = 0;
+    // masked calls: the mask rows of the masked windows packed one after the other (mask_pitch = width), each at a multiple of 64
+    std::vector<int64_t> mbytes;
+    int64_t mask_total = 0, mask_used = 0;
 };
+
+// the windows of a masked call as the device sees them: the rows of the windows that have a source packed as pack_rows packs them,
+// the mask rows of the masked ones packed likewise in a buffer of their own; a constant window sends no rows, an unmasked one no mask
+inline void pack_rows(int nwindows, const MaskedWindowSpec* w, const int32_t* typesize, UpdateHostPlan* hp, std::vector<MaskedWindowSpec>* dw)
+{
+    dw->assign(w, w + nwindows);
+    hp->wbytes.assign((size_t)nwindows, 0);
+    hp->mbytes.assign((size_t)nwindows, 0);
+    for (int k = 0; k < nwindows; k++) {
+        if (w[k].width <= 0 || w[k].height <= 0) continue;
+        MaskedWindowSpec& d = (*dw)[(size_t)k];
+        if (!(w[k].flags & WM_CONST)) {
+            const int64_t row = (int64_t)w[k].width * typesize[w[k].chunk_first];
+            d.out_off = hp->rows_total;
+            d.out_pitch = row;
+            hp->wbytes[(size_t)k] = row * w[k].height;
+            hp->rows_used = hp->rows_total + hp->wbytes[(size_t)k];
+            hp->rows_total += (hp->wbytes[(size_t)k] + 255) & ~255ll;
+        }
+        if (w[k].flags & WM_MASK) {
+            d.mask_off = hp->mask_total;
+            d.mask_pitch = w[k].width;
+            hp->mbytes[(size_t)k] = (int64_t)w[k].width * w[k].height;
+            hp->mask_used = hp->mask_total + hp->mbytes[(size_t)k];
+            hp->mask_total += (hp->mbytes[(size_t)k] + 63) & ~63ll;
+        }
+    }
+}
 
 // cimg_update_windows_host: only the touched chunks go up, and a header that claims more than the buffer holds is the chunk's
 // own error, found by run_update (hence `up`: what is there to copy, a header at least).  ERR_INVALID_PARAM with bad_window < 0:
@@ -484,6 +604,7 @@ inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, cons
     pack_rows(nwindows, w, tsv.data(), hp, dw);
     hp->bytes_uploaded = hp->comp_bytes_uploaded;
     for (const int64_t b : hp->wbytes) hp->bytes_uploaded += b;
+    for (const int64_t b : hp->mbytes) hp->bytes_uploaded += b;      // (masked calls only: the table is empty otherwise)
     return 0;
 }
 inline int plan_update_host(int typesize, int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_size,

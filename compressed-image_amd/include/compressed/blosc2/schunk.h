@@ -430,6 +430,103 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 					}
 				}
 
+				/// One rectangle of fill_regions / the masked set_regions: a strided_rect whose data (if the call has a source) starts at
+				/// r.src_off, whose mask bytes (if the call has a mask) start at mask_off, and whose value (if the call has no source) is
+				/// `value`.  An image's channels share the mask: their rects differ in src_off and value, not in mask_off.
+				struct masked_rect { strided_rect r; size_t mask_off; T value; };
+
+				/// Batch building block of fill_regions and the masked set_regions: plan_regions_write over cimg_window_masked.  src null:
+				/// every rectangle is painted with its value and no source is named; mask null: every sample is written.  A lazy chunk
+				/// that holds a sample is filled with its value and patched on the host under the same mask, in region order.  (Template
+				/// over the job so that only callers refer to the masked entry point's types.)
+				template <typename Job>
+				void plan_regions_write_masked(const T* src, const uint8_t* mask, const std::vector<masked_rect>& rects, size_t row_len, Job& job,
+					region_write& rw) const
+				{
+					rw.job_first = job.chunks.size();
+					size_t cs = 0;
+					for (size_t i = 0; i < m_Chunks.size();)
+					{
+						const bool lazy = m_Chunks[i].is_lazy();
+						size_t j = i, ce = cs;
+						while (j < m_Chunks.size() && m_Chunks[j].is_lazy() == lazy) { ce += m_Chunks[j].num_elements; ++j; if (lazy) break; }
+						const int32_t first = static_cast<int32_t>(job.chunks.size());
+						std::vector<T> px;
+						bool met = false;
+						std::vector<cimg_window_masked> wins;
+						std::vector<const std::byte*> srcs;
+						std::vector<const uint8_t*> masks;
+						for (const masked_rect& mr : rects)
+						{
+							const strided_rect& q = mr.r;
+							if (q.nx == 0 || q.ny == 0 || ce == cs) continue;
+							const size_t base = q.y * row_len + q.x, stride = q.sy * row_len, reach = (q.nx - 1) * q.sx;   // a row's samples: [rs, rs + reach]
+							const size_t r_lo = cs <= base + reach ? 0 : (cs - base - reach + stride - 1) / stride;
+							const size_t r_hi = base >= ce ? 0 : std::min(q.ny, (ce - 1 - base) / stride + 1);
+							auto cols = [&](size_t r, size_t& c_lo, size_t& c_hi) {
+								const size_t rs = base + r * stride;
+								c_lo = rs >= cs ? 0 : (cs - rs + q.sx - 1) / q.sx;
+								c_hi = std::min(q.nx - 1, (ce - 1 - rs) / q.sx);
+								return c_lo <= c_hi && c_lo < q.nx;
+							};
+							auto emit = [&](size_t ra, size_t rb, size_t c_lo, size_t c_hi) {
+								met = true;
+								if (lazy)
+								{
+									if (px.empty()) px.assign(m_Chunks[i].num_elements, std::get<T>(m_Chunks[i].value));
+									for (size_t r = ra; r < rb; ++r)
+										for (size_t c = c_lo; c <= c_hi; ++c)
+											if (!mask || mask[mr.mask_off + r * q.nx + c]) px[base + r * stride + c * q.sx - cs] = src ? src[q.src_off + r * q.nx + c] : mr.value;
+									return;
+								}
+								cimg_window_masked win{};
+								win.chunk_first = first;
+								win.chunk_count = static_cast<int32_t>(j - i);
+								win.origin = static_cast<int64_t>(base + ra * stride + c_lo * q.sx - cs);
+								win.row_pitch = static_cast<int64_t>(stride);
+								win.col_pitch = static_cast<int64_t>(q.sx);
+								win.width = static_cast<int32_t>(c_hi - c_lo + 1);
+								win.height = static_cast<int32_t>(rb - ra);
+								if (src) win.out_pitch = static_cast<int64_t>(q.nx * sizeof(T));
+								else
+								{
+									static_assert(sizeof(T) <= sizeof(win.value), "a constant has at most 8 bytes");
+									win.flags |= CIMG_WM_CONST;
+									std::memcpy(win.value, &mr.value, sizeof(T));
+								}
+								if (mask) { win.flags |= CIMG_WM_MASK; win.mask_pitch = static_cast<int64_t>(q.nx); }
+								wins.push_back(win);
+								srcs.push_back(src ? reinterpret_cast<const std::byte*>(src + q.src_off + ra * q.nx + c_lo) : nullptr);
+								masks.push_back(mask ? mask + mr.mask_off + ra * q.nx + c_lo : nullptr);
+							};
+							size_t ra = r_lo, rb = r_hi, c_lo = 0, c_hi = 0;
+							if (ra < rb) { if (cols(ra, c_lo, c_hi)) { if (c_lo > 0 || c_hi < q.nx - 1 || rb - ra == 1) { emit(ra, ra + 1, c_lo, c_hi); ++ra; } } else ++ra; }
+							if (ra < rb) { if (cols(rb - 1, c_lo, c_hi)) { if (c_lo > 0 || c_hi < q.nx - 1) { emit(rb - 1, rb, c_lo, c_hi); --rb; } } else --rb; }
+							if (ra < rb) emit(ra, rb, 0, q.nx - 1);
+						}
+						if (met && lazy)
+						{
+							rw.lazy.push_back(i);
+							rw.lazy_pixels.push_back(std::move(px));
+						}
+						else if (met)
+						{
+							for (size_t k = i; k < j; ++k)
+							{
+								job.chunks.push_back(m_Chunks[k].bytes().data());
+								job.held.push_back(m_Chunks[k].bytes().size());
+								job.destsize.push_back(static_cast<int32_t>(min_compressed_size(m_ChunkSize)));
+								rw.compressed.push_back(k);
+							}
+							job.windows.insert(job.windows.end(), wins.begin(), wins.end());
+							job.srcs.insert(job.srcs.end(), srcs.begin(), srcs.end());
+							job.masks.insert(job.masks.end(), masks.begin(), masks.end());
+						}
+						cs = ce;
+						i = j;
+					}
+				}
+
 				/// After the engine call succeeded: take this table's new chunks out of the call's results and compress the patched lazy
 				/// chunks (one batch call).  May throw; nothing of the table has changed yet.
 				void prepare_region_write(context_raw_ptr cctx, region_write& rw, std::vector<std::vector<std::byte>>& made) const

@@ -550,6 +550,65 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				return out;
 			}
 
+			// The same over cimg_window_masked (cimg_update_windows_masked_host): fill_region / fill_regions and the masked set_region /
+			// set_regions.  srcs[k] is null for a constant window, masks[k] for an unmasked one; a call of constant windows names no
+			// source at all, so nothing but the touched chunks (and the mask rows) travels.  A template, so that only code that
+			// instantiates it refers to the masked entry point.
+			struct update_job_masked
+			{
+				std::vector<const std::byte*> chunks;
+				std::vector<size_t> held;
+				std::vector<int32_t> destsize;
+				std::vector<cimg_window_masked> windows;
+				std::vector<const std::byte*> srcs;
+				std::vector<const uint8_t*> masks;
+				cimg_cparams cparams{};
+			};
+
+			template <typename Job = update_job_masked>
+			inline std::vector<std::vector<std::byte>> update_windows_masked(Job& job)
+			{
+				const size_t n = job.chunks.size();
+				std::vector<std::vector<std::byte>> out(n);
+				if (job.windows.empty()) return out;
+				if (job.windows.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range("fill_regions: too many windows for one call");
+				const std::byte* cbase = job.chunks[0];
+				for (const auto* c : job.chunks) if (c < cbase) cbase = c;
+				const std::byte* sbase = nullptr;
+				for (const auto* s : job.srcs) if (s && (!sbase || s < sbase)) sbase = s;
+				const uint8_t* mbase = nullptr;
+				for (const auto* m : job.masks) if (m && (!mbase || m < mbase)) mbase = m;
+				std::vector<int64_t> comp_off(n);
+				std::vector<int32_t> held(n), status(n), ncb(n);
+				std::vector<void*> made(n, nullptr);
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (job.held[i] > static_cast<size_t>(std::numeric_limits<int32_t>::max()))
+						throw std::out_of_range(detail::text("Blosc2 chunk size may not exceed numeric limit of int32_t, got ", job.held[i]));
+					comp_off[i] = job.chunks[i] - cbase;
+					held[i] = static_cast<int32_t>(job.held[i]);
+				}
+				for (size_t k = 0; k < job.windows.size(); ++k)
+				{
+					if (job.srcs[k]) job.windows[k].out_off = job.srcs[k] - sbase;
+					if (job.masks[k]) job.windows[k].mask_off = job.masks[k] - mbase;
+				}
+				const auto alloc = [](void*, size_t bytes) -> void* { return std::malloc(bytes ? bytes : 1); };
+				const int rc = cimg_update_windows_masked_host(engine(), &job.cparams, static_cast<int32_t>(n), cbase, comp_off.data(), held.data(),
+					job.destsize.data(), static_cast<int32_t>(job.windows.size()), job.windows.data(), sbase, mbase, alloc, nullptr, made.data(),
+					ncb.data(), status.data());
+				for (size_t i = 0; i < n; ++i)
+				{
+					if (!made[i]) continue;
+					const auto* b = static_cast<const std::byte*>(made[i]);
+					out[i].assign(b, b + ncb[i]);
+					std::free(made[i]);
+				}
+				if (rc < 0)
+					throw std::runtime_error(detail::text("Error code ", rc, " while writing masked regions into blosc2 chunks (", cimg_last_error(engine()), ")"));
+				return out;
+			}
+
 			// one chunk -> its pixels; chunk_bytes = what the chunk buffer really holds (0: unknown, trust the header)
 			struct target { const std::byte* chunk; std::byte* out; size_t capacity; size_t chunk_bytes = 0; };
 

@@ -280,6 +280,81 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				s.commit_region_write(rw);
 			}, *m_Schunk);
 		}
+		/// Paint the (subsampled) rectangle with one value: np.copyto(view, value).  No h x w copies of the value exist anywhere: only
+		/// the touched chunks go to the device.  With trunc-prec storage the value is truncated like any written pixel.
+		void fill_region(T value, size_t x, size_t y, size_t width, size_t height, size_t step_x = 1, size_t step_y = 1)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			fill_regions(std::span<const region>(&r, 1), std::span<const T>(&value, 1));
+		}
+		/// Many rectangles painted in ONE engine call: `values` holds one value for all regions or one per region; later regions win.
+		void fill_regions(std::span<const region> regions, std::span<const T> values) { write_masked(regions, nullptr, values, nullptr, "fill_regions"); }
+		/// fill_regions through mattes: `mask` holds one byte an element, back to back in region order, each region row-major in its
+		/// subsampled shape; an element is painted where its mask byte is not 0 and keeps its value elsewhere.
+		void fill_regions(std::span<const region> regions, std::span<const T> values, std::span<const uint8_t> mask)
+		{
+			if (mask.size() != check_regions(regions))
+				throw std::invalid_argument(detail::text("fill_regions: the mask holds ", mask.size(), " bytes, the regions have ", check_regions(regions), " elements"));
+			if (mask.empty()) return;                                 // (no element anywhere)
+			write_masked(regions, nullptr, values, mask.data(), "fill_regions");
+		}
+		/// set_region through a matte: np.copyto(view, data, where=mask).  data and mask have the subsampled shape.  One engine call,
+		/// every touched block decoded once.  (The mask trails the steps, which have no defaults here.)
+		void set_region(std::span<const T> data, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, std::span<const uint8_t> mask)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), data, mask);
+		}
+		/// set_regions through mattes: data and masks lie back to back in region order, both in the subsampled shapes.
+		void set_regions(std::span<const region> regions, std::span<const T> data, std::span<const uint8_t> mask)
+		{
+			const size_t total = check_regions(regions);
+			if (data.size() != total)
+				throw std::invalid_argument(detail::text("set_regions: span holds ", data.size(), " elements, the regions have ", total));
+			if (mask.size() != total)
+				throw std::invalid_argument(detail::text("set_regions: the mask holds ", mask.size(), " bytes, the regions have ", total, " elements"));
+			if (total == 0) return;
+			write_masked(regions, data.data(), std::span<const T>(), mask.data(), "set_regions");
+		}
+		/// The regions as the chunk table takes them for a masked / constant write of channel `channel` of `channels`: data region-major,
+		/// channel-minor as in region_rects, the mask region-major only (an image's channels share it); value: this channel's, one or
+		/// one per region.
+		template <typename Table>
+		static std::vector<typename Table::masked_rect> masked_rects(std::span<const region> regions, size_t channel, size_t channels, std::span<const T> values)
+		{
+			std::vector<typename Table::masked_rect> out;
+			size_t at = 0, mat = 0;
+			for (size_t k = 0; k < regions.size(); ++k)
+			{
+				const region& r = regions[k];
+				const size_t n = r.out_elems();
+				const T v = values.empty() ? T{} : values[values.size() == 1 ? 0 : k];
+				if (n) out.push_back({ { r.x, r.y, (r.width + r.step_x - 1) / r.step_x, (r.height + r.step_y - 1) / r.step_y, r.step_x, r.step_y, at + channel * n }, mat, v });
+				at += channels * n;
+				mat += n;
+			}
+			return out;
+		}
+		/// fill_regions and the masked set_regions: ONE engine call (cimg_update_windows_masked_host).  Every region is checked before
+		/// anything runs; lazy chunks a region meets become real; nothing changes unless the whole call succeeds.
+		void write_masked(std::span<const region> regions, const T* src, std::span<const T> values, const uint8_t* mask, const char* what)
+		{
+			if (!src && values.size() != 1 && values.size() != regions.size())
+				throw std::invalid_argument(detail::text(what, ": got ", values.size(), " values for ", regions.size(), " regions (one, or one per region)"));
+			if (check_regions(regions) == 0) return;
+			require();
+			require_encoder();
+			blosc2::batch::update_job_masked job;
+			region_cparams(job.cparams);
+			std::visit([&](auto& s) {
+				using table_t = std::decay_t<decltype(s)>;
+				typename table_t::region_write rw;
+				s.plan_regions_write_masked(src, mask, masked_rects<table_t>(regions, 0, 1, values), m_Width, job, rw);
+				auto made = blosc2::batch::update_windows_masked(job);
+				s.prepare_region_write(m_CompressionContext.get(), rw, made);
+				s.commit_region_write(rw);
+			}, *m_Schunk);
+		}
 		/// The regions as the chunk table takes them; region k's data starts where `channels` channels of the regions before it end,
 		/// plus `channel` pieces of its own (an image's data is region-major, channel-minor).
 		template <typename Table>

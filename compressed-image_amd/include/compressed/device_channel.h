@@ -571,6 +571,39 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, w, d_src);
 		}
 
+		/// Paint the (subsampled) rectangle with one value: np.copyto(view, value) without a source array.  Only the blocks that hold a
+		/// written element are re-encoded, and a block the rectangle covers whole (steps of 1) is not even decoded; nothing but the
+		/// window table reaches the device.  With trunc-prec storage the value is truncated like any written pixel.
+		void fill_region(T value, size_t x, size_t y, size_t width, size_t height, size_t step_x = 1, size_t step_y = 1)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			fill_regions(std::span<const region>(&r, 1), std::span<const T>(&value, 1));
+		}
+		/// Many rectangles painted in ONE engine call (cimg_update_windows_masked_device) and one repack: `values` holds one value for
+		/// all regions or one per region.  Later regions win where two overlap.
+		void fill_regions(std::span<const region> regions, std::span<const T> values) { write_masked(regions, nullptr, values, nullptr, "fill_regions"); }
+		/// fill_regions through a matte: d_mask holds one uint8 an element in device memory, back to back in region order, each
+		/// region row-major in its subsampled shape; an element is painted where its mask byte is not 0 and keeps its value elsewhere.
+		void fill_regions(std::span<const region> regions, std::span<const T> values, const uint8_t* d_mask)
+		{
+			if (!d_mask) throw std::invalid_argument("fill_regions: the mask is a null pointer");
+			write_masked(regions, nullptr, values, d_mask, "fill_regions");
+		}
+		/// set_region through a matte: np.copyto(view, src, where=mask).  d_src and d_mask (uint8, any nonzero byte writes) have the
+		/// subsampled shape, in device memory.  One engine call, every touched block decoded once.
+		/// (The mask trails the steps, which have no defaults here: a literal 0 must never be taken for a null mask.)
+		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, const uint8_t* d_mask)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src, d_mask);
+		}
+		/// set_regions through mattes: data and masks lie back to back in region order, both in the subsampled shapes.
+		void set_regions(std::span<const region> regions, const T* d_src, const uint8_t* d_mask)
+		{
+			if (!d_src || !d_mask) throw std::invalid_argument("set_regions: the source or the mask is a null pointer");
+			write_masked(regions, d_src, std::span<const T>(), d_mask, "set_regions");
+		}
+
 		void check_region(size_t x, size_t y, size_t width, size_t height) const
 		{
 			if (x > m_Width || y > m_Height || width > m_Width - x || height > m_Height - y)
@@ -621,16 +654,67 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			return w;
 		}
 
+		/// The region as a masked window: a constant (d_src null: `value`) or source elements at out_off, under the mask bytes at mask_off
+		/// when there is a mask.
+		cimg_window_masked masked_window(const region& r, bool constant, T value, bool masked, size_t out_elems_before, size_t mask_elems_before) const
+		{
+			const cimg_window_strided s = region_window(r.x, r.y, r.width, r.height, r.step_x, r.step_y, out_elems_before * sizeof(T));
+			cimg_window_masked w{};
+			w.chunk_first = s.chunk_first; w.chunk_count = s.chunk_count;
+			w.origin = s.origin; w.row_pitch = s.row_pitch; w.col_pitch = s.col_pitch;
+			w.width = s.width; w.height = s.height;
+			if (constant)
+			{
+				static_assert(sizeof(T) <= sizeof(w.value), "a constant has at most 8 bytes");
+				w.flags |= CIMG_WM_CONST;
+				std::memcpy(w.value, &value, sizeof(T));
+			}
+			else { w.out_off = s.out_off; w.out_pitch = s.out_pitch; }
+			if (masked)
+			{
+				w.flags |= CIMG_WM_MASK;
+				w.mask_off = static_cast<int64_t>(mask_elems_before);
+				w.mask_pitch = s.width;
+			}
+			return w;
+		}
+		/// fill_regions and the masked set_regions: ONE engine call (cimg_update_windows_masked_device) and one repack.  Every region is
+		/// checked before anything runs; nothing changes unless the whole call succeeds.
+		void write_masked(std::span<const region> regions, const T* d_src, std::span<const T> values, const uint8_t* d_mask, const char* what)
+		{
+			if (m_ReadOnly) throw std::runtime_error(detail::text(what, ": this device_channel shares the store of a device_image and is read-only; use the device_image's"));
+			const bool constant = d_src == nullptr;
+			if (constant && values.size() != 1 && values.size() != regions.size())
+				throw std::invalid_argument(detail::text(what, ": got ", values.size(), " values for ", regions.size(), " regions (one, or one per region)"));
+			const size_t total = check_regions(regions);
+			require();
+			std::vector<cimg_window_masked> w;
+			size_t at = 0;
+			for (size_t k = 0; k < regions.size(); ++k)
+			{
+				const region& r = regions[k];
+				if (r.width && r.height) w.push_back(masked_window(r, constant, constant ? values[values.size() == 1 ? 0 : k] : T{}, d_mask != nullptr, at, at));
+				at += r.out_elems();
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range(detail::text(what, ": too many regions for one call"));
+			if (d_src) detail::device_range(m_Store->engine, d_src, total * sizeof(T), what);
+			if (d_mask) detail::device_range(m_Store->engine, d_mask, total, what);
+			m_Store = updated_store(*m_Store, cparams(), m_ChunkSize, w, d_src, d_mask);
+		}
+
 		/// Apply window writes to a store: the update's output goes to a scratch allocation, then ONE pack launch gathers the new
 		/// store -- untouched chunks from the old one, touched ones from the scratch.  The old store is left as it was.
 		/// (Window: cimg_window through cimg_update_windows_device, cimg_window_strided through cimg_update_windows_strided_device,
-		/// cimg_window_typed through cimg_update_windows_typed_device -- each instantiation refers to its own entry point only)
+		/// cimg_window_typed through cimg_update_windows_typed_device, cimg_window_masked through cimg_update_windows_masked_device with
+		/// d_mask beside d_src -- each instantiation refers to its own entry point only)
 		template <typename Window>
 		static std::shared_ptr<detail::device_store> updated_store(const detail::device_store& old, const cimg_cparams& cp, size_t nominal_chunk_bytes,
-			const std::vector<Window>& windows, const void* d_src)
+			const std::vector<Window>& windows, const void* d_src, const void* d_mask = nullptr)
 		{
 			constexpr bool typed = std::is_same_v<Window, cimg_window_typed>;
-			constexpr bool strided = std::is_same_v<Window, cimg_window_strided> || typed;
+			constexpr bool masked = std::is_same_v<Window, cimg_window_masked>;
+			constexpr bool strided = std::is_same_v<Window, cimg_window_strided> || typed || masked;
 			cimg_engine* e = old.engine;
 			const size_t n = old.num_chunks();
 			const int32_t dest = static_cast<int32_t>(blosc2::min_compressed_size(nominal_chunk_bytes));
@@ -658,7 +742,11 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			detail::device_store scratch;
 			scratch.allocate(e, scratch_bytes + 64);
 			detail::engine_lock lock(e);
-			if constexpr (typed)
+			if constexpr (masked)
+				detail::engine_call(e, cimg_update_windows_masked_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(),
+					old.nbytes.data(), old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, d_mask,
+					scratch.base, new_off.data(), new_cbytes.data(), status.data()), "Writing the masked regions");
+			else if constexpr (typed)
 				detail::engine_call(e, cimg_update_windows_typed_device(e, &cp, static_cast<int32_t>(n), old.base, old.off.data(), old.cbytes.data(),
 					old.nbytes.data(), old.blocksize.data(), destsize.data(), static_cast<int32_t>(windows.size()), windows.data(), d_src, scratch.base,
 					new_off.data(), new_cbytes.data(), status.data()), "Writing the typed regions");

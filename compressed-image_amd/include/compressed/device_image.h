@@ -317,6 +317,65 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src);
 		}
 
+		/// Paint the (subsampled) rectangle of every channel: `values` holds one value for all channels or one a channel.  No source
+		/// array exists anywhere; one engine call (cimg_update_windows_masked_device) and one repack of the store.
+		void fill_region(std::span<const T> values, size_t x, size_t y, size_t width, size_t height, size_t step_x = 1, size_t step_y = 1)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			fill_regions(std::span<const region>(&r, 1), values);
+		}
+		void fill_regions(std::span<const region> regions, std::span<const T> values) { write_masked(regions, nullptr, values, nullptr, false, "fill_regions"); }
+		/// fill_regions through mattes in device memory.  The channels share ONE mask: a byte an element of a region, back to back in
+		/// region order, each region row-major in its subsampled shape.
+		void fill_regions(std::span<const region> regions, std::span<const T> values, const uint8_t* d_mask)
+		{
+			if (!d_mask) throw std::invalid_argument("fill_regions: the mask is a null pointer");
+			write_masked(regions, nullptr, values, d_mask, false, "fill_regions");
+		}
+		/// set_region of every channel through one shared matte (h', w'); d_src as set_regions takes it.  (The mask trails the steps.)
+		void set_region(const T* d_src, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, const uint8_t* d_mask)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), d_src, d_mask);
+		}
+		/// set_regions through mattes: data region-major, channel-minor; ONE mask for all channels, region-major.
+		void set_regions(std::span<const region> regions, const T* d_src, const uint8_t* d_mask)
+		{
+			if (!d_src || !d_mask) throw std::invalid_argument("set_regions: the source or the mask is a null pointer");
+			write_masked(regions, d_src, std::span<const T>(), d_mask, true, "set_regions");
+		}
+		void write_masked(std::span<const region> regions, const T* d_src, std::span<const T> values, const uint8_t* d_mask, bool has_src, const char* what)
+		{
+			if (!has_src && values.size() != 1 && values.size() != m_NumChannels)
+				throw std::invalid_argument(detail::text(what, ": got ", values.size(), " values for ", m_NumChannels, " channels (one, or one a channel)"));
+			const size_t per_channel = prototype().check_regions(regions);
+			if (m_NumChannels == 0) return;
+			std::vector<device_channel<T>> per_ch;                    // one prototype a channel, made once
+			for (size_t c = 0; c < m_NumChannels; ++c)
+			{
+				per_ch.push_back(prototype());
+				per_ch.back().m_First = c * chunks_per_channel();
+				per_ch.back().m_Count = chunks_per_channel();
+			}
+			std::vector<cimg_window_masked> w;
+			size_t at = 0, mat = 0;
+			for (const region& r : regions)
+			{
+				for (size_t c = 0; c < m_NumChannels; ++c)
+				{
+					if (r.width && r.height)
+						w.push_back(per_ch[c].masked_window(r, !has_src, has_src ? T{} : values[values.size() == 1 ? 0 : c], d_mask != nullptr, at, mat));
+					at += r.out_elems();
+				}
+				mat += r.out_elems();
+			}
+			if (w.empty()) return;
+			if (w.size() > static_cast<size_t>(std::numeric_limits<int32_t>::max())) throw std::out_of_range(detail::text(what, ": too many regions for one call"));
+			if (d_src) detail::device_range(m_Store->engine, d_src, per_channel * m_NumChannels * sizeof(T), what);
+			if (d_mask) detail::device_range(m_Store->engine, d_mask, per_channel, what);
+			m_Store = device_channel<T>::updated_store(*m_Store, prototype().cparams(), m_ChunkSize, w, d_src, d_mask);
+		}
+
 		/// Write U = float, half or T over the (subsampled) rectangle of every channel, channel c converted with the inverse of
 		/// get_region<U> under scales[c] and offsets[c] (a span of one value serves every channel) in the patch launch itself.  d_src holds
 		/// planes (C, oh, ow) or, with `interleaved`, pixels (oh, ow, C): the C windows of a region then read the channel slots of the

@@ -365,6 +365,84 @@ namespace NAMESPACE_COMPRESSED_IMAGE
 				}, m_Channels[ch].chunks());
 		}
 
+		/// Paint the (subsampled) rectangle of every channel: `values` holds one value for all channels or one a channel.
+		void fill_region(std::span<const T> values, size_t x, size_t y, size_t width, size_t height, size_t step_x = 1, size_t step_y = 1)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			fill_regions(std::span<const region>(&r, 1), values);
+		}
+		/// Many rectangles of every channel painted: one engine call for all channels that share their codec parameters.
+		void fill_regions(std::span<const region> regions, std::span<const T> values) { write_masked(regions, nullptr, values, nullptr, false, "fill_regions"); }
+		/// fill_regions through mattes.  The channels share ONE mask: a byte an element of a region (not of a region and channel), back
+		/// to back in region order, each region row-major in its subsampled shape.
+		void fill_regions(std::span<const region> regions, std::span<const T> values, std::span<const uint8_t> mask)
+		{
+			write_masked(regions, nullptr, values, &mask, false, "fill_regions");
+		}
+		/// set_region of every channel through one shared matte: data as set_regions takes it (channel-minor), mask (h', w').
+		void set_region(std::span<const T> data, size_t x, size_t y, size_t width, size_t height, size_t step_x, size_t step_y, std::span<const uint8_t> mask)
+		{
+			const region r{ x, y, width, height, step_x, step_y };
+			set_regions(std::span<const region>(&r, 1), data, mask);
+		}
+		/// set_regions through mattes: data region-major, channel-minor; ONE mask for all channels, region-major.
+		void set_regions(std::span<const region> regions, std::span<const T> data, std::span<const uint8_t> mask)
+		{
+			size_t total = 0;
+			for (const auto& ch : m_Channels) total += ch.check_regions(regions);
+			if (data.size() != total)
+				throw std::invalid_argument(detail::text("set_regions: span holds ", data.size(), " elements, the regions have ", total));
+			write_masked(regions, data.data(), std::span<const T>(), &mask, true, "set_regions");
+		}
+		/// fill_regions and the masked set_regions of every channel: one engine call (cimg_update_windows_masked_host) per group of
+		/// channels that share their codec parameters; every region is checked before anything runs; lazy chunks a region meets become
+		/// real; nothing changes unless the whole call succeeds.
+		void write_masked(std::span<const region> regions, const T* src, std::span<const T> values, const std::span<const uint8_t>* mask, bool has_src, const char* what)
+		{
+			if (!has_src && values.size() != 1 && values.size() != m_Channels.size())
+				throw std::invalid_argument(detail::text(what, ": got ", values.size(), " values for ", m_Channels.size(), " channels (one, or one a channel)"));
+			size_t per_channel = 0;
+			for (const auto& ch : m_Channels) per_channel = ch.check_regions(regions);
+			if (mask && mask->size() != per_channel)
+				throw std::invalid_argument(detail::text(what, ": the mask holds ", mask->size(), " bytes, the regions have ", per_channel, " elements a channel"));
+			if (per_channel == 0 || m_Channels.empty()) return;
+			std::vector<blosc2::batch::update_job_masked> jobs;
+			std::vector<size_t> job_of(m_Channels.size());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+			{
+				cimg_cparams c{};
+				m_Channels[ch].region_cparams(c);
+				size_t k = 0;
+				while (k < jobs.size() && std::memcmp(&jobs[k].cparams, &c, sizeof c) != 0) ++k;
+				if (k == jobs.size()) { jobs.emplace_back(); jobs.back().cparams = c; }
+				job_of[ch] = k;
+			}
+			using table_var = std::variant<typename blosc2::schunk<T>::region_write, typename blosc2::lazy_schunk<T>::region_write>;
+			std::vector<table_var> rws;
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using table_t = std::decay_t<decltype(table)>;
+					typename table_t::region_write rw;
+					const T v = has_src ? T{} : values[values.size() == 1 ? 0 : ch];
+					table.plan_regions_write_masked(src, mask ? mask->data() : nullptr,
+						compressed::channel<T>::template masked_rects<table_t>(regions, ch, m_Channels.size(), std::span<const T>(&v, 1)), m_Channels[ch].width(),
+						jobs[job_of[ch]], rw);
+					rws.emplace_back(std::move(rw));
+				}, m_Channels[ch].chunks());
+			std::vector<std::vector<std::vector<std::byte>>> made;
+			for (auto& job : jobs) made.push_back(blosc2::batch::update_windows_masked(job));
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.prepare_region_write(m_Channels[ch].compression_context(), std::get<rw_t>(rws[ch]), made[job_of[ch]]);
+				}, m_Channels[ch].chunks());
+			for (size_t ch = 0; ch < m_Channels.size(); ++ch)
+				std::visit([&](auto& table) {
+					using rw_t = typename std::decay_t<decltype(table)>::region_write;
+					table.commit_region_write(std::get<rw_t>(rws[ch]));
+				}, m_Channels[ch].chunks());
+		}
+
 		/// All channels into caller-owned memory (num_channels * height * width elements, channel-major): no
 		/// intermediate vectors, no zero fill -- what the Python binding uses to decode straight into a numpy array.
 		void decompress_into(std::span<T> out) const

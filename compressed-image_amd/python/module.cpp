@@ -63,6 +63,34 @@ namespace
 		else return static_cast<T>(v.cast<long long>());
 	}
 
+	// value= of fill_region / fill_regions: a number (also a 0-d array), or -- where `many` > 0 -- a sequence or array of `many`
+	// numbers (regions for channels, channels for images)
+	template <typename T> std::vector<T> fill_values(const py::object& value, size_t many, const char* what)
+	{
+		const bool is_array = py::isinstance<py::array>(value);
+		const bool seq = is_array ? py::reinterpret_borrow<py::array>(value).ndim() > 0
+			: (py::isinstance<py::sequence>(value) && !py::isinstance<py::str>(value) && !py::isinstance<py::bytes>(value));
+		std::vector<T> v;
+		if (!seq) { v.push_back(from_scalar<T>(value)); return v; }
+		if (many == 0) throw py::value_error(std::string(what) + ": value must be one number");
+		for (auto h : value) v.push_back(from_scalar<T>(py::reinterpret_borrow<py::object>(h)));
+		if (v.size() != 1 && v.size() != many)
+			throw py::value_error(std::string(what) + ": value holds " + std::to_string(v.size()) + " numbers, expected one or " + std::to_string(many));
+		return v;
+	}
+	// mask= / masks= of the host classes: a numpy array of dtype bool or uint8 and exactly `shape` (a contiguous copy is kept)
+	inline std::pair<py::array, std::span<const uint8_t>> host_mask(const py::object& mask, const std::vector<py::ssize_t>& shape, const char* what)
+	{
+		if (!py::isinstance<py::array>(mask)) throw py::value_error(std::string(what) + ": a mask is a numpy array of dtype bool or uint8");
+		py::array a = py::reinterpret_borrow<py::array>(mask);
+		if (!a.dtype().is(py::dtype("uint8")) && !a.dtype().is(py::dtype("bool")))
+			throw py::value_error(std::string(what) + ": a mask has dtype bool or uint8, got " + std::string(py::str(a.dtype())));
+		if (std::vector<py::ssize_t>(a.shape(), a.shape() + a.ndim()) != shape)
+			throw py::value_error(std::string(what) + ": the mask's shape does not match the written elements' shape");
+		py::array c = py::module_::import("numpy").attr("ascontiguousarray")(a);
+		return { c, std::span<const uint8_t>(static_cast<const uint8_t*>(c.data()), static_cast<size_t>(c.size())) };
+	}
+
 	// contiguous view of the array's elements as T (copying only if it is not C-contiguous)
 	template <typename T> std::pair<py::array, std::span<const T>> elements(const py::array& a)
 	{
@@ -348,6 +376,44 @@ namespace
 				return 0;
 			});
 		}
+		// set_region / set_regions through mattes (mask: (h', w') / (N, h', w') numpy, bool or uint8): np.copyto(view, array, where=mask)
+		void set_regions_masked(const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t step_x, py::ssize_t step_y,
+			const py::object& masks, bool single)
+		{
+			const char* what = single ? "set_region" : "set_regions";
+			check_steps(step_x, step_y);
+			const py::ssize_t nd = single ? 2 : 3;
+			if (arrays.ndim() != nd) throw py::value_error(std::string(what) + (single ? ": the array must have the shape (height, width)" : ": arrays must have the shape (N, height, width)"));
+			const auto regions = region_list(xs, ys, static_cast<py::ssize_t>(covered(arrays.shape(nd - 1), step_x)),
+				static_cast<py::ssize_t>(covered(arrays.shape(nd - 2), step_y)), step_x, step_y);
+			if (!single && regions.size() != static_cast<size_t>(arrays.shape(0)))
+				throw py::value_error(std::string(what) + ": got " + std::to_string(arrays.shape(0)) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(compressed::channel<T>& ch) {
+				if (!arrays.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				auto [mkeep, m] = host_mask(masks, std::vector<py::ssize_t>(arrays.shape(), arrays.shape() + arrays.ndim()), what);
+				ch.check_regions(regions);
+				auto [keep, px] = elements<T>(arrays);
+				ch.set_regions(regions, px, m);
+				return 0;
+			});
+		}
+		// fill_region / fill_regions: value a number (fill_regions: or N numbers), masks (h', w') / (N, h', w') or None
+		void fill_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& value,
+			py::ssize_t step_x, py::ssize_t step_y, const py::object& masks, bool single)
+		{
+			const char* what = single ? "fill_region" : "fill_regions";
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			visit([&]<typename T>(compressed::channel<T>& ch) {
+				const std::vector<T> values = fill_values<T>(value, single ? 0 : regions.size(), what);
+				std::vector<py::ssize_t> shape{ ceil_div(height, step_y), ceil_div(width, step_x) };
+				if (!single) shape.insert(shape.begin(), static_cast<py::ssize_t>(regions.size()));
+				ch.check_regions(regions);
+				if (masks.is_none()) { ch.fill_regions(regions, values); return 0; }
+				auto [mkeep, m] = host_mask(masks, shape, what);
+				ch.fill_regions(regions, values, m);
+				return 0;
+			});
+		}
 		// a[key] = value for the keys of __getitem__: anything numpy.broadcast_to(numpy.asarray(value), selection shape) accepts;
 		// scalars and sequences are converted to the channel's dtype, an ARRAY of another dtype is refused
 		void setitem(const py::object& key, const py::object& value)
@@ -549,6 +615,50 @@ namespace
 				return 0;
 			});
 		}
+		// set_region / set_regions of every channel through ONE shared matte: arrays a list of C (h', w') arrays (set_region) or
+		// (N, C, h', w') (set_regions); mask (h', w') / (N, h', w'), numpy bool or uint8
+		void set_regions_masked(const py::object& xs, const py::object& ys, const py::object& arrays_in, py::ssize_t step_x, py::ssize_t step_y,
+			const py::object& masks, bool single)
+		{
+			const char* what = single ? "set_region" : "set_regions";
+			check_steps(step_x, step_y);
+			py::module_ np = py::module_::import("numpy");
+			py::array arrays = single ? py::array(np.attr("stack")(arrays_in)) : py::array(np.attr("asarray")(arrays_in));   // (C, h', w') / (N, C, h', w')
+			const py::ssize_t nd = single ? 3 : 4;
+			if (arrays.ndim() != nd) throw py::value_error(std::string(what) + (single ? ": one (height, width) array a channel" : ": arrays must have the shape (N, channels, height, width)"));
+			const auto regions = region_list(xs, ys, static_cast<py::ssize_t>(covered(arrays.shape(nd - 1), step_x)),
+				static_cast<py::ssize_t>(covered(arrays.shape(nd - 2), step_y)), step_x, step_y);
+			if (!single && regions.size() != static_cast<size_t>(arrays.shape(0)))
+				throw py::value_error(std::string(what) + ": got " + std::to_string(arrays.shape(0)) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(const img_ptr<T>& img) {
+				if (!arrays.dtype().is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
+				if (static_cast<size_t>(arrays.shape(nd - 3)) != img->num_channels()) throw py::value_error(std::string(what) + ": the arrays' channel count does not match the image");
+				std::vector<py::ssize_t> mshape{ arrays.shape(nd - 2), arrays.shape(nd - 1) };
+				if (!single) mshape.insert(mshape.begin(), arrays.shape(0));
+				auto [mkeep, m] = host_mask(masks, mshape, what);
+				img->check_regions(regions);
+				auto [keep, px] = elements<T>(arrays);
+				img->set_regions(regions, px, m);
+				return 0;
+			});
+		}
+		// fill_region / fill_regions of every channel: value a number or C numbers, masks shared by the channels
+		void fill_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& value,
+			py::ssize_t step_x, py::ssize_t step_y, const py::object& masks, bool single)
+		{
+			const char* what = single ? "fill_region" : "fill_regions";
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			visit([&]<typename T>(const img_ptr<T>& img) {
+				const std::vector<T> values = fill_values<T>(value, img->num_channels(), what);
+				std::vector<py::ssize_t> shape{ ceil_div(height, step_y), ceil_div(width, step_x) };
+				if (!single) shape.insert(shape.begin(), static_cast<py::ssize_t>(regions.size()));
+				img->check_regions(regions);
+				if (masks.is_none()) { img->fill_regions(regions, values); return 0; }
+				auto [mkeep, m] = host_mask(masks, shape, what);
+				img->fill_regions(regions, values, m);
+				return 0;
+			});
+		}
 		py::array get_decompressed() const
 		{
 			return visit([]<typename T>(const img_ptr<T>& img) {
@@ -702,6 +812,15 @@ namespace
 		if (x < 0 || y < 0 || w < 0 || h < 0) throw py::value_error("region coordinates and sizes must be >= 0");
 	}
 
+	// mask= / masks= of the device classes: bool or uint8 in device memory, of exactly `shape`
+	inline const uint8_t* device_mask(const py::object& mask, const std::vector<py::ssize_t>& shape, const char* what)
+	{
+		const device_view m = view_of(mask, what);
+		if (!m.dt.is(py::dtype("uint8")) && !m.dt.is(py::dtype("bool")))
+			throw py::value_error(std::string(what) + ": a mask has dtype bool or uint8, got " + std::string(py::str(m.dt)));
+		if (m.shape != shape) throw py::value_error(std::string(what) + ": the mask's shape does not match the written elements' shape");
+		return static_cast<const uint8_t*>(m.ptr);
+	}
 	template <typename T> using dchan_ptr = std::shared_ptr<compressed::device_channel<T>>;
 	using any_dchannel = std::variant<dchan_ptr<compressed::half>, dchan_ptr<float>, dchan_ptr<double>, dchan_ptr<uint8_t>, dchan_ptr<int8_t>,
 		dchan_ptr<uint16_t>, dchan_ptr<int16_t>, dchan_ptr<uint32_t>, dchan_ptr<int32_t>>;
@@ -826,14 +945,28 @@ namespace
 		// array: (h', w') in device memory, written over every step_y-th row and step_x-th element from (x, y)
 		// (dtype=: the array holds float32, float16 or the stored type and every element is unscaled, rounded and stored in the patch launch)
 		void set_region(py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y,
-			const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0))
+			const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0), const py::object& offset = py::float_(0.0),
+			const py::object& mask = py::none())
 		{
 			if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
 			check_steps(step_x, step_y);
 			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
 			if (dtype.is_none()) require_plain(sc, of, "set_region");
+			if (!mask.is_none() && !dtype.is_none()) throw py::value_error("set_region: mask= cannot be combined with dtype= (masked typed writes are not built)");
 			const device_view v = view_of(array, "set_region");
 			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				if (!mask.is_none())
+				{
+					if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+					if (v.shape.size() != 2) throw py::value_error("region arrays must be two-dimensional (height, width), got " + std::to_string(v.shape.size()) + " dimensions");
+					const uint8_t* m = device_mask(mask, v.shape, "set_region");
+					const size_t w = covered(v.shape[1], step_x), h = covered(v.shape[0], step_y);
+					ch.check_region(static_cast<size_t>(x), static_cast<size_t>(y), w, h);
+					wait_for(stream);
+					ch.set_region(static_cast<const T*>(v.ptr), static_cast<size_t>(x), static_cast<size_t>(y), w, h, static_cast<size_t>(step_x),
+						static_cast<size_t>(step_y), m);
+					return 0;
+				}
 				if (!dtype.is_none())
 				{
 					typed_source_dispatch<T>(dtype, v.dt, [&]<typename U>() {
@@ -862,12 +995,13 @@ namespace
 		// arrays: (N, h', w') in device memory (pixels: (N,)), region k from (xs[k], ys[k]); later regions win
 		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
 			py::ssize_t step_y, bool pixels, const py::object& dtype = py::none(), const py::object& scale = py::float_(1.0),
-			const py::object& offset = py::float_(0.0))
+			const py::object& offset = py::float_(0.0), const py::object& masks = py::none())
 		{
 			const char* what = pixels ? "set_pixels" : "set_regions";
 			check_steps(step_x, step_y);
 			const std::vector<float> sc = float_list(scale, 1, "scale"), of = float_list(offset, 1, "offset");
 			if (dtype.is_none()) require_plain(sc, of, what);
+			if (!masks.is_none() && !dtype.is_none()) throw py::value_error(std::string(what) + ": masks= cannot be combined with dtype= (masked typed writes are not built)");
 			const device_view v = view_of(arrays, what);
 			if (v.shape.size() != (pixels ? 1u : 3u)) throw py::value_error(std::string(what) + (pixels ? ": values must have the shape (N,)" : ": arrays must have the shape (N, height, width)"));
 			const auto regions = region_list(xs, ys, pixels ? 1 : static_cast<py::ssize_t>(covered(v.shape[2], step_x)),
@@ -885,10 +1019,38 @@ namespace
 					return 0;
 				}
 				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the channel dtype");
+				const uint8_t* m = masks.is_none() ? nullptr : device_mask(masks, v.shape, what);
 				ch.check_regions(regions);
 				if (regions.empty() || v.count() == 0) return 0;
 				wait_for(stream);
-				ch.set_regions(regions, static_cast<const T*>(v.ptr));
+				if (m) ch.set_regions(regions, static_cast<const T*>(v.ptr), m);
+				else ch.set_regions(regions, static_cast<const T*>(v.ptr));
+				return 0;
+			});
+		}
+		// paint every step_y-th row and step_x-th element of the rectangle with one value (mask: (h', w') bool / uint8 in device memory,
+		// paint only where it is not 0): no source array exists anywhere
+		void fill_region(py::ssize_t x, py::ssize_t y, py::ssize_t width, py::ssize_t height, const py::object& value, std::optional<uintptr_t> stream,
+			py::ssize_t step_x, py::ssize_t step_y, const py::object& mask)
+		{
+			fill_regions(py::make_tuple(x), py::make_tuple(y), width, height, value, stream, step_x, step_y, mask, true);
+		}
+		// N rectangles of one size painted in one engine call: value a number or N numbers, masks (N, h', w')
+		void fill_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& value,
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, const py::object& masks, bool single = false)
+		{
+			const char* what = single ? "fill_region" : "fill_regions";
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			visit([&]<typename T>(compressed::device_channel<T>& ch) {
+				const std::vector<T> values = fill_values<T>(value, single ? 0 : regions.size(), what);
+				std::vector<py::ssize_t> shape{ ceil_div(height, step_y), ceil_div(width, step_x) };
+				if (!single) shape.insert(shape.begin(), static_cast<py::ssize_t>(regions.size()));
+				const uint8_t* m = masks.is_none() ? nullptr : device_mask(masks, shape, what);
+				ch.check_regions(regions);
+				if (regions.empty() || width == 0 || height == 0) return 0;
+				wait_for(stream);
+				if (m) ch.fill_regions(std::span<const compressed::region>(regions), std::span<const T>(values), m);
+				else ch.fill_regions(std::span<const compressed::region>(regions), std::span<const T>(values));
 				return 0;
 			});
 		}
@@ -1092,6 +1254,52 @@ namespace
 				return 0;
 			});
 		}
+		// set_region / set_regions of every channel through ONE shared matte in device memory: array (C, h', w') / (N, C, h', w'),
+		// mask (h', w') / (N, h', w'), bool or uint8
+		void set_regions_masked(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
+			py::ssize_t step_y, const py::object& masks, bool single)
+		{
+			const char* what = single ? "set_region" : "set_regions";
+			check_steps(step_x, step_y);
+			const device_view v = view_of(arrays, what);
+			const size_t nd = single ? 3 : 4;
+			if (v.shape.size() != nd) throw py::value_error(std::string(what) + (single ? ": region arrays must have the shape (channels, height, width)" : ": arrays must have the shape (N, channels, height, width)"));
+			const auto regions = region_list(xs, ys, static_cast<py::ssize_t>(covered(v.shape[nd - 1], step_x)), static_cast<py::ssize_t>(covered(v.shape[nd - 2], step_y)),
+				step_x, step_y);
+			if (!single && regions.size() != static_cast<size_t>(v.shape[0]))
+				throw py::value_error(std::string(what) + ": got " + std::to_string(v.shape[0]) + " arrays for " + std::to_string(regions.size()) + " coordinates");
+			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				if (!v.dt.is(np_dtype<T>())) throw py::value_error("array dtype does not match the image dtype");
+				if (static_cast<size_t>(v.shape[nd - 3]) != img->num_channels()) throw py::value_error(std::string(what) + ": the arrays' channel count does not match the image");
+				std::vector<py::ssize_t> mshape{ v.shape[nd - 2], v.shape[nd - 1] };
+				if (!single) mshape.insert(mshape.begin(), v.shape[0]);
+				const uint8_t* m = device_mask(masks, mshape, what);
+				if (img->num_channels()) img->channel(0).check_regions(regions);
+				if (regions.empty() || v.count() == 0) return 0;
+				wait_for(stream);
+				img->set_regions(std::span<const compressed::region>(regions), static_cast<const T*>(v.ptr), m);
+				return 0;
+			});
+		}
+		// fill_region / fill_regions of every channel: value a number or C numbers; masks (h', w') / (N, h', w') in device memory, shared
+		void fill_regions(const py::object& xs, const py::object& ys, py::ssize_t width, py::ssize_t height, const py::object& value,
+			std::optional<uintptr_t> stream, py::ssize_t step_x, py::ssize_t step_y, const py::object& masks, bool single)
+		{
+			const char* what = single ? "fill_region" : "fill_regions";
+			const auto regions = region_list(xs, ys, width, height, step_x, step_y);
+			visit([&]<typename T>(const dimg_ptr<T>& img) {
+				const std::vector<T> values = fill_values<T>(value, img->num_channels(), what);
+				std::vector<py::ssize_t> shape{ ceil_div(height, step_y), ceil_div(width, step_x) };
+				if (!single) shape.insert(shape.begin(), static_cast<py::ssize_t>(regions.size()));
+				const uint8_t* m = masks.is_none() ? nullptr : device_mask(masks, shape, what);
+				if (img->num_channels()) img->channel(0).check_regions(regions);
+				if (regions.empty() || width == 0 || height == 0) return 0;
+				wait_for(stream);
+				if (m) img->fill_regions(std::span<const compressed::region>(regions), std::span<const T>(values), m);
+				else img->fill_regions(std::span<const compressed::region>(regions), std::span<const T>(values));
+				return 0;
+			});
+		}
 		// arrays: (N, C, h', w') in device memory (pixels: (N, C)), region k from (xs[k], ys[k]) of every channel; later regions win
 		// (dtype=: converted in the patch launch; interleaved: (N, h', w', C) -- pixels are (N, C) either way)
 		void set_regions(const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream, py::ssize_t step_x,
@@ -1189,10 +1397,20 @@ PYBIND11_MODULE(compressed_image, m)
 		.def("get_pixels", [](const Channel& c, const py::object& xs, const py::object& ys) { return c.get_regions(xs, ys, 1, 1, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"))
 		.def("__getitem__", &Channel::getitem, py::arg("key"))
-		.def("set_region", &Channel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("set_regions", [](Channel& c, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy) {
-				c.set_regions(xs, ys, arrays, sx, sy, false); },
-			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_region", [](Channel& c, py::ssize_t x, py::ssize_t y, const py::array& array, py::ssize_t sx, py::ssize_t sy, const py::object& mask) {
+				if (mask.is_none()) c.set_region(x, y, array, sx, sy);
+				else c.set_regions_masked(py::make_tuple(x), py::make_tuple(y), array, sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("array"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("set_regions", [](Channel& c, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy, const py::object& masks) {
+				if (masks.is_none()) c.set_regions(xs, ys, arrays, sx, sy, false);
+				else c.set_regions_masked(xs, ys, arrays, sx, sy, masks, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("masks") = py::none())
+		.def("fill_region", [](Channel& c, py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h, const py::object& value, py::ssize_t sx, py::ssize_t sy,
+				const py::object& mask) { check_region_args(x, y, w, h); c.fill_regions(py::make_tuple(x), py::make_tuple(y), w, h, value, sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("fill_regions", [](Channel& c, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& value, py::ssize_t sx,
+				py::ssize_t sy, const py::object& masks) { c.fill_regions(xs, ys, w, h, value, sx, sy, masks, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("masks") = py::none())
 		.def("set_pixels", [](Channel& c, const py::object& xs, const py::object& ys, const py::array& values) { c.set_regions(xs, ys, values, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"), py::arg("values"))
 		.def("__setitem__", &Channel::setitem, py::arg("key"), py::arg("value"));
@@ -1219,10 +1437,21 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("step_x") = 1, py::arg("step_y") = 1)
 		.def("get_pixels", [](const Image& i, const py::object& xs, const py::object& ys) { return i.get_regions(xs, ys, 1, 1, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"))
-		.def("set_region", &Image::set_region, py::arg("x"), py::arg("y"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
-		.def("set_regions", [](Image& i, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy) {
-				i.set_regions(xs, ys, arrays, sx, sy, false); },
-			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1)
+		.def("set_region", [](Image& i, py::ssize_t x, py::ssize_t y, const std::vector<py::array>& arrays, py::ssize_t sx, py::ssize_t sy, const py::object& mask) {
+				if (mask.is_none()) { i.set_region(x, y, arrays, sx, sy); return; }
+				if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+				i.set_regions_masked(py::make_tuple(x), py::make_tuple(y), py::cast(arrays), sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("set_regions", [](Image& i, const py::object& xs, const py::object& ys, const py::array& arrays, py::ssize_t sx, py::ssize_t sy, const py::object& masks) {
+				if (masks.is_none()) i.set_regions(xs, ys, arrays, sx, sy, false);
+				else i.set_regions_masked(xs, ys, arrays, sx, sy, masks, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("masks") = py::none())
+		.def("fill_region", [](Image& i, py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h, const py::object& value, py::ssize_t sx, py::ssize_t sy,
+				const py::object& mask) { check_region_args(x, y, w, h); i.fill_regions(py::make_tuple(x), py::make_tuple(y), w, h, value, sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("fill_regions", [](Image& i, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& value, py::ssize_t sx,
+				py::ssize_t sy, const py::object& masks) { i.fill_regions(xs, ys, w, h, value, sx, sy, masks, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("masks") = py::none())
 		.def("set_pixels", [](Image& i, const py::object& xs, const py::object& ys, const py::array& values) { i.set_regions(xs, ys, values, 1, 1, true); },
 			py::arg("xs"), py::arg("ys"), py::arg("values"))
 		.def("get_channel_index", [](const Image& i, const std::string& name) { return i.visit([&](auto& img) { return img->get_channel_offset(name); }); }, py::arg("channelname"))
@@ -1297,12 +1526,20 @@ PYBIND11_MODULE(compressed_image, m)
 			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
 		.def("__getitem__", &DeviceChannel::getitem, py::arg("key"))
 		.def("set_region", &DeviceChannel::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
-			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0)
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0,
+			py::arg("mask") = py::none())
 		.def("set_regions", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
-				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset) {
-				c.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset); },
+				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset, const py::object& masks) {
+				c.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset, masks); },
 			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1,
-			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0)
+			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0, py::arg("masks") = py::none())
+		.def("fill_region", &DeviceChannel::fill_region, py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("value"),
+			py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("fill_regions", [](DeviceChannel& c, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& value,
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy, const py::object& masks) {
+				c.fill_regions(xs, ys, w, h, value, stream, sx, sy, masks); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("stream") = std::nullopt,
+			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("masks") = py::none())
 		.def("set_pixels", [](DeviceChannel& c, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream,
 				const py::object& dtype, const py::object& scale, const py::object& offset) {
 				c.set_regions(xs, ys, values, stream, 1, 1, true, dtype, scale, offset); },
@@ -1338,14 +1575,31 @@ PYBIND11_MODULE(compressed_image, m)
 				return i.get_regions(xs, ys, 1, 1, out, stream, 1, 1, true, dtype, scale, offset); },
 			py::arg("xs"), py::arg("ys"), py::arg("out") = py::none(), py::arg("stream") = std::nullopt, py::arg("dtype") = py::none(),
 			py::arg("scale") = 1.0, py::arg("offset") = 0.0)
-		.def("set_region", &DeviceImage::set_region, py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
+		.def("set_region", [](DeviceImage& i, py::ssize_t x, py::ssize_t y, const py::object& array, std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy,
+				const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved, const py::object& mask) {
+				if (mask.is_none()) { i.set_region(x, y, array, stream, sx, sy, dtype, scale, offset, interleaved); return; }
+				if (!dtype.is_none() || interleaved) throw py::value_error("set_region: mask= cannot be combined with dtype= or interleaved= (masked typed writes are not built)");
+				if (x < 0 || y < 0) throw py::value_error("region coordinates must be >= 0");
+				i.set_regions_masked(py::make_tuple(x), py::make_tuple(y), array, stream, sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("array"), py::arg("stream") = std::nullopt,
 			py::arg("step_x") = 1, py::arg("step_y") = 1, py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0,
-			py::arg("interleaved") = false)
+			py::arg("interleaved") = false, py::arg("mask") = py::none())
 		.def("set_regions", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& arrays, std::optional<uintptr_t> stream,
-				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved) {
-				i.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset, interleaved); },
+				py::ssize_t sx, py::ssize_t sy, const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved, const py::object& masks) {
+				if (masks.is_none()) { i.set_regions(xs, ys, arrays, stream, sx, sy, false, dtype, scale, offset, interleaved); return; }
+				if (!dtype.is_none() || interleaved) throw py::value_error("set_regions: masks= cannot be combined with dtype= or interleaved= (masked typed writes are not built)");
+				i.set_regions_masked(xs, ys, arrays, stream, sx, sy, masks, false); },
 			py::arg("xs"), py::arg("ys"), py::arg("arrays"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1, py::arg("step_y") = 1,
-			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0, py::arg("interleaved") = false)
+			py::arg("dtype") = py::none(), py::arg("scale") = 1.0, py::arg("offset") = 0.0, py::arg("interleaved") = false, py::arg("masks") = py::none())
+		.def("fill_region", [](DeviceImage& i, py::ssize_t x, py::ssize_t y, py::ssize_t w, py::ssize_t h, const py::object& value, std::optional<uintptr_t> stream,
+				py::ssize_t sx, py::ssize_t sy, const py::object& mask) {
+				check_region_args(x, y, w, h); i.fill_regions(py::make_tuple(x), py::make_tuple(y), w, h, value, stream, sx, sy, mask, true); },
+			py::arg("x"), py::arg("y"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1,
+			py::arg("step_y") = 1, py::arg("mask") = py::none())
+		.def("fill_regions", [](DeviceImage& i, const py::object& xs, const py::object& ys, py::ssize_t w, py::ssize_t h, const py::object& value,
+				std::optional<uintptr_t> stream, py::ssize_t sx, py::ssize_t sy, const py::object& masks) { i.fill_regions(xs, ys, w, h, value, stream, sx, sy, masks, false); },
+			py::arg("xs"), py::arg("ys"), py::arg("width"), py::arg("height"), py::arg("value"), py::arg("stream") = std::nullopt, py::arg("step_x") = 1,
+			py::arg("step_y") = 1, py::arg("masks") = py::none())
 		.def("set_pixels", [](DeviceImage& i, const py::object& xs, const py::object& ys, const py::object& values, std::optional<uintptr_t> stream,
 				const py::object& dtype, const py::object& scale, const py::object& offset, bool interleaved) {
 				i.set_regions(xs, ys, values, stream, 1, 1, true, dtype, scale, offset, interleaved); },

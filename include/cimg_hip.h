@@ -356,6 +356,45 @@ int cimg_update_windows_typed_device(cimg_engine* e, const cimg_cparams* p, int3
                                      const int32_t* blocksize, const int32_t* destsize, int32_t nwindows,
                                      const cimg_window_typed* w, const void* d_src, void* d_new, const int64_t* new_off,
                                      int32_t* new_cbytes, int32_t* status);
+/* Masked and constant window writes: np.copyto(view, src_or_scalar, where=mask) on compressed planes.  The windows are
+ * cimg_window_strided with flags, a mask and a value.  For element c of window row r: if the window has CIMG_WM_MASK and the byte at
+ * mask + mask_off + r * mask_pitch + c is 0, the plane element keeps its value (any nonzero byte writes); otherwise the element
+ * becomes `value` (the first `typesize` bytes) under CIMG_WM_CONST, or the source element at src + out_off + r * out_pitch +
+ * c * typesize without it.  Windows apply in call order: a later window wins on every byte it actually writes; where its mask is
+ * 0 the earlier window's byte stands.  Every touched chunk's new bytes equal what cimg_compress_batch_* with `p` gives for the
+ * decoded pixels with the windows written in (trunc-prec included: a constant is truncated like any written pixel).
+ * The checks, status[], the return value, locking, the routes (splice; whole for zstd, wide blocks, memcpyed and special chunks) and
+ * cimg_engine_update_stats are those of cimg_update_windows_strided_*; a call whose windows all have flags == 0 gives that call's
+ * new chunks, new_cbytes, status, return value and stats.  The patch launch is cimg_update_patch_masked
+ * (CIMG_K_UPDATE_PATCH_MASKED).  A block counts as covered -- not staged -- only through windows with col_pitch 1 and no mask,
+ * constant or not; a masked window never covers.  A block whose mask bytes are all 0 is still a touched block: staged, re-encoded
+ * and byte for byte the old block -- no call reads the mask on the host to prune.  The host call uploads the touched chunks, the
+ * rows of the windows without CIMG_WM_CONST and the mask rows of the windows with CIMG_WM_MASK, nothing else (bytes_uploaded says
+ * so): a constant unmasked call uploads chunks only.
+ * Added refusals (BLOSC2_ERROR_INVALID_PARAM before status[] or new_cbytes[] are touched, nothing runs): unknown flag bits;
+ * CIMG_WM_CONST with typesize > 8; a masked window with mask_off < 0, mask_pitch < 0, or height > 1 and mask_pitch < width; a NULL
+ * mask pointer while some window has CIMG_WM_MASK; a NULL source pointer while some window lacks CIMG_WM_CONST.  The source pointer
+ * may be NULL when every window is constant, the mask pointer when none is masked. */
+enum { CIMG_WM_CONST = 1, CIMG_WM_MASK = 2 };
+typedef struct cimg_window_masked {
+    int32_t chunk_first, chunk_count;
+    int64_t origin, row_pitch, col_pitch;   /* plane side: as cimg_window_strided */
+    int32_t width, height;
+    int64_t out_off, out_pitch;             /* SOURCE rows (dense, width * typesize bytes); ignored with CIMG_WM_CONST */
+    int64_t mask_off, mask_pitch;           /* MASK: one byte an element, row r at mask + mask_off + r * mask_pitch; ignored without CIMG_WM_MASK */
+    int32_t flags;                          /* CIMG_WM_* */
+    int32_t pad_;
+    uint8_t value[8];                       /* CIMG_WM_CONST: the element's bytes, the first `typesize` used */
+} cimg_window_masked;
+int cimg_update_windows_masked_device(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* d_comp,
+                                      const int64_t* comp_off, const int32_t* comp_size, const int32_t* nbytes,
+                                      const int32_t* blocksize, const int32_t* destsize, int32_t nwindows,
+                                      const cimg_window_masked* w, const void* d_src, const void* d_mask, void* d_new,
+                                      const int64_t* new_off, int32_t* new_cbytes, int32_t* status);
+int cimg_update_windows_masked_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+                                    const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_masked* w,
+                                    const void* h_src, const void* h_mask, cimg_alloc_fn alloc, void* user, void** new_chunks,
+                                    int32_t* new_cbytes, int32_t* status);
 /* The last update call on this engine: blocks staged from their old streams, blocks re-encoded on the splice route, chunks decoded
  * and compressed whole, bytes uploaded (host call only: touched chunks and window bytes).  Any pointer may be NULL. */
 void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* blocks_encoded, int64_t* chunks_whole,
@@ -445,7 +484,9 @@ enum { CIMG_K_ENCODE = 0, CIMG_K_LAYOUT = 1, CIMG_K_EMIT = 2, CIMG_K_DECODE = 3,
        /* the window launch of cimg_decompress_windows_typed_device */
        CIMG_K_DECODE_WINDOW_TYPED = 27,
        /* the patch launch of cimg_update_windows_typed_device */
-       CIMG_K_UPDATE_PATCH_TYPED = 28, CIMG_K_COUNT = 29 };
+       CIMG_K_UPDATE_PATCH_TYPED = 28,
+       /* the patch launch of cimg_update_windows_masked_device / _host */
+       CIMG_K_UPDATE_PATCH_MASKED = 29, CIMG_K_COUNT = 30 };
 /* on = 0: off; on = n > 0: the kernels of every n-th batch call are bracketed by events (1 = every call).  Each
  * event record costs about 5 us of stream time, so a throughput run samples (bench.py: every 4th batch). */
 void cimg_engine_enable_timing(cimg_engine* e, int on);

@@ -44,6 +44,12 @@ first) that writes profiles/typed/diag_windows_typed_write.json:
       set_regions.  The two routes alternate in one process; kernel time (every launch of the shared engine, HIP events, plus torch
       events around torch's part) and wall time, medians of REPS after a warm-up.  Then the patch launch alone on an all-identity
       call: set_regions(dtype=uint8) (cimg_update_patch_typed) against set_regions (cimg_update_patch_strided), same windows.
+Masked leg, a process of its own (`python tools/diag_windows.py --masked-leg [--out file]`, torch first) that
+writes profiles/masked/diag_windows_masked.json:
+  (10) DeviceChannel.fill_region against set_region with a materialised constant tensor, and set_region(mask=) under a 50 % mask
+      against get_region + torch.where + set_region; the same on Channel with numpy arrays (np.full, np.where): a 1024^2 region of a 16384^2 float32 lz4 plane, and the whole of a 4096^2 uint8
+      plane.  The routes alternate in one process; wall time and kernel time (every launch of the shared engine, HIP events, plus
+      torch events around torch's part), medians of REPS after a warm-up, with min and max.
 Prints one JSON line.  usage: python tools/diag_windows.py [--out file]"""
 import importlib.util
 import json
@@ -58,7 +64,8 @@ GROUPED_LEG = "--grouped-leg" in sys.argv
 WRITE_STRIDED_LEG = "--write-strided-leg" in sys.argv
 TYPED_LEG = "--typed-leg" in sys.argv
 TYPED_WRITE_LEG = "--typed-write-leg" in sys.argv
-if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG or TYPED_LEG or TYPED_WRITE_LEG:
+MASKED_LEG = "--masked-leg" in sys.argv
+if STRIDED_LEG or GROUPED_LEG or WRITE_STRIDED_LEG or TYPED_LEG or TYPED_WRITE_LEG or MASKED_LEG:
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,6 +234,95 @@ def typed_write_leg():
     out["crops256_224_u8_identity"] = r
     return out
 
+
+def masked_leg():
+    """(10): fill_region and set_region(mask=) of DeviceChannel against the compositions they replace"""
+    import ctypes as C
+    path = os.path.join(ROOT, "compressed-image_amd", "compressed_image" + sysconfig.get_config_var("EXT_SUFFIX"))
+    spec_m = importlib.util.spec_from_file_location("compressed_image", path)
+    ci = importlib.util.module_from_spec(spec_m)
+    spec_m.loader.exec_module(ci)
+    L = hip.load()
+    L.cimg_shared_engine.restype = C.c_void_p
+    se = hip.Engine.__new__(hip.Engine)                    # the module's engine, for its kernel times
+    se.handle = C.c_void_p(L.cimg_shared_engine())
+    every = range(len(hip.KERNELS))
+    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def alternating(old, new, old_has_torch):
+        old(); new()
+        torch.cuda.synchronize()
+        se.enable_timing(1)
+        rows = {"old": ([], []), "new": ([], [])}
+        for _ in range(REPS):
+            for name, f in (("old", old), ("new", new)):
+                se.reset_timing()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                rows[name][0].append((time.perf_counter() - t) * 1e6)
+                k = sum(se.kernel_time(kid)[0] for kid in every) * 1e3
+                rows[name][1].append(k + (ev_a.elapsed_time(ev_b) * 1e3 if name == "old" and old_has_torch else 0.0))
+        se.enable_timing(0)
+        return {name: dict(wall_us=round(float(np.median(wl)), 1), wall_min_us=round(float(np.min(wl)), 1), wall_max_us=round(float(np.max(wl)), 1),
+                           kernel_us=round(float(np.median(kl)), 1)) for name, (wl, kl) in rows.items()}
+
+    out = {}
+    rng = np.random.default_rng(10)
+    for name, dtype, m, (x, y, w, h) in (("f32_16384_region1024", np.float32, 16384, (5000, 7000, 1024, 1024)), ("u8_4096_whole", np.uint8, 4096, (0, 0, 4096, 4096))):
+        host_plane = synth.tiled_channel(dtype, m, m)
+        # Channel (host-resident chunks, numpy arrays): the old routes cross PCIe with h x w pixels, the fill with none
+        hc_old = ci.Channel(host_plane, m, m)
+        hc_new = ci.Channel(host_plane, m, m)
+        r = alternating(lambda: hc_old.set_region(x, y, np.full((h, w), 7, dtype)), lambda: hc_new.fill_region(x, y, w, h, 7), False)
+        r["pixels_equal"] = bool(np.array_equal(hc_old.get_region(x, y, w, h), hc_new.get_region(x, y, w, h)))
+        out["channel_fill_" + name] = r
+        hmask = rng.random((h, w)) < 0.5
+        hnew = np.ascontiguousarray(hc_old.get_region(x, y, w, h)[::-1])
+        r = alternating(lambda: hc_old.set_region(x, y, np.where(hmask, hnew, hc_old.get_region(x, y, w, h))),
+                        lambda: hc_new.set_region(x, y, hnew, mask=hmask), False)
+        r["pixels_equal"] = bool(np.array_equal(hc_old.get_region(x, y, w, h), hc_new.get_region(x, y, w, h)))
+        out["channel_masked_" + name] = r
+        del hc_old, hc_new
+        plane = torch.from_numpy(host_plane).cuda()
+        del host_plane
+        ch_old = ci.DeviceChannel(plane, m, m)
+        ch_new = ci.DeviceChannel(plane, m, m)
+        del plane
+        tdt = torch.float32 if dtype is np.float32 else torch.uint8
+        # fill: the parent's only way materialises h x w copies of the scalar
+        def old_fill():
+            ev_a.record()
+            c = torch.full((h, w), 7, dtype=tdt, device="cuda")
+            ev_b.record()
+            ch_old.set_region(x, y, c)
+        r = alternating(old_fill, lambda: ch_new.fill_region(x, y, w, h, 7), True)
+        r["pixels_equal"] = bool(torch.equal(torch.as_tensor(ch_old.get_region(x, y, w, h), device="cuda"), torch.as_tensor(ch_new.get_region(x, y, w, h), device="cuda")))
+        out["fill_" + name] = r
+        # masked write: get_region + where + set_region against set_region(mask=)
+        mask = torch.from_numpy(rng.random((h, w)) < 0.5).cuda()
+        new_px = torch.as_tensor(ch_old.get_region(x, y, w, h), device="cuda").flip(0).contiguous()
+        def old_masked():
+            cur = torch.as_tensor(ch_old.get_region(x, y, w, h), device="cuda")
+            ev_a.record()
+            mixed = torch.where(mask, new_px, cur)
+            ev_b.record()
+            ch_old.set_region(x, y, mixed)
+        r = alternating(old_masked, lambda: ch_new.set_region(x, y, new_px, mask=mask), True)
+        r["pixels_equal"] = bool(torch.equal(torch.as_tensor(ch_old.get_region(x, y, w, h), device="cuda"), torch.as_tensor(ch_new.get_region(x, y, w, h), device="cuda")))
+        out["masked_" + name] = r
+        del ch_old, ch_new
+    return out
+
+
+if MASKED_LEG:
+    line = json.dumps(masked_leg())
+    print("MASKED " + line)
+    dst = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "masked", "diag_windows_masked.json")
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    open(dst, "w").write(line + "\n")
+    sys.exit(0)
 
 if TYPED_WRITE_LEG:
     line = json.dumps(typed_write_leg())
