@@ -213,6 +213,9 @@ def load():
     L.cimg_decompress_batch_device_begin.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_decompress_batch_device_fetch.argtypes = [vp, vp]
     L.cimg_compress_batch_host.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.cimg_compress_batch_host_begin.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp]
+    L.cimg_compress_batch_host_fetch.argtypes = [vp, C.c_int32, vp, vp]
+    L.cimg_compress_batch_host_packed.argtypes = [vp, C.POINTER(CParams), C.c_int32, vp, vp, vp, vp, vp, _ALLOC_FN, vp, vp]
     L.cimg_decompress_batch_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.cimg_decompress_batch_host_sized.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.cimg_device_malloc.argtypes = [vp, C.c_size_t]
@@ -419,6 +422,16 @@ class Engine:
                                                               d_raw, _ptr(raw_off)))
         return nbytes.size
 
+    def decompress_device_begin_sized(self, d_comp, comp_off, comp_size, nbytes, blocksize, d_raw, raw_off, check=True):
+        """cimg_decompress_batch_device_begin_sized: _begin for callers that know how many bytes each compressed buffer holds"""
+        raw_off, comp_off, comp_size, nbytes, blocksize = _i64(raw_off), _i64(comp_off), _i32(comp_size), _i32(nbytes), _i32(blocksize)
+        rc = load().cimg_decompress_batch_device_begin_sized(self.handle, nbytes.size, d_comp, _ptr(comp_off), _ptr(comp_size), _ptr(nbytes),
+                                                             _ptr(blocksize), d_raw, _ptr(raw_off))
+        if check:
+            self._check(rc)
+            return nbytes.size
+        return rc, nbytes.size
+
     def decompress_device_fetch(self, nchunks, check=True):
         status = np.zeros(nchunks, np.int32)
         rc = load().cimg_decompress_batch_device_fetch(self.handle, _ptr(status))
@@ -495,6 +508,68 @@ class Engine:
         self._check(load().cimg_compress_batch_host(self.handle, C.byref(p), nbytes.size, _ptr(raw), _ptr(raw_off), _ptr(nbytes),
                                                     _ptr(comp), _ptr(comp_off), _ptr(destsize), _ptr(cbytes)))
         return [comp[o:o + max(c, 0)].tobytes() for o, c in zip(comp_off, cbytes)]
+
+    # the same in two steps, in one call into the caller's allocator, and from interleaved pixels (include/cimg_hip.h); with
+    # check=False each returns its return code first and raises nothing
+    def compress_host_begin(self, p, raw, nbytes, destsize, check=True):
+        """cimg_compress_batch_host_begin: the chunks stay in the engine's staging area.  Returns cbytes."""
+        raw = np.ascontiguousarray(raw).view(np.uint8).ravel()
+        nbytes, destsize = _i32(nbytes), _i32(destsize)
+        raw_off = _i64(np.concatenate([[0], np.cumsum(nbytes[:-1], dtype=np.int64)]))
+        cbytes = np.zeros(nbytes.size, np.int32)
+        rc = load().cimg_compress_batch_host_begin(self.handle, C.byref(p), nbytes.size, _ptr(raw), _ptr(raw_off), _ptr(nbytes), _ptr(destsize),
+                                                   _ptr(cbytes))
+        if check:
+            self._check(rc)
+            return cbytes
+        return rc, cbytes
+
+    def compress_host_fetch(self, cbytes, check=True):
+        """cimg_compress_batch_host_fetch of the batch whose _begin reported `cbytes`.  Returns list of chunk bytes (b'' = did not fit)."""
+        cbytes = _i32(cbytes)
+        room = np.maximum(cbytes, 0).astype(np.int64) + 64
+        comp_off = _i64(np.concatenate([[0], np.cumsum(room[:-1])]))
+        comp = np.zeros(int(room.sum()), np.uint8)
+        rc = load().cimg_compress_batch_host_fetch(self.handle, cbytes.size, _ptr(comp), _ptr(comp_off))
+        chunks = [comp[o:o + max(c, 0)].tobytes() for o, c in zip(comp_off, cbytes)]
+        if check:
+            self._check(rc)
+            return chunks
+        return rc, chunks
+
+    def compress_host_packed(self, p, raw, nbytes, destsize, check=True):
+        """cimg_compress_batch_host_packed with an allocator that hands out plain host memory.  Returns list of chunk bytes."""
+        raw = np.ascontiguousarray(raw).view(np.uint8).ravel()
+        nbytes, destsize = _i32(nbytes), _i32(destsize)
+        raw_off = _i64(np.concatenate([[0], np.cumsum(nbytes[:-1], dtype=np.int64)]))
+        cbytes = np.zeros(nbytes.size, np.int32)
+        ptrs = (C.c_void_p * max(nbytes.size, 1))()
+        keep = []
+
+        def alloc(_user, n):
+            b = C.create_string_buffer(max(int(n), 1))
+            keep.append(b)
+            return C.addressof(b)
+        rc = load().cimg_compress_batch_host_packed(self.handle, C.byref(p), nbytes.size, _ptr(raw), _ptr(raw_off), _ptr(nbytes), _ptr(destsize),
+                                                    _ptr(cbytes), _ALLOC_FN(alloc), None, ptrs)
+        chunks = [C.string_at(ptrs[i], int(cbytes[i])) if rc == 0 and ptrs[i] and cbytes[i] > 0 else b"" for i in range(nbytes.size)]
+        if check:
+            self._check(rc)
+            return chunks
+        return rc, chunks
+
+    def compress_host_interleaved_begin(self, p, nchannels, npixels, interleaved, raw_off, nbytes, destsize, check=True):
+        """cimg_compress_batch_host_interleaved_begin: raw_off / nbytes address the PLANAR layout (channel c at c * plane_stride,
+        plane_stride = npixels * typesize rounded up to 16).  Returns cbytes; compress_host_fetch delivers the chunks."""
+        il = np.ascontiguousarray(interleaved).view(np.uint8).ravel()
+        raw_off, nbytes, destsize = _i64(raw_off), _i32(nbytes), _i32(destsize)
+        cbytes = np.zeros(nbytes.size, np.int32)
+        rc = load().cimg_compress_batch_host_interleaved_begin(self.handle, C.byref(p), nchannels, npixels, _ptr(il), nbytes.size, _ptr(raw_off),
+                                                               _ptr(nbytes), _ptr(destsize), _ptr(cbytes))
+        if check:
+            self._check(rc)
+            return cbytes
+        return rc, cbytes
 
     def decompress_host(self, chunks, check=True):
         """chunks: list of bytes.  Returns (list of uint8 arrays, status array)."""

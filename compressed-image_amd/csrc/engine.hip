@@ -1945,6 +1945,7 @@ int compress_host_pipeline(cimg_engine* e, const cimg_cparams* p, int32_t nchunk
     e->fetch_off.clear();
     if (!p || !h_raw || !raw_off || !nbytes || !destsize || !cbytes) return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
+    e->cflight_chunks = -1;                                // the launches below reuse h_out: a pending cimg_compress_batch_device_begin is void
     // pack pixels back to back (16-byte aligned) and give every chunk its full destsize on the device
     std::vector<int64_t> d_raw_off((size_t)nchunks), d_comp_off((size_t)nchunks);
     int64_t raw_total = 0, comp_total = 0;
@@ -2055,6 +2056,7 @@ int cimg_compress_batch_host_interleaved_begin(cimg_engine* e, const cimg_cparam
     if (nchunks <= 0) return 0;
     if (!p || !h_interleaved || !raw_off || !nbytes || !destsize || !cbytes) return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
+    e->cflight_chunks = -1;                                // the launch below reuses h_out: a pending cimg_compress_batch_device_begin is void
     const int ts = p->typesize;
     if (nchannels < 1 || npixels <= 0 || (ts != 1 && ts != 2 && ts != 4 && ts != 8)) return e->fail(ERR_INVALID_PARAM, "interleaved batch: %d channels of %d-byte elements are not supported", nchannels, ts);
     const int64_t plane_stride = (npixels * ts + 15) & ~15ll;
@@ -2133,6 +2135,7 @@ int cimg_decompress_batch_host_sized(cimg_engine* e, int32_t nchunks, const void
     if (!h_comp || !h_raw || !comp_off || !raw_off || !raw_capacity) return e->fail(ERR_INVALID_PARAM, "null argument");
     (void)hipSetDevice(e->device);
     e->fetch_off.clear();                                  // the staging area is reused: a pending _fetch is void
+    e->dflight_open = false;                               // the launches below reuse dflight and h_dec: so is a pending cimg_decompress_batch_device_begin
     const uint8_t* hc = (const uint8_t*)h_comp;
     std::vector<int64_t> d_comp_off((size_t)nchunks), d_raw_off((size_t)nchunks);
     std::vector<int32_t> nb((size_t)nchunks), bs((size_t)nchunks), cb((size_t)nchunks);

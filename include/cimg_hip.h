@@ -93,8 +93,23 @@ int cimg_decompress_batch_device(cimg_engine* e, int32_t nchunks,
  * _begin may follow the compress _begin of the chunks it reads directly (stream order: it sees them finished; nbytes /
  * blocksize are the caller's, nothing of the compress results is needed on the host) -- so the host's share of a round
  * trip (planning, launches, the wait) hides behind the kernels instead of leaving the GPU idle between the calls.
- * Each _fetch refers to the most recent _begin of its kind; a plain batch call of the same kind in between invalidates
- * it (error).  Threads sharing an engine hold cimg_engine_lock from _begin to _fetch. */
+ * Each _fetch refers to the most recent _begin of its kind and delivers it once.  The engine keeps ONE result area per kind, so
+ * a call in between that does work of the same kind overwrites it and voids the pending _begin (its _fetch then fails with
+ * BLOSC2_ERROR_INVALID_PARAM and writes nothing):
+ *   - a pending compress _begin is voided by every call that compresses: cimg_compress_batch_device, the host-resident
+ *     compress calls (cimg_compress_batch_host, _host_begin, _host_packed, _host_interleaved_begin),
+ *     cimg_compress_batch_device_packed_begin and the window writes (cimg_update_windows_*);
+ *   - a pending decompress _begin by every call that decompresses: cimg_decompress_batch_device(_sized),
+ *     cimg_decompress_batch_host(_sized), the window reads (cimg_decompress_windows_*) and the window writes.
+ * A call of the other kind leaves it valid, and so do the calls that do neither (deinterleave, interleave, pack, wait_stream,
+ * timing, stamps).  A _begin ALWAYS replaces what its slot held, also when it is refused or has nchunks <= 0 (then a batch of no
+ * chunks is in flight: a _fetch naming the earlier count fails).  Of the other calls, only these refused ones are promised to
+ * void nothing: a plain device call (cimg_compress_batch_device, cimg_decompress_batch_device(_sized)) with nchunks <= 0 or a
+ * missing array argument, and a host-resident call with nchunks <= 0 or without its destination (h_comp / comp_off, alloc /
+ * chunk_ptr).  Any other refused call -- by the planner, by a header check, for a missing p or size array of a host-resident
+ * call, which has claimed the staging area by then -- may void like a call of its kind.  A compress _fetch that names
+ * another chunk count than the batch in flight fails and leaves it in flight.
+ * Threads sharing an engine hold cimg_engine_lock from _begin to _fetch. */
 int cimg_compress_batch_device_begin(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
                                      const void* d_raw, const int64_t* raw_off, const int32_t* nbytes,
                                      void* d_comp, const int64_t* comp_off, const int32_t* destsize);
@@ -142,7 +157,15 @@ int cimg_compress_batch_host(cimg_engine* e, const cimg_cparams* p, int32_t nchu
 /* The same in two steps, for host code that wants to allocate the chunks' final storage with their exact sizes:
  * _begin uploads and compresses (the chunks stay in the engine's device staging area) and reports cbytes[];
  * _fetch copies chunk i (cbytes[i] bytes) to h_comp + comp_off[i] and synchronizes.  _fetch refers to the most
- * recent _begin on this engine; any other batch call in between invalidates it (error). */
+ * recent _begin on this engine that staged a batch -- this one, _host_interleaved_begin or
+ * cimg_compress_batch_device_packed_begin: they share one staging area -- and delivers it once.  A call in between that
+ * reuses the staging area voids it (the _fetch fails with BLOSC2_ERROR_INVALID_PARAM and writes nothing): every
+ * host-resident batch call (compress or decompress), every host-resident window read or write, and
+ * cimg_compress_batch_device_packed_begin.  The device-resident calls (cimg_compress_batch_device and its _begin / _fetch,
+ * cimg_decompress_batch_device*, the device window reads and writes, pack, interleave, deinterleave) do not touch the staging
+ * area: the staged chunks are intact and the _fetch stays valid.  A staging _begin always replaces the staged batch, also with
+ * nchunks <= 0 or when it is refused (nothing is staged then); which other refused calls void nothing is said with the device
+ * pair above.  A _fetch that names another chunk count than the staged batch fails and leaves it staged. */
 int cimg_compress_batch_host_begin(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
                                    const void* h_raw, const int64_t* raw_off, const int32_t* nbytes,
                                    const int32_t* destsize, int32_t* cbytes);
@@ -292,7 +315,10 @@ int cimg_decompress_windows_typed_device(cimg_engine* e, int32_t nchunks, const 
  * like the chunk's own --, split decision, effective blocksize for its nbytes) and every
  * destsize[i] >= 32.  A damaged touched chunk gets its decode error in status[i] and new_cbytes[i] = 0; the others are still
  * written; the call returns the first failing code.  clevel is not in the header: passing the one the chunks were made with is
- * the caller's job, as it is for compress. */
+ * the caller's job, as it is for compress.
+ * Every window write takes the engine's lock, decodes and encodes, and so voids a pending cimg_decompress_batch_device_begin AND a
+ * pending cimg_compress_batch_device_begin (their _fetch then fails); the host calls reuse the staging area as well and void a
+ * pending cimg_compress_batch_host_begin / _device_packed_begin. */
 /* Device-resident chunks in, device-resident new chunks out.  Chunk i is read at d_comp + comp_off[i] (comp_size may be NULL);
  * if some window row meets it, its new form is written to d_new + new_off[i] (capacity destsize[i]) and new_cbytes[i] > 0;
  * otherwise new_cbytes[i] = 0 and neither area is touched.  d_new must not overlap the input chunks. */
@@ -407,8 +433,9 @@ void cimg_engine_update_stats(cimg_engine* e, int64_t* blocks_decoded, int64_t* 
  * moves chunk i (cbytes[i] bytes; nothing for a chunk that did not fit) to d_dst + dst_off[i] with one launch of the pack kernel.
  * The chunk bytes are those cimg_compress_batch_device writes for the same input and parameters.  _fetch refers to the most recent
  * _begin (of this kind or of the host kind: both leave their chunks in the same staging area); any other batch call that reuses the
- * staging area (the host-resident calls) voids it, and _fetch then fails with BLOSC2_ERROR_INVALID_PARAM.  Both return after the
- * engine's stream has been synchronised. */
+ * staging area (the host-resident calls) voids it, and _fetch then fails with BLOSC2_ERROR_INVALID_PARAM.  _begin is a compress
+ * call: it voids a pending cimg_compress_batch_device_begin like any other.  Both return after the engine's stream has been
+ * synchronised. */
 int cimg_compress_batch_device_packed_begin(cimg_engine* e, const cimg_cparams* p, int32_t nchunks,
                                             const void* d_raw, const int64_t* raw_off, const int32_t* nbytes, const int32_t* destsize,
                                             int32_t* cbytes);

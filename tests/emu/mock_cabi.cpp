@@ -91,6 +91,23 @@ int cimg_compress_batch_host_fetch(cimg_engine* e, int32_t n, void* h_comp, cons
     return 0;
 }
 
+// For the mocks of the other host-resident calls (mock_window*.cpp, mock_window_write*.cpp, mock_device.cpp), which do not see this
+// file's engine: the engine reuses its staging area in every host-resident call, so a staged batch is void after one of them ...
+void cimg_mock_void_staged(cimg_engine* e)
+{
+    if (!e) return;
+    LOCK_ENGINE(e);
+    e->off.clear();
+}
+// ... and the packed _fetch moves whatever batch is staged, begun by the host kind or by its own: 0 and its sizes, or -12
+int cimg_mock_staged_sizes(cimg_engine* e, int32_t n, int32_t* len)
+{
+    LOCK_ENGINE(e);
+    if (n <= 0 || (size_t)n != e->off.size()) return -12;
+    for (int i = 0; i < n; i++) len[i] = e->len[(size_t)i];
+    return 0;
+}
+
 // (the engine cuts a batch into groups and asks for a block per group: here two groups, so that the host mirror meets chunks in
 // more than one block)
 int cimg_compress_batch_host_packed(cimg_engine* e, const cimg_cparams* p, int32_t n, const void* h_raw, const int64_t* raw_off,
@@ -142,13 +159,13 @@ int cimg_decompress_batch_host_sized(cimg_engine* e, int32_t n, const void* h_co
 {
     LOCK_ENGINE(e);
     if (n <= 0) return 0;
+    e->off.clear();                                          // as the engine: the staging area is reused, a pending _fetch is void -- before the headers are looked at
     if (comp_size)
         for (int i = 0; i < n; i++) {
             int32_t cb = 0;
             if (comp_size[i] >= 16) memcpy(&cb, (const uint8_t*)h_comp + comp_off[i] + 12, 4);
             if (comp_size[i] < 32 || cb > comp_size[i]) { e->err = "chunk buffer shorter than its header says"; return -5; }
         }
-    e->off.clear();                                          // as the engine: the staging area is reused, a pending _fetch is void
     std::vector<int32_t> nb((size_t)n), bs((size_t)n), st((size_t)n, 0);
     for (int i = 0; i < n; i++) {
         const uint8_t* c = (const uint8_t*)h_comp + comp_off[i];

@@ -9,22 +9,16 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
+#include <vector>
 
 using namespace cimg;
 
 extern "C" int emu_decompress_batch(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* nbytes,
                                     const int32_t* blocksize, uint8_t* raw, const int64_t* raw_off, int32_t* status);
 
-namespace {
-
-// sizes of the batch the last _packed_begin of an engine left in its staging area (the staging area itself is mock_cabi.cpp's: the
-// chunks are moved out of it with cimg_compress_batch_host_fetch, whose bookkeeping also says when a pending fetch has been voided)
-std::mutex g_mu;
-std::map<cimg_engine*, std::vector<int32_t>> g_pending;
-
-}  // namespace
+// mock_cabi.cpp: the sizes of the batch staged by the last _begin -- of the host kind or of the packed kind, which share the staging
+// area as they do in the engine -- or -12 where none of n chunks is waiting
+extern "C" int cimg_mock_staged_sizes(cimg_engine* e, int32_t n, int32_t* len);
 
 extern "C" {
 
@@ -60,13 +54,8 @@ int cimg_decompress_batch_device(cimg_engine* e, int32_t n, const void* d_comp, 
 int cimg_compress_batch_device_packed_begin(cimg_engine* e, const cimg_cparams* p, int32_t n, const void* d_raw, const int64_t* raw_off,
                                             const int32_t* nbytes, const int32_t* destsize, int32_t* cbytes)
 {
-    { std::lock_guard<std::mutex> g(g_mu); g_pending.erase(e); }
-    if (n <= 0) return 0;
-    const int rc = cimg_compress_batch_host_begin(e, p, n, d_raw, raw_off, nbytes, destsize, cbytes);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(g_mu);
-    g_pending[e].assign(cbytes, cbytes + n);
-    return 0;
+    // (device memory is host memory: the host _begin stages the batch, and its bookkeeping says when a pending fetch has been voided)
+    return cimg_compress_batch_host_begin(e, p, n, d_raw, raw_off, nbytes, destsize, cbytes);
 }
 
 int cimg_pack_chunks_device(cimg_engine*, int32_t n, const void* const* d_src, const int32_t* bytes, void* d_dst, const int64_t* dst_off)
@@ -77,14 +66,8 @@ int cimg_pack_chunks_device(cimg_engine*, int32_t n, const void* const* d_src, c
 int cimg_compress_batch_device_packed_fetch(cimg_engine* e, int32_t n, void* d_dst, const int64_t* dst_off)
 {
     if (n <= 0) return 0;
-    std::vector<int32_t> len;
-    {
-        std::lock_guard<std::mutex> g(g_mu);
-        auto it = g_pending.find(e);
-        if (it == g_pending.end() || (int32_t)it->second.size() != n) return -12;
-        len = it->second;
-        g_pending.erase(it);
-    }
+    std::vector<int32_t> len((size_t)n);
+    if (cimg_mock_staged_sizes(e, n, len.data())) return -12;
     // out of the staging area (an error if another batch call has reused it since _begin), then through the pack kernel's body
     std::vector<int64_t> off((size_t)n);
     int64_t total = 0;

@@ -11,6 +11,10 @@ using namespace cimg;
 extern "C" int emu_decompress_batch(int nchunks, const uint8_t* comp, const int64_t* comp_off, const int32_t* nbytes,
                                     const int32_t* blocksize, uint8_t* raw, const int64_t* raw_off, int32_t* status);
 
+// mock_cabi.cpp: a host-resident window call goes through the engine's staging area, so a batch staged there by a compress _begin is
+// void after it (include/cimg_hip.h); the host calls of this file and of the files that include it say so through this
+extern "C" void cimg_mock_void_staged(cimg_engine* e);
+
 namespace {
 
 WindowStats g_stats;
@@ -34,9 +38,10 @@ int cimg_decompress_windows_device(cimg_engine*, int32_t nchunks, const void* d_
                               reinterpret_cast<const WindowSpec*>(w), (uint8_t*)d_out, status, &g_stats);
 }
 
-int cimg_decompress_windows_host(cimg_engine*, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
+int cimg_decompress_windows_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off, const int32_t* comp_size,
                                  int32_t nwindows, const cimg_window* w, void* h_out, int32_t* status)
 {
+    if (nchunks > 0 && nwindows > 0) cimg_mock_void_staged(e);
     return emu_windows_host(whole, nchunks, (const uint8_t*)h_comp, comp_off, comp_size, nwindows, reinterpret_cast<const WindowSpec*>(w),
                             (uint8_t*)h_out, status, &g_stats);
 }

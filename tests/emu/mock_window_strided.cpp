@@ -16,10 +16,11 @@ int cimg_decompress_windows_strided_device(cimg_engine*, int32_t nchunks, const 
                                       reinterpret_cast<const StridedWindowSpec*>(w), (uint8_t*)d_out, status, &g_stats);
 }
 
-int cimg_decompress_windows_strided_host(cimg_engine*, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+int cimg_decompress_windows_strided_host(cimg_engine* e, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                                          const int32_t* comp_size, int32_t nwindows, const cimg_window_strided* w, void* h_out,
                                          int32_t* status)
 {
+    if (nchunks > 0 && nwindows > 0) cimg_mock_void_staged(e);
     return emu_windows_strided_host(whole, nchunks, (const uint8_t*)h_comp, comp_off, comp_size, nwindows,
                                     reinterpret_cast<const StridedWindowSpec*>(w), (uint8_t*)h_out, status, &g_stats);
 }

@@ -13,6 +13,10 @@ extern "C" int emu_decompress_batch(int nchunks, const uint8_t* comp, const int6
 extern "C" int emu_compress_batch(const void* p, int nchunks, const uint8_t* raw, const int64_t* raw_off, const int32_t* nbytes,
                                   uint8_t* comp, const int64_t* comp_off, const int32_t* destsize, int32_t* cbytes);
 
+// mock_cabi.cpp: a host-resident window write goes through the engine's staging area, so a batch staged there by a compress _begin is
+// void after it (include/cimg_hip.h); the host calls of this file and of the files that include it say so through this
+extern "C" void cimg_mock_void_staged(cimg_engine* e);
+
 namespace {
 
 UpdateStats g_stats;
@@ -46,11 +50,12 @@ int cimg_update_windows_device(cimg_engine*, const cimg_cparams* p, int32_t nchu
                              (uint8_t*)d_new, new_off, new_cbytes, status, &g_stats);
 }
 
-int cimg_update_windows_host(cimg_engine*, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+int cimg_update_windows_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                              const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window* w,
                              const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes, int32_t* status)
 {
     if (!p) return ERR_INVALID_PARAM;
+    if (nchunks > 0 && nwindows > 0) cimg_mock_void_staged(e);
     return emu_update_host(whole, emu_compress_batch, host_params(p), nchunks, (const uint8_t*)h_comp, comp_off, comp_size, destsize,
                            nwindows, reinterpret_cast<const WindowSpec*>(w), (const uint8_t*)h_src, alloc, user, new_chunks, new_cbytes,
                            status, &g_stats);

@@ -25,12 +25,13 @@ int cimg_update_windows_masked_device(cimg_engine*, const cimg_cparams* p, int32
                                     (const uint8_t*)d_mask, (uint8_t*)d_new, new_off, new_cbytes, status, &g_stats);
 }
 
-int cimg_update_windows_masked_host(cimg_engine*, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+int cimg_update_windows_masked_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                                     const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_masked* w,
                                     const void* h_src, const void* h_mask, cimg_alloc_fn alloc, void* user, void** new_chunks,
                                     int32_t* new_cbytes, int32_t* status)
 {
     if (!p) return ERR_INVALID_PARAM;
+    if (nchunks > 0 && nwindows > 0) cimg_mock_void_staged(e);
     g_masked_update_calls++;
     return emu_update_masked_host(whole, emu_compress_batch, host_params(p), nchunks, (const uint8_t*)h_comp, comp_off, comp_size, destsize,
                                   nwindows, reinterpret_cast<const MaskedWindowSpec*>(w), (const uint8_t*)h_src, (const uint8_t*)h_mask, alloc,

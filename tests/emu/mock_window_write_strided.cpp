@@ -18,12 +18,13 @@ int cimg_update_windows_strided_device(cimg_engine*, const cimg_cparams* p, int3
                                      (uint8_t*)d_new, new_off, new_cbytes, status, &g_stats);
 }
 
-int cimg_update_windows_strided_host(cimg_engine*, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
+int cimg_update_windows_strided_host(cimg_engine* e, const cimg_cparams* p, int32_t nchunks, const void* h_comp, const int64_t* comp_off,
                                      const int32_t* comp_size, const int32_t* destsize, int32_t nwindows, const cimg_window_strided* w,
                                      const void* h_src, cimg_alloc_fn alloc, void* user, void** new_chunks, int32_t* new_cbytes,
                                      int32_t* status)
 {
     if (!p) return ERR_INVALID_PARAM;
+    if (nchunks > 0 && nwindows > 0) cimg_mock_void_staged(e);
     return emu_update_strided_host(whole, emu_compress_batch, host_params(p), nchunks, (const uint8_t*)h_comp, comp_off, comp_size, destsize,
                                    nwindows, reinterpret_cast<const StridedWindowSpec*>(w), (const uint8_t*)h_src, alloc, user, new_chunks,
                                    new_cbytes, status, &g_stats);
